@@ -8,8 +8,8 @@ included); with N > 1 the step ends with ONE RCCL all-reduce of the profile tabl
 torch.distributed).  `value` = all reads of all ranks / max-over-ranks time.
 
   N = 1   BASELINE.json configs[1] (C2): ONE batch of 10 M synthetic 150 bp reads against a ~5 GB k<=12 64-bit index
-          (1400 taxa x 300 kb, sibling genomes 3 % apart; 1 % read errors; -k 12 7, three frames).  The same line also
-          carries `secondary` = configs[2] (C3: the same reads against the 128-bit index, -k 25 7), `tertiary` (a crowded
+          (1400 taxa x 300 kb, sibling genomes 3 % apart; 1 % read errors; -k 12 7, three frames).  With --full the same line
+          also carries `secondary` = configs[2] (C3: the same reads against the 128-bit index, -k 25 7), `tertiary` (a crowded
           index: clades of taxa sharing conserved genes), `quaternary` (long reads: 100 000 x 10 kb reads and two 9.6 Mbp
           contigs against the same index), `e2e` (PCIe-inclusive rates and the file-to-file rate of the
           C++ driver: FASTQ in, JSONL + profile out, index load excluded), `cpu_baseline` (the oracle with the
@@ -17,13 +17,20 @@ torch.distributed).  `value` = all reads of all ranks / max-over-ranks time.
           characters: a reader that keeps the line's tail sees them all).  At N = 1 the process imports no torch: the reads
           lie in plain device buffers of the C ABI and the library runs on the HIP runtime it was built for (`runtime`).
   N > 1   the same 10 M-read batch on EVERY rank, index replicated ("weak": N x 10 M reads per step; N = 1 and N = 8 differ
-          by the reduce only).  The same line carries `c2_strong` = BASELINE.json's metric read literally (10 M reads in all,
+          by the reduce only).  With --full the line carries `c2_strong` = BASELINE.json's metric read literally (10 M reads in all,
           10 M / N per rank) and `c4` = BASELINE.json configs[3]: 100 M reads in all, 100 M / N per rank in batches of at
           most 10 M (both "strong").  `--total-reads T` makes that form the headline instead.
   --partitioned   BASELINE.json configs[4] (C5): the index range-partitioned over the ranks (kasa_amd/dist.py), one
           slice per rank made of the genomes' k-mers of its prefix range plus random filler records.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--taxa G] [--genome-len L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--taxa G] [--genome-len L] [--full] [--dump-outputs DIR]
+
+Without --full a run does what the headline needs and no more: it builds the index and the reads, warms up, times the K
+steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed
+step, the per-stage and per-kernel times of those steps).  --full adds every further leg named above, the live counter
+passes behind `roofline.traffic`, the upload timing and the index's trie cross-check.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs); the inputs are seeded, so two builds given the same arguments can be compared.
+A run that fails ends with its exit code; nothing is measured again.
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N ranks itself, before anything touches a
 GPU; under `python -m torch.distributed.run` it takes RANK / LOCAL_RANK / WORLD_SIZE from the environment.
@@ -130,38 +137,36 @@ def stage_bytes(n_q, n_bases, n_idx, rec_bytes, rec_words, stats):
             "score": kb["score_main_kernel"] + kb["score_other_kernel"] + kb["row_merge_kernel"] + 16 * stats["nnz"]}
 
 
-def run_with_retry():
-    """The default line is measured by a child process (this one has not touched a GPU).  If the child ends without its line
-    it is measured ONCE more -- and the line says so: `attempts`, `retried`, `first_rc` (negative: the signal) and the tail of
-    the failed child's stderr travel in the JSON (round 4 retried silently, which hid an unexplained crash from the record)."""
-    import tempfile
-    cmd = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + ["--child"]
-    rc, first = 1, None
-    for attempt in (1, 2):
-        with tempfile.TemporaryFile(mode="w+") as err:
-            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=err, text=True)
-            err.seek(0)
-            tail = err.read()
-        sys.stderr.write(tail)
-        sys.stderr.flush()
-        lines = [ln for ln in (r.stdout or "").splitlines() if ln.startswith("{")]
-        if r.returncode == 0 and lines:
-            try:
-                out = json.loads(lines[-1])
-                out["attempts"] = attempt
-                out["retried"] = attempt > 1
-                if first is not None:
-                    out["first_rc"], out["first_stderr_tail"] = first
-                print(json.dumps(out), flush=True)
-            except ValueError:
-                sys.stdout.write(r.stdout)
-                sys.stdout.flush()
-            return 0
-        log(f"bench.py: the measuring process ended with code {r.returncode} and {'a' if lines else 'no'} line (attempt {attempt} of 2)")
-        if first is None:
-            first = (r.returncode, tail[-1500:])
-        rc = r.returncode or 1
-    return rc
+DUMP_BYTES = 64 << 20                                  # --dump-outputs: all files together at most this
+DUMP_SAMPLE_READS = 16384                              # reads whose score rows are written (a fixed, seeded sample)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(ctx, out_dir, want_per_read):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float32 / float64 .npy files.
+    The profile tables whole; of the per-read score CSR (the last batch of the step) the rows of a fixed, seeded sample of
+    reads -- taken in the sample's order while they fit the size limit -- plus the batch's read count, nnz and score sum."""
+    os.makedirs(out_dir, exist_ok=True)
+    ca, cu, ct = ctx.profile()
+    arrays = {"profile_count_all": ca.astype(np.float64), "profile_count_unique": cu.astype(np.float64),
+              "profile_count_total": ct.astype(np.float64)}
+    if want_per_read:
+        off, tax, sc = ctx.scores()
+        n = int(off.shape[0] - 1)
+        order = np.random.default_rng(DUMP_SEED).permutation(n)[:min(n, DUMP_SAMPLE_READS)]
+        lens = (off[order + 1] - off[order]).astype(np.int64)
+        budget = (DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 16 * order.shape[0] - 4096) // 12   # 8 + 4 bytes per entry
+        keep = int(np.searchsorted(np.cumsum(lens), budget, side="right"))
+        pick = np.sort(order[:keep])
+        lens = (off[pick + 1] - off[pick]).astype(np.int64)
+        starts = np.repeat(off[pick].astype(np.int64) - np.cumsum(lens) + lens, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+        arrays.update({"scores_read": pick.astype(np.float64), "scores_row_length": lens.astype(np.float64),
+                       "scores_taxon": tax[starts].astype(np.float64), "scores_value": sc[starts].astype(np.float32),
+                       "scores_batch": np.array([n, tax.shape[0], float(np.sum(sc, dtype=np.float64))], dtype=np.float64)})
+        del off, tax, sc
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def launch_ranks(n):
@@ -291,13 +296,15 @@ def measure(args, ctx, world, dist, share, torch, kdist, batches, comm=0):
     for _ in range(args.warmup):
         step()
     fence()
-    # what the per-batch upload costs (geometry kernels, two scans, one 8-byte read-back), timed alone before the run
-    t0 = time.perf_counter()
-    for _ in range(3):
-        ctx.upload_resident(*batches[0])
-    ctx.synchronize()
-    upload_ms = (time.perf_counter() - t0) / 3 * 1e3
-    fence()
+    upload_ms = None
+    if args.full:
+        # what the per-batch upload costs (geometry kernels, two scans, one 8-byte read-back), timed alone before the run
+        t0 = time.perf_counter()
+        for _ in range(3):
+            ctx.upload_resident(*batches[0])
+        ctx.synchronize()
+        upload_ms = (time.perf_counter() - t0) / 3 * 1e3
+        fence()
     ctx.stage_reset()
     acc["reduce_s"] = 0.0
     t0 = time.perf_counter()
@@ -933,12 +940,17 @@ def main():
     ap.add_argument("--debug-flags", type=int, default=0, help="kasa_ctx_debug bits for A/B runs of one kernel choice against another (0 = the product path)")
     ap.add_argument("--partitioned", action="store_true", help="BASELINE.json configs[4]: range-partitioned index (see bench_partitioned)")
     ap.add_argument("--part-records", type=float, default=3.0e9, help="--partitioned: index records per rank (36 GB at 3e9)")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # (set by run_with_retry)
+    ap.add_argument("--full", action="store_true",
+                    help="also every further leg: live counter passes, PCIe-inclusive and file-to-file rates, CPU baseline, the 128-bit, "
+                         "crowded and long-read workloads (N = 1), c2_strong and c4 (N > 1), the upload timing and the index's trie check; "
+                         "without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (profile tables, a seeded sample of the per-read "
+                         "scores) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.dump_outputs and (args.partitioned or args.long_reads):
+        raise SystemExit("--dump-outputs: the read-sharded path only (not --partitioned or --long-reads)")
 
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.child and not args.no_pmc and not args.crowded and not args.long_reads and not args.wide
-            and not args.partitioned and os.environ.get("KASA_BENCH_NO_RETRY") != "1"):
-        raise SystemExit(run_with_retry())             # nothing has touched a GPU in this process
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))      # nothing has touched a GPU in this process
 
@@ -989,7 +1001,7 @@ def main():
 
     holder = {}
 
-    def one(wide, workload="pairs", total_reads=None, legs=True):
+    def one(wide, workload="pairs", total_reads=None, legs=True, dump=False):
         """One measurement: index (wide: 128-bit, -k 25 7) + the rank's reads resident in HBM + measure().
         workload: "pairs" (sibling genomes, BASELINE's synthetic database) or "crowded" (clades sharing conserved genes);
         total_reads: None = --reads on every rank (weak), else that many over all ranks in batches of at most --reads (strong)."""
@@ -1004,7 +1016,7 @@ def main():
         log(f"[rank {rank}] {workload} index: {ix.n} records ({ix.n * rec_bytes / 1e9:.2f} GB on disk layout), "
             f"{ix.trie_prefix.shape[0]} prefixes, {time.perf_counter() - t0:.1f} s")
         t0 = time.perf_counter()
-        dix = capi.DeviceIndex(ix, local_rank, check_trie=True)
+        dix = capi.DeviceIndex(ix, local_rank, check_trie=args.full)   # (the trie cross-check is not the headline's)
         ctx = capi.Context(dix, k_high, k_low, 3)
         if args.debug_flags:
             ctx.debug_flags(args.debug_flags)
@@ -1024,8 +1036,11 @@ def main():
         args.warmup = warm
         out = None
         if rank == 0:
+            if args.dump_outputs and dump:                         # before anything else runs on the context: the last timed step's results
+                names = dump_outputs(ctx, args.dump_outputs, not args.profile_only)
+                log(f"[rank {rank}] outputs of the last step: {', '.join(names)} in {args.dump_outputs}")
             out = report(args, ctx, reads, ix, world, res, wide, per_rank, n_batches, "weak" if total_reads is None else "strong", extra_cfg)
-            if legs and world == 1 and not args.no_e2e and workload == "pairs":
+            if args.full and legs and world == 1 and not args.no_e2e and workload == "pairs":
                 try:                                               # an extra pass: it must never cost the headline line
                     out["e2e"] = pcie_inclusive(ctx, reads, not args.profile_only, ix, k_high, dix, k_low)
                 except Exception as ex:                            # e.g. no memory left for the page-locked buffers
@@ -1038,14 +1053,14 @@ def main():
         del keep, batches
         if torch is not None:
             torch.cuda.empty_cache()
-        if rank == 0 and world == 1 and not wide and legs and workload == "pairs":
+        if args.full and rank == 0 and world == 1 and not wide and legs and workload == "pairs":
             holder["ix"], holder["reads"], holder["k"] = ix, reads, (k_high, k_low)
         if rank == 0 and world == 1 and out["roofline"].get("kernel") and workload == "crowded" and not args.crowded:
             # the crowded workload's dominant kernel: HBM bytes from the counters, measured now (two child passes)
             out["roofline"].update({k: v for k, v in pmc_traffic(args, wide, out["roofline"]["kernel"], not args.no_pmc, crowded=True).items() if k != "insts"})
         if rank == 0 and world == 1 and out["roofline"].get("kernel") and workload == "pairs":
             # HBM bytes of the dominant kernel from the counters (the device is free now)
-            live = not args.no_pmc and (args.pmc_secondary if (wide and not args.wide) else True)
+            live = args.full and not args.no_pmc and (args.pmc_secondary if (wide and not args.wide) else True)
             pm = pmc_traffic(args, wide, out["roofline"]["kernel"], live)
             insts = pm.pop("insts", None)
             out["roofline"].update(pm)
@@ -1066,12 +1081,12 @@ def main():
             print(json.dumps(out), flush=True)
         return
     if args.crowded:
-        out = one(False, workload="crowded", legs=False)
+        out = one(False, workload="crowded", legs=False, dump=True)
         if rank == 0:
             print(json.dumps(out), flush=True)
         return
-    out = one(args.wide, total_reads=args.total_reads)
-    if rank == 0 and world == 1 and not args.wide:
+    out = one(args.wide, total_reads=args.total_reads, dump=True)
+    if args.full and rank == 0 and world == 1 and not args.wide:
         ix, reads, (k_high, k_low) = holder["ix"], holder["reads"], holder["k"]
         if not args.no_e2e and not args.no_f2f:
             try:                                                   # the device is free now: the C++ driver as a child process
@@ -1083,30 +1098,30 @@ def main():
             out["cpu_baseline"] = cpu_baseline_report(ix, reads, k_high, k_low, args)
         holder.clear()
         del ix, reads
-    if world == 1 and not args.wide and not args.no_secondary:
+    if args.full and world == 1 and not args.wide and not args.no_secondary:
         sec = one(True, legs=False)
         if rank == 0 and out is not None and sec is not None:
             out["secondary"] = {k: sec[k] for k in KEEP}
-    if world == 1 and not args.wide and not args.no_tertiary:
+    if args.full and world == 1 and not args.wide and not args.no_tertiary:
         try:
             ter = one(False, workload="crowded", legs=False)
         except Exception as ex:                                     # never lose the headline to the extra workload
             ter = {"error": str(ex)[:400]}
         if rank == 0 and out is not None and ter is not None:
             out["tertiary"] = {k: ter[k] for k in KEEP} if "error" not in ter else ter
-    if world == 1 and not args.wide and not args.no_quaternary:
+    if args.full and world == 1 and not args.wide and not args.no_quaternary:
         try:
             qua = long_reads_leg(args, capi, synth, torch, local_rank)
         except Exception as ex:                                     # never lose the headline to the extra workload
             qua = {"error": str(ex)[:400]}
         if rank == 0 and out is not None:
             out["quaternary"] = qua
-    if world > 1 and args.total_reads is None and not args.no_c2_strong:
+    if args.full and world > 1 and args.total_reads is None and not args.no_c2_strong:
         # BASELINE.json's metric read literally: 10 M reads IN ALL at 1/2/4/8 GPUs ("strong": 10 M / N per rank, one batch each)
         c2s = one(args.wide, total_reads=args.reads, legs=False)
         if rank == 0 and out is not None and c2s is not None:
             out["c2_strong"] = {k: c2s[k] for k in KEEP}
-    if world > 1 and args.total_reads is None and not args.no_c4:
+    if args.full and world > 1 and args.total_reads is None and not args.no_c4:
         c4 = one(args.wide, total_reads=args.c4_reads, legs=False)   # BASELINE.json configs[3]: 100 M reads in all ("strong")
         if rank == 0 and out is not None and c4 is not None:
             out["c4"] = {k: c4[k] for k in KEEP}

@@ -269,7 +269,7 @@ def test_bench_same_step_at_every_n(tmp_path):
     is the only difference) and the line carries `c4` (BASELINE.json configs[3] in small: a fixed total, in batches), the
     per-rank step times and the reduce time.  N = 1 with --total-reads goes through the same loop in several batches."""
     out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "8000", "--c4-reads", "30000",
-                  "--taxa", "8", "--genome-len", "20000", "--no-cpu"])
+                  "--taxa", "8", "--genome-len", "20000", "--no-cpu", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["batches_per_step"] == 1 and out["config"]["reads_per_gpu"] == 8000
     assert out["config"]["total_reads"] == 16000 and len(out["rank_step_ms"]["per_rank"]) == 2 and out["reduce_ms_per_step"] > 0
     assert out["upload_ms_per_batch"] > 0 and 0.5 < out["identified_fraction"] <= 1.0
@@ -290,7 +290,8 @@ def test_bench_default_line_carries_every_leg(tmp_path):
     PCIe-inclusive and the file-to-file rates, the CPU baseline with its one-thread rate, the dominant kernel's HBM traffic from
     counter passes run as children -- all in the one JSON line."""
     out = _bench(["--steps", "1", "--warmup", "1", "--reads", "30000", "--taxa", "8", "--genome-len", "20000",
-                  "--cpu-sample", "5000", "--cpu-sample-parallel", "20000", "--f2f-settle", "0", "--crowded-reads", "10000", "--long-reads-n", "300"], share=False)
+                  "--cpu-sample", "5000", "--cpu-sample-parallel", "20000", "--f2f-settle", "0", "--crowded-reads", "10000", "--long-reads-n", "300",
+                  "--full"], share=False)
     assert out["n_gpus"] == 1 and out["scaling"] == "weak" and out["dtype"] == "u64"
     assert out["secondary"]["dtype"] == "u128" and out["secondary"]["value"] > 0
     assert out["tertiary"]["value"] > 0 and out["tertiary"]["config"]["database"] == "crowded" and out["tertiary"]["config"]["reads_per_gpu"] == 10000
@@ -309,6 +310,40 @@ def test_bench_default_line_carries_every_leg(tmp_path):
     assert q["contig_different_genomes"]["replay_reads"] == 1 and q["contig_one_genome_32_times"]["replay_events"] > 0
     if out["roofline"].get("third_bound"):
         assert out["roofline"]["third_bound"]["bound"] == "issue" and out["roofline"]["third_bound"]["predicted_ms"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """N = 1 without --full: the headline alone (no further leg in the line), --steps timed steps, and --dump-outputs writes what
+    the last step computed -- the profile tables and a seeded sample of score rows, equal to the same reads run here directly."""
+    from kasa_amd import synth
+    d = tmp_path / "out"
+    out = _bench(["--steps", "3", "--warmup", "1", "--reads", "30000", "--taxa", "8", "--genome-len", "20000",
+                  "--dump-outputs", str(d)], share=False)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "u64" and out["higher_is_better"] is True
+    assert out["metric"].startswith("reads/s in identify") and out["unit"] == "reads/s"
+    for leg in ("secondary", "tertiary", "quaternary", "e2e", "cpu_baseline", "c2_strong", "c4"):
+        assert leg not in out
+    got = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+    assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    g = synth.genomes(8, 20000, seed=11)
+    ix = synth.index_from_genomes(g, device=0)
+    r = synth.reads_from_genomes(g, 30000, 150, seed=1000)
+    dix = capi.DeviceIndex(ix)
+    ctx = capi.Context(dix, 12, 7, 3)
+    ctx.run_batch(r.bases, r.offsets, True)
+    ca, cu, ct = ctx.profile()
+    off, tax, sc = ctx.scores()
+    ctx.close(); dix.close()
+    assert np.array_equal(got["profile_count_all"], ca) and np.array_equal(got["profile_count_unique"], cu.astype(np.float64))
+    assert np.array_equal(got["profile_count_total"], ct.astype(np.float64))
+    pick = got["scores_read"].astype(np.int64)
+    assert pick.shape[0] > 1000 and np.all(np.diff(pick) > 0)
+    rows = [np.arange(int(off[i]), int(off[i + 1])) for i in pick]
+    assert np.array_equal(got["scores_row_length"], np.array([x.shape[0] for x in rows], dtype=np.float64))
+    at = np.concatenate(rows)
+    assert np.array_equal(got["scores_taxon"], tax[at].astype(np.float64)) and np.array_equal(got["scores_value"], sc[at])
+    assert got["scores_batch"][0] == 30000 and got["scores_batch"][1] == tax.shape[0]
 
 
 def test_c_abi_reduce_with_a_communicator_of_its_own(tmp_path):

@@ -96,7 +96,7 @@ if PMC_ONLY or WIDE or CROWDED:
             ins = e["SQ_INSTS_VALU"] + e["SQ_INSTS_SALU"]
             print("%-24s insts %.2fe9 -> %.1f ms at 4 cycles; HBM %.1f GB" % (k, ins / 1e9, ins * 4 / (1024 * 2.4e9) * 1e3, e.get("hbm_bytes_per_launch", 0) / 1e9))
     sys.exit(0)
-args = ["python3", "bench.py", "--steps", "5", "--warmup", "2"]          # (secondary, file to file and CPU baseline are part of the default line)
+args = ["python3", "bench.py", "--steps", "5", "--warmup", "2", "--full"]          # (secondary, file to file and CPU baseline are legs of --full)
 with open(os.path.join(out, tag + "_bench_1gpu.json"), "w") as f:
     run(args, stdout=f, stderr=subprocess.DEVNULL)
 print(open(os.path.join(out, tag + "_bench_1gpu.json")).read()[:600])
