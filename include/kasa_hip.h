@@ -457,6 +457,39 @@ int kasa_ctx_record_placement(kasa_ctx *ctx, uint32_t *candidates, float *keptRa
 int kasa_ctx_debug(kasa_ctx *ctx, int forceSlowScore, uint32_t *lastSlowReads);
 int kasa_ctx_synchronize(kasa_ctx *ctx);
 
+/* ---- build: the index files from a database, on the device -----------------------------------------------------------
+ * kASA's `build` (main.cpp:628-686 -> kASA.hpp:449-575 BuildAll): sequences tagged with tax IDs -> every '^'-padded window
+ * of K letters (Read.hpp:2928-3176), sorted by (k-mer, tax ID) and made unique (Build.hpp:305-477), the prefix trie of 6
+ * letters (Trie.hpp:365-394) and the frequency rows of `_f.txt` (kASA.hpp:517-526).  The reference goes through in-RAM
+ * bricks, STXXL temporary files and a k-way merge; here a brick is encoded, sorted and made unique on the device, its run
+ * stays in device memory, and the runs are merged there.
+ *   kasa_build_create  K = 12 (64-bit index) or 25 (128-bit, --kH 25); frames = 3, or 1 (--one); codonLut = NULL: the built-in
+ *                      table (-a gc.prt id: the host's table over kasa_builtin_codon_table); taxIds[nTaxa] = the content file's tax IDs
+ *                      (entry 0 = 0, as for kasa_index_create; nTaxa < 2^22); maxPairsPerBrick = pairs the encoder emits
+ *                      per brick (0 = automatic, from the device's free memory; tests force many bricks on tiny inputs).
+ *   kasa_build_add     any number of calls, as a parser hands sequences over: nSeq sequences (bases, offsets[nSeq + 1]),
+ *                      seqTaxId[s] one of taxIds (KASA_E_ARG otherwise: unknown accessions are the host's to skip,
+ *                      Read.hpp:2352-2368), protein = amino-acid letters (kASA::detectAlphabet per file).
+ *   kasa_build_finish  the last brick, the merges (KASA_E_LIMIT when the unique result plus one merge buffer does not fit
+ *                      the device), records, trie and frequencies.  nRecords = unique (k-mer, tax ID) entries, nTrie =
+ *                      trie entries.
+ *   kasa_build_fetch   records: nRecords packed file records, 12 bytes {u64 kmer, u32 taxid} or 20 bytes {u64 lo, u64 hi,
+ *                      u32 taxid}; triePrefix / trieCount: nTrie entries of the `_trie` file; freq: nTaxa x K, row r =
+ *                      content row r, column j = entries whose letter j from the right is not '^' (k = K - j).  Any may
+ *                      be NULL.  kasa_build_fetch_range: records [first, first + count) only (a host writes while it copies).
+ *   kasa_build_stats   stats8 = {pairs in, bricks, merges of two runs, records out, device microseconds of encode,
+ *                      sort + unique, merge, emit (records, trie, frequencies)}.
+ * Counts and offsets are 64-bit: the 2^32-record limit of kasa_index_create is identify's, not the build's. */
+typedef struct kasa_builder kasa_builder;
+int kasa_build_create(int device, int K, int frames, const uint8_t *codonLut, const uint32_t *taxIds, uint32_t nTaxa,
+                      uint64_t maxPairsPerBrick, kasa_builder **out);
+int kasa_build_add(kasa_builder *b, const uint8_t *bases, const int64_t *offsets, int64_t nSeq, const uint32_t *seqTaxId, int protein);
+int kasa_build_finish(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie);
+int kasa_build_fetch(kasa_builder *b, void *records, uint32_t *triePrefix, uint64_t *trieCount, uint64_t *freq);
+int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t count, void *records);
+int kasa_build_stats(kasa_builder *b, uint64_t *stats8);
+void kasa_build_destroy(kasa_builder *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ EXPORTS = [
     "kasa_batch_records_import_device", "kasa_batch_records_inbox", "kasa_batch_coherence",
     "kasa_ctx_set_taxa_text", "kasa_batch_text", "kasa_batch_text_fetch", "kasa_batch_text_fetch_range", "kasa_text_dtoa", "kasa_ctx_reserve", "kasa_runtime_versions", "kasa_ctx_group_tiles", "kasa_ctx_dense_reads", "kasa_ctx_replay_stats", "kasa_ctx_group_second_chance", "kasa_ctx_record_placement",
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
+    "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
 ]
 
 
@@ -160,6 +161,14 @@ def lib():
         L.kasa_batch_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         L.kasa_batch_rank_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_runtime_versions.argtypes = [C.c_void_p] * 5
+        L.kasa_build_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+        L.kasa_build_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
+        L.kasa_build_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_build_fetch.argtypes = [C.c_void_p] * 5
+        L.kasa_build_fetch_range.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.kasa_build_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_build_destroy.argtypes = [C.c_void_p]
+        L.kasa_build_destroy.restype = None
         _check_runtime(L)
         _lib = L
     return _lib
@@ -413,6 +422,69 @@ class DeviceIndex:
     def close(self):
         if getattr(self, "h", None):
             lib().kasa_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Builder:
+    """`kASA build` on the device (kasa_build_*): sequences tagged with tax IDs -> the records, trie and frequencies of an
+    index.  K = 12 or 25 letters, frames = 3 or 1 (--one); max_pairs_per_brick = 0: sized from the device's free memory."""
+
+    STATS = ("pairs_in", "bricks", "merges", "records_out", "encode_us", "sort_unique_us", "merge_us", "emit_us")
+
+    def __init__(self, taxids, K: int = 12, frames: int = 3, codon_lut=None, max_pairs_per_brick: int = 0, device: int = 0):
+        self.K = K
+        self.taxids = np.ascontiguousarray(taxids, dtype=np.uint32)
+        lut = np.ascontiguousarray(codon_lut, dtype=np.uint8) if codon_lut is not None else None
+        h = C.c_void_p()
+        _check(lib().kasa_build_create(C.c_int(device), C.c_int(K), C.c_int(frames), _p(lut), _p(self.taxids),
+                                       C.c_uint32(self.taxids.shape[0]), C.c_uint64(max_pairs_per_brick), C.byref(h)))
+        self.h = h
+        self.n_records = self.n_trie = None
+
+    def add(self, bases: np.ndarray, offsets: np.ndarray, seq_taxid: np.ndarray, protein: bool = False):
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        seq_taxid = np.ascontiguousarray(seq_taxid, dtype=np.uint32)
+        n = offsets.shape[0] - 1
+        if seq_taxid.shape[0] != n:
+            raise ValueError("one tax ID per sequence")
+        _check(lib().kasa_build_add(self.h, _p(bases), _p(offsets), C.c_int64(n), _p(seq_taxid), C.c_int(1 if protein else 0)))
+
+    def finish(self):
+        n, m = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_build_finish(self.h, C.byref(n), C.byref(m)))
+        self.n_records, self.n_trie = int(n.value), int(m.value)
+        return self.n_records, self.n_trie
+
+    def fetch(self):
+        """(k-mers: u64 or KEY128_DTYPE, tax IDs, trie prefixes, trie counts, freq[nTaxa, K])."""
+        from .formats import REC_DTYPE, REC128_DTYPE, KEY128_DTYPE
+        rec = np.zeros(self.n_records, dtype=REC128_DTYPE if self.K == 25 else REC_DTYPE)
+        tp = np.zeros(self.n_trie, dtype=np.uint32)
+        tc = np.zeros(self.n_trie, dtype=np.uint64)
+        freq = np.zeros((self.taxids.shape[0], self.K), dtype=np.uint64)
+        _check(lib().kasa_build_fetch(self.h, _p(rec), _p(tp), _p(tc), _p(freq)))
+        if self.K == 25:
+            km = np.zeros(self.n_records, dtype=KEY128_DTYPE)
+            km["lo"], km["hi"] = rec["lo"], rec["hi"]
+        else:
+            km = np.ascontiguousarray(rec["kmer"])
+        return km, np.ascontiguousarray(rec["tax"]), tp, tc, freq
+
+    def stats(self) -> dict:
+        s = np.zeros(8, dtype=np.uint64)
+        _check(lib().kasa_build_stats(self.h, _p(s)))
+        return dict(zip(self.STATS, (int(x) for x in s)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().kasa_build_destroy(self.h)
             self.h = None
 
     def __del__(self):

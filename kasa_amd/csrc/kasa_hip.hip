@@ -8207,3 +8207,8 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
     HIPCHK(hipStreamSynchronize(c->stream));
     return KASA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// build: the index files from a database on the device (kasa_build_*)
+// ------------------------------------------------------------------------------------------------
+#include "kasa_build.h"

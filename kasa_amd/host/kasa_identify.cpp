@@ -6,7 +6,7 @@
 // (source/modes/Compare.hpp:2733) does per batch on the CPU is delegated to libkasa_hip.so; everything in this
 // file is host logic: argument parsing, file formats, FASTA/FASTQ reading, ranking, text.
 //
-// Modes: identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
+// Modes: build (main.cpp:628-686, the index files made on the device: kasa_build_*), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
 // (index replicated, one RCCL all-reduce of the profile tables).  Input is streamed in chunks, batches are cut where the
 // reference cuts them (-m) and parsed / computed / written in a pipeline.
 // Not supported here (reported as errors, never silently ignored): --visualize; --coherence together with -e or paired-end input.  128-bit indices (build --kH 25) are read as they are (20-byte records).
@@ -34,6 +34,7 @@
 #include <string_view>
 #include <thread>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 
 #include <dirent.h>
@@ -1956,6 +1957,191 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// build (main.cpp:628-686 -> Read::BuildAll, Read.hpp:2928-3176): the index files from a database, on the device
+// ---------------------------------------------------------------------------------------------------
+// The content file as the build reads it (Read.hpp:2958-3006): accession -> tax ID from column 4 (';'-separated); the tax ID
+// is column 2, or column 5 from the first line with five columns on; the first line that names an accession keeps it.
+struct BuildContent { Content c; std::unordered_map<string, uint32_t> accToTax; };
+static BuildContent loadBuildContent(const string &path)
+{
+    gzFile g = gzopen(path.c_str(), "rb");
+    if (!g) throw std::runtime_error("Content file not found.");
+    string text; vector<char> buf(1 << 20); int n;
+    while ((n = gzread(g, buf.data(), (unsigned)buf.size())) > 0) text.append(buf.data(), (size_t)n);
+    gzclose(g);
+    BuildContent bc; bc.c.names.push_back("non_unique"); bc.c.taxids.push_back(0);
+    bool asStr = false;
+    std::stringstream ss(text); string line;
+    while (std::getline(ss, line)) {
+        if (line.empty()) continue;
+        const auto cols = splitTabs(line);
+        if (cols.size() >= 5) asStr = true;
+        if (cols.size() < 4) throw std::runtime_error("Content file contains less than 4 columns, it may be damaged... The faulty line was: " + line + "\n");
+        if (asStr && cols.size() < 5) throw std::runtime_error("Content file: tax IDs are in column 5 from an earlier line on, this line has 4 columns: " + line);
+        const uint32_t tid = (uint32_t)std::stoul(asStr ? cols[4] : cols[1]);
+        string nm = cols[0]; nm.erase(std::remove(nm.begin(), nm.end(), ','), nm.end());
+        bc.c.names.push_back(nm); bc.c.taxids.push_back(tid);
+        std::stringstream accs(cols[3]); string acc;
+        while (std::getline(accs, acc, ';')) bc.accToTax.emplace(acc, tid);
+    }
+    return bc;
+}
+
+// Read.hpp:2343-2366: the first word of the header split at '|', the first field with a '.' is the accession; an accession
+// that is not listed sends the whole header to the table.  false: not listed at all (the reference skips the sequence).
+static bool taxOfHeader(std::string_view header, const std::unordered_map<string, uint32_t> &accToTax, uint32_t &tax)
+{
+    const std::string_view word = header.substr(0, header.find(' '));
+    string acc;
+    for (size_t a = 0;;) {
+        const size_t b = word.find('|', a);
+        const std::string_view f = word.substr(a, b == std::string_view::npos ? std::string_view::npos : b - a);
+        if (f.find('.') != std::string_view::npos) { acc.assign(f); break; }
+        if (b == std::string_view::npos) break;
+        a = b + 1;
+    }
+    auto it = accToTax.find(acc);
+    if (it == accToTax.end()) it = accToTax.find(string(header));
+    if (it == accToTax.end()) return false;
+    tax = it->second;
+    return true;
+}
+
+static int buildMode(const vector<string> &a)
+{
+    string input, contentPath, index, codonFile, codonId;
+    int kH = 12, frames = 3, device = 0;
+    unsigned threads = 1;
+    int64_t memoryGiB = 5;
+    bool verbose = false;
+    for (size_t i = 2; i < a.size(); ++i) {
+        const string &s = a[i];
+        auto next = [&]() -> string { if (i + 1 >= a.size()) throw std::runtime_error("missing value after " + s); return a[++i]; };
+        if (s == "-i" || s == "--input") input = next();
+        else if (s == "-c" || s == "--content") contentPath = next();
+        else if (s == "-d" || s == "--database") index = next();
+        else if (s == "--kH") kH = std::stoi(next());
+        else if (s == "-k") { kH = std::stoi(next()); (void)next(); }
+        else if (s == "-a" || s == "--alphabet") { codonFile = next(); codonId = next(); }
+        else if (s == "--one") frames = 1;
+        else if (s == "--three") frames = 3;
+        else if (s == "-m" || s == "--memory") { const string v = next(); memoryGiB = v == "inf" ? (1 << 30) : std::stoll(v); }
+        else if (s == "-n" || s == "--threads") threads = (unsigned)std::max(1, std::stoi(next()));
+        else if (s == "--device") device = std::stoi(next());
+        else if (s == "-t" || s == "--temp") next();                                 // no temporary files: the runs stay in device memory
+        else if (s == "-v" || s == "--verbose") verbose = true;
+        else if (s == "-g" || s == "--percentage") throw std::runtime_error("parameter " + s + " (a percentage of the k-mers) is not supported by the MI355X build path");
+        else if (s == "--continue") throw std::runtime_error("parameter --continue is not supported by the MI355X build path: build the index in one run");
+        else if (s == "--spaced") throw std::runtime_error("parameter --spaced is not supported by the MI355X build path");
+        else if (s == "-f" || s == "--acc2tax" || s == "-y" || s == "--taxonomy" || s == "-u" || s == "--level")
+            throw std::runtime_error("parameter " + s + ": generating a content file from the taxonomy is not supported by the MI355X build path; give one with -c");
+        else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
+    }
+    if (contentPath.empty()) throw std::runtime_error("no content file given (-c): generating one from the taxonomy is not supported by the MI355X build path");
+    if (index.empty()) throw std::runtime_error("no index given (-d)");
+    if (input.empty()) throw std::runtime_error("Input file not found");
+    if ((double)memoryGiB * 0.9 < 1.0) throw std::runtime_error("Not enough memory given!");   // main.cpp:658-660
+    const int K = kH > 12 ? 25 : 12;                                                          // main.cpp:629
+    const auto t0 = std::chrono::steady_clock::now();
+    auto secs = [](std::chrono::steady_clock::time_point x) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - x).count(); };
+    const BuildContent bc = loadBuildContent(contentPath);
+    vector<uint8_t> lut;
+    if (!codonFile.empty()) lut = codonTableFromFile(codonFile, codonId);
+    kasa_builder *b = nullptr;
+    const char *brickEnv = getenv("KASA_BUILD_BRICK_PAIRS");                                 // tests: many bricks on a small database
+    if (kasa_build_create(device, K, frames, lut.empty() ? nullptr : lut.data(), bc.c.taxids.data(), (uint32_t)bc.c.taxids.size(),
+                          brickEnv ? (uint64_t)atoll(brickEnv) : 0, &b)) throwLast();
+    std::unique_ptr<kasa_builder, void (*)(kasa_builder *)> guard(b, kasa_build_destroy);
+    double tParse = 0, tAdd = 0;
+    uint64_t nSeq = 0, nSkipped = 0;
+    for (const string &file : gatherFiles(input)) {
+        if (verbose) std::cout << "OUT: Reading " << file << std::endl;
+        if (!std::ifstream(file)) throw std::runtime_error("Input file not found");
+        ChunkReader cr(file);
+        const char *chunk; size_t chunkBytes; ReadSet rs; vector<ReadSet> parts;
+        vector<int64_t> off; vector<uint32_t> tax; HugeVec<uint8_t> bases;
+        for (;;) {
+            auto tp = std::chrono::steady_clock::now();
+            if (!cr.next(chunk, chunkBytes, verbose)) break;
+            if (!cr.fasta) throw std::runtime_error("No > found in input.");                  // Read.hpp:2372
+            rs.clear();
+            parsePiece(chunk, chunkBytes, cr.fasta, threads, 8u << 20, rs, parts, cr.chunkStart);
+            // the sequences the content file lists, back to back
+            off.assign(1, 0); tax.clear(); bases.clear(); bases.reserve(rs.bases.size());
+            for (size_t r = 0; r < rs.size(); ++r) {
+                std::string_view nm = rs.name(r);
+                if (!nm.empty() && nm.back() == ' ') nm.remove_suffix(1);                     // (the reader's trailing space)
+                uint32_t t;
+                if (!taxOfHeader(nm, bc.accToTax, t)) { ++nSkipped; continue; }
+                bases.append(rs.bases.data() + rs.off[r], (size_t)(rs.off[r + 1] - rs.off[r]));
+                off.push_back((int64_t)bases.size());
+                tax.push_back(t);
+            }
+            tParse += secs(tp);
+            tp = std::chrono::steady_clock::now();
+            nSeq += tax.size();
+            if (!tax.empty() && kasa_build_add(b, bases.data(), off.data(), (int64_t)tax.size(), tax.data(), cr.protein ? 1 : 0)) throwLast();
+            tAdd += secs(tp);
+        }
+    }
+    if (verbose && nSkipped) std::cout << "OUT: " << nSkipped << " sequence(s) without an accession of the content file were skipped" << std::endl;
+    auto tf = std::chrono::steady_clock::now();
+    uint64_t nRec = 0, nTrie = 0;
+    if (kasa_build_finish(b, &nRec, &nTrie)) throwLast();
+    const double tFinish = secs(tf);
+    if (nRec == 0) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
+    // files: records, _info.txt, _trie, _trie.txt, _f.txt (formats.write_index's layout)
+    tf = std::chrono::steady_clock::now();
+    const size_t nTaxa = bc.c.taxids.size(), recBytes = K == 25 ? 20 : 12;
+    vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie), freq(nTaxa * (size_t)K);
+    if (kasa_build_fetch(b, nullptr, tp.data(), tc.data(), freq.data())) throwLast();
+    {
+        FILE *f = fopen(index.c_str(), "wb");
+        if (!f) throw std::runtime_error("The index file cannot be written: " + index);
+        const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
+        vector<uint8_t> bufs[2] = {vector<uint8_t>((size_t)std::min(step, nRec) * recBytes), vector<uint8_t>((size_t)std::min(step, nRec) * recBytes)};
+        std::future<size_t> pending;                                                          // a range is written while the next one is copied
+        int cur = 0;
+        for (uint64_t first = 0; first < nRec; first += step) {
+            const uint64_t cnt = std::min(step, nRec - first);
+            if (kasa_build_fetch_range(b, first, cnt, bufs[cur].data())) throwLast();
+            if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
+            const uint8_t *src = bufs[cur].data(); const size_t bytes = (size_t)cnt * recBytes;
+            pending = std::async(std::launch::async, [f, src, bytes] { return fwrite(src, 1, bytes, f) == bytes ? bytes + 1 : (size_t)0; });
+            cur ^= 1;
+        }
+        if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
+        if (fclose(f) != 0) throw std::runtime_error("writing the index file failed");
+    }
+    { std::ofstream f(index + "_info.txt", std::ios::binary); f << nRec; if (K == 25) f << "\n128"; }
+    {
+        vector<uint8_t> t(nTrie * 12);
+        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
+        std::ofstream f(index + "_trie", std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
+        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
+    }
+    {
+        string out;
+        for (size_t r = 0; r < nTaxa; ++r) {
+            out += bc.c.names[r];
+            for (int j = 0; j < K; ++j) { out += '\t'; out += std::to_string(freq[r * (size_t)K + j]); }
+            out += '\n';
+        }
+        std::ofstream f(index + "_f.txt", std::ios::binary); f << out;
+    }
+    const double tWrite = secs(tf);
+    uint64_t st[8] = {0};
+    if (kasa_build_stats(b, st)) throwLast();
+    std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries, from " << nSeq << " sequence(s)" << std::endl;
+    if (getenv("KASA_BUILD_TIMING") || verbose)
+        std::cout << "OUT: build timing: parse " << tParse << " s, add " << tAdd << " s, finish " << tFinish << " s, write " << tWrite << " s, total " << secs(t0)
+                  << " s; pairs " << st[0] << ", bricks " << st[1] << ", merges " << st[2] << ", device ms encode " << st[4] / 1e3 << " sort+unique " << st[5] / 1e3
+                  << " merge " << st[6] / 1e3 << " emit " << st[7] / 1e3 << std::endl;
+    std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
+    return 0;
+}
+
 static int run(int argc, char **argv)
 {
     vector<string> a(argv, argv + argc);
@@ -2007,7 +2193,8 @@ static int run(int argc, char **argv)
         }
         return 0;
     }
-    if (argc < 2 || (a[1] != "identify" && a[1] != "identify_multiple")) throw std::runtime_error("only the modes `identify` and `identify_multiple` are available on this path");
+    if (argc >= 2 && a[1] == "build") return buildMode(a);
+    if (argc < 2 || (a[1] != "identify" && a[1] != "identify_multiple")) throw std::runtime_error("only the modes `build`, `identify` and `identify_multiple` are available on this path");
     Params p;
     p.mode = a[1];
     int frameFlags = 0;
