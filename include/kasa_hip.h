@@ -490,6 +490,34 @@ int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t count, void
 int kasa_build_stats(kasa_builder *b, uint64_t *stats8);
 void kasa_build_destroy(kasa_builder *b);
 
+/* ---- edit: update, delete and shrink an existing index, on the device ------------------------------------------------
+ * kASA's `update` (Update.hpp:99-180: the sorted union of the old records and those `build` makes of new sequences),
+ * `delete` (Update.hpp:28-90: the records of the taxa delnodes.dmp does not list, in order), `shrink` (Shrink.hpp:152-370)
+ * and `getFrequency` (main.cpp:1336-1362) on a builder.  An existing index is one more sorted run: kasa_build_finish merges
+ * the brick runs, then every index run once with that result, then drops the taxa, then shrinks, then writes records,
+ * trie and frequencies as for a build.  A builder that calls none of these behaves as before.
+ *   kasa_build_add_index   records [first, first + count) of an index run of `total` packed file records (12 or 20 bytes,
+ *                          as kasa_build_fetch writes them, the width of the builder's K).  first = 0 starts a run; the calls
+ *                          of a run cover [0, total) in order.  KASA_E_ARG names the record and its tax ID when the tax ID
+ *                          is not one of taxIds, or when a record does not follow its predecessor in strict (k-mer, tax
+ *                          ID) order (unsorted input, a duplicate); the run is then discarded.
+ *   kasa_build_drop_taxa   the records of these tax IDs go (delete -l delnodes.dmp).  Calls combine as a union; IDs that no
+ *                          record carries are ignored.
+ *   kasa_build_shrink      once per builder.  strategy 1: per taxon, the j-th record in index order (j = 1, 2, ...) goes iff
+ *                          j == (uint64_t)d_m for some m, d_1 = step = 100.0 / fabsf(percentage) in double, d_m+1 = d_m +
+ *                          step (no record goes when step < 1 or percentage = 0).  2: the halved index (64-bit K only, at most
+ *                          65535 content rows with row 0): records with fewer than seven real letters go, the others are
+ *                          fetched as 6-byte records {u32 low 30 bits of the k-mer, u16 content row} and the frequencies
+ *                          are those of the full index.  3: records whose normalised Shannon entropy of the K letters
+ *                          ('^' included) is 0.5 or less go.  A shrink that leaves no record fails kasa_build_finish
+ *                          with KASA_E_ARG.
+ *   kasa_build_edit_stats  stats4 = {index records in, dropped by delete, dropped by shrink, device microseconds of the
+ *                          loads and the filters}. */
+int kasa_build_add_index(kasa_builder *b, uint64_t first, uint64_t count, uint64_t total, const void *records);
+int kasa_build_drop_taxa(kasa_builder *b, const uint32_t *taxIds, uint64_t n);
+int kasa_build_shrink(kasa_builder *b, int strategy, float percentage);
+int kasa_build_edit_stats(kasa_builder *b, uint64_t *stats4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ EXPORTS = [
     "kasa_ctx_set_taxa_text", "kasa_batch_text", "kasa_batch_text_fetch", "kasa_batch_text_fetch_range", "kasa_text_dtoa", "kasa_ctx_reserve", "kasa_runtime_versions", "kasa_ctx_group_tiles", "kasa_ctx_dense_reads", "kasa_ctx_replay_stats", "kasa_ctx_group_second_chance", "kasa_ctx_record_placement",
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
+    "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats",
 ]
 
 
@@ -169,6 +170,10 @@ def lib():
         L.kasa_build_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_build_destroy.argtypes = [C.c_void_p]
         L.kasa_build_destroy.restype = None
+        L.kasa_build_add_index.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.kasa_build_drop_taxa.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.kasa_build_shrink.argtypes = [C.c_void_p, C.c_int, C.c_float]
+        L.kasa_build_edit_stats.argtypes = [C.c_void_p, C.c_void_p]
         _check_runtime(L)
         _lib = L
     return _lib
@@ -436,6 +441,7 @@ class Builder:
     index.  K = 12 or 25 letters, frames = 3 or 1 (--one); max_pairs_per_brick = 0: sized from the device's free memory."""
 
     STATS = ("pairs_in", "bricks", "merges", "records_out", "encode_us", "sort_unique_us", "merge_us", "emit_us")
+    EDIT_STATS = ("index_in", "dropped_delete", "dropped_shrink", "edit_us")
 
     def __init__(self, taxids, K: int = 12, frames: int = 3, codon_lut=None, max_pairs_per_brick: int = 0, device: int = 0):
         self.K = K
@@ -462,14 +468,49 @@ class Builder:
         self.n_records, self.n_trie = int(n.value), int(m.value)
         return self.n_records, self.n_trie
 
+    def add_index(self, records: np.ndarray, chunk: int = 0):
+        """An existing index as one more sorted run: records = REC_DTYPE (K = 12) or REC128_DTYPE (K = 25), sorted by (k-mer,
+        tax ID) and unique; chunk > 0 hands them over in pieces of that many records (as a host reading a file does)."""
+        from .formats import REC_DTYPE, REC128_DTYPE
+        rec = np.ascontiguousarray(records, dtype=REC128_DTYPE if self.K == 25 else REC_DTYPE)
+        n = rec.shape[0]
+        step = chunk if chunk > 0 else max(n, 1)
+        first = 0
+        while True:
+            cnt = min(step, n - first)
+            _check(lib().kasa_build_add_index(self.h, C.c_uint64(first), C.c_uint64(cnt), C.c_uint64(n), _p(rec[first:first + cnt]) if cnt else None))
+            first += cnt
+            if first >= n:
+                break
+
+    def drop_taxa(self, taxids):
+        ids = np.ascontiguousarray(taxids, dtype=np.uint32)
+        _check(lib().kasa_build_drop_taxa(self.h, _p(ids), C.c_uint64(ids.shape[0])))
+
+    def shrink(self, strategy: int, percentage: float = 0.0):
+        self.halved = strategy == 2
+        _check(lib().kasa_build_shrink(self.h, C.c_int(strategy), C.c_float(percentage)))
+
+    def edit_stats(self) -> dict:
+        s = np.zeros(4, dtype=np.uint64)
+        _check(lib().kasa_build_edit_stats(self.h, _p(s)))
+        return dict(zip(self.EDIT_STATS, (int(x) for x in s)))
+
     def fetch(self):
-        """(k-mers: u64 or KEY128_DTYPE, tax IDs, trie prefixes, trie counts, freq[nTaxa, K])."""
-        from .formats import REC_DTYPE, REC128_DTYPE, KEY128_DTYPE
-        rec = np.zeros(self.n_records, dtype=REC128_DTYPE if self.K == 25 else REC_DTYPE)
+        """(k-mers: u64 or KEY128_DTYPE, tax IDs, trie prefixes, trie counts, freq[nTaxa, K]).  After shrink(2) the device
+        holds 6-byte records: the k-mers are rebuilt from them and the trie, the tax IDs from the content rows."""
+        from .formats import REC_DTYPE, REC128_DTYPE, KEY128_DTYPE, HALF_DTYPE
+        halved = getattr(self, "halved", False)
+        rec = np.zeros(self.n_records, dtype=HALF_DTYPE if halved else (REC128_DTYPE if self.K == 25 else REC_DTYPE))
         tp = np.zeros(self.n_trie, dtype=np.uint32)
         tc = np.zeros(self.n_trie, dtype=np.uint64)
         freq = np.zeros((self.taxids.shape[0], self.K), dtype=np.uint64)
         _check(lib().kasa_build_fetch(self.h, _p(rec), _p(tp), _p(tc), _p(freq)))
+        self.raw_records = rec
+        if halved:
+            pre = np.repeat(tp.astype(np.uint64), tc.astype(np.int64))
+            km = (pre << np.uint64(30)) | rec["low"].astype(np.uint64)
+            return km, self.taxids[rec["tax"].astype(np.int64)], tp, tc, freq
         if self.K == 25:
             km = np.zeros(self.n_records, dtype=KEY128_DTYPE)
             km["lo"], km["hi"] = rec["lo"], rec["hi"]

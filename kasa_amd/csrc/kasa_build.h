@@ -216,11 +216,26 @@ struct kasa_builder {
     // stats: pairs in, bricks, merges, records out, ms encode / sort+unique / merge / emit
     uint64_t pairsIn = 0, bricks = 0, merges = 0;
     double ms[4] = {0, 0, 0, 0};
+    // editing an existing index (kasa_edit.h): its runs, the taxa to drop, the shrink strategy
+    std::vector<Run> idxRuns;
+    bool loading = false;                  // idxRuns.back() is being loaded: [0, loadNext) of loadTotal records are in
+    uint64_t loadNext = 0, loadTotal = 0;
+    DevBuf loadStage, loadErr;
+    std::vector<uint8_t> dropRank;         // rank -> dropped (kasa_build_drop_taxa); empty: nothing dropped
+    int shrinkStrategy = 0;                // 0: none, 1: every n-th of a taxon, 2: halved, 3: entropy
+    float shrinkP = 0.f;
+    bool halved = false, freqDone = false;
+    uint64_t indexIn = 0, droppedDelete = 0, droppedShrink = 0;
+    double msEdit = 0;                     // device ms of the loads and the filters
     int keyBytes() const { return wide ? 16 : 8; }
-    int recBytes() const { return wide ? 20 : 12; }
+    int recBytes() const { return halved ? 6 : (wide ? 20 : 12); }
 };
 
 namespace kasa_build_impl {
+
+// kasa_edit.h: the index runs' merges and the filters after the brick merges; the 6-byte records of a halved index
+template <class Key> static int edit_finish(kasa_builder *b);
+template <class Key> static int edit_emit_halved(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n);
 
 // elapsed device time of a stage: events around it, read after the stream has drained
 struct StageClock {
@@ -392,6 +407,30 @@ static int merge_two(kasa_builder *b, kasa_builder::Run &A, kasa_builder::Run &B
     return KASA_OK;
 }
 
+// the frequency rows by rank of the run (k, v, n) into b->freqR
+template <class Key>
+static int freq_into(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n)
+{
+    const uint32_t nRank = (uint32_t)b->ids.size();
+    constexpr int KL = KeyTraits<Key>::LETTERS;
+    int rc;
+    DevBuf hist, extra;
+    if ((rc = b->freqR.reserve((size_t)nRank * KL * 8 + 64)) || (rc = hist.reserve((size_t)nRank * (KL + 1) * 8 + 64)) || (rc = extra.reserve((size_t)nRank * KL * 8 + 64))) return rc;
+    HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nRank * (KL + 1) * 8, b->stream));
+    HIPCHK(hipMemsetAsync(extra.p, 0, (size_t)nRank * KL * 8, b->stream));
+    if (n) {
+        if ((uint64_t)nRank * (KL + 1) <= (uint64_t)FREQ_LDS_CELLS)
+            bld_freq_kernel<Key, true><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
+        else
+            bld_freq_kernel<Key, false><<<grid_for(n, 256, 8192), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+    }
+    bld_freq_final_kernel<<<blocks_for(nRank, 256), 256, 0, b->stream>>>(hist.as<unsigned long long>(), extra.as<unsigned long long>(), nRank, KL, b->freqR.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(b->stream));                          // (hist and extra go out of scope here)
+    return KASA_OK;
+}
+
 template <class Key>
 static int finish_impl(kasa_builder *b)
 {
@@ -417,15 +456,16 @@ static int finish_impl(kasa_builder *b)
     if (b->runs.empty()) b->runs.emplace_back();
     b->result = std::move(b->runs[0]);
     b->runs.clear();
+    if ((rc = edit_finish<Key>(b))) return rc;                       // nothing when no kasa_build_add_index/drop_taxa/shrink was called
     const uint64_t n = b->result.n;
     const Key *k = b->result.k.as<Key>();
     const uint32_t *v = b->result.v.as<uint32_t>();
-    const uint32_t nRank = (uint32_t)b->ids.size();
     constexpr int KL = KeyTraits<Key>::LETTERS;
     StageClock clk(&b->ms[3], b->stream);
-    if ((rc = b->rec.reserve(n * (uint64_t)b->recBytes() + 64)) || (rc = b->freqR.reserve((size_t)nRank * KL * 8 + 64))) return rc;
+    if ((rc = b->rec.reserve(n * (uint64_t)b->recBytes() + 64))) return rc;
     if (n) {
-        bld_emit_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, v, n, b->idOfRank.as<uint32_t>(), b->rec.as<uint32_t>());
+        if (b->halved) { if ((rc = edit_emit_halved<Key>(b, k, v, n))) return rc; }
+        else bld_emit_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, v, n, b->idOfRank.as<uint32_t>(), b->rec.as<uint32_t>());
         HIPCHK(hipGetLastError());
         // trie
         const int shift = 5 * (KL - RANGE_LETTERS);
@@ -451,20 +491,7 @@ static int finish_impl(kasa_builder *b)
         bld_trie_count_kernel<<<grid_for(b->nTrie), 256, 0, b->stream>>>(b->trieFirst.as<uint64_t>(), b->nTrie, n, b->trieCount.as<uint64_t>());
         HIPCHK(hipGetLastError());
     } else b->nTrie = 0;
-    // frequencies
-    DevBuf hist, extra;
-    if ((rc = hist.reserve((size_t)nRank * (KL + 1) * 8 + 64)) || (rc = extra.reserve((size_t)nRank * KL * 8 + 64))) return rc;
-    HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nRank * (KL + 1) * 8, b->stream));
-    HIPCHK(hipMemsetAsync(extra.p, 0, (size_t)nRank * KL * 8, b->stream));
-    if (n) {
-        if ((uint64_t)nRank * (KL + 1) <= (uint64_t)FREQ_LDS_CELLS)
-            bld_freq_kernel<Key, true><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
-        else
-            bld_freq_kernel<Key, false><<<grid_for(n, 256, 8192), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
-        HIPCHK(hipGetLastError());
-    }
-    bld_freq_final_kernel<<<blocks_for(nRank, 256), 256, 0, b->stream>>>(hist.as<unsigned long long>(), extra.as<unsigned long long>(), nRank, KL, b->freqR.as<uint64_t>());
-    HIPCHK(hipGetLastError());
+    if (!b->freqDone && (rc = freq_into<Key>(b, k, v, n))) return rc;  // (a halved index keeps the frequencies of the full one)
     clk.stop();
     HIPCHK(hipStreamSynchronize(b->stream));
     b->result.k.release(); b->result.v.release();

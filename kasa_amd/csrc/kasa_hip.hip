@@ -8212,3 +8212,4 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
 // build: the index files from a database on the device (kasa_build_*)
 // ------------------------------------------------------------------------------------------------
 #include "kasa_build.h"
+#include "kasa_edit.h"

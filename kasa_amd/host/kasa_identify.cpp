@@ -6,7 +6,8 @@
 // (source/modes/Compare.hpp:2733) does per batch on the CPU is delegated to libkasa_hip.so; everything in this
 // file is host logic: argument parsing, file formats, FASTA/FASTQ reading, ranking, text.
 //
-// Modes: build (main.cpp:628-686, the index files made on the device: kasa_build_*), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
+// Modes: build (main.cpp:628-686, the index files made on the device: kasa_build_*), update, delete, shrink and getFrequency
+// (main.cpp:699-875, 1336-1362: an existing index edited on the device), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
 // (index replicated, one RCCL all-reduce of the profile tables).  Input is streamed in chunks, batches are cut where the
 // reference cuts them (-m) and parsed / computed / written in a pipeline.
 // Not supported here (reported as errors, never silently ignored): --visualize; --coherence together with -e or paired-end input.  128-bit indices (build --kH 25) are read as they are (20-byte records).
@@ -2008,6 +2009,90 @@ static bool taxOfHeader(std::string_view header, const std::unordered_map<string
     return true;
 }
 
+// the sequences of a database (a file or a folder, .gz too) the content file lists, streamed into the builder
+static void addDatabase(kasa_builder *b, const string &input, const BuildContent &bc, unsigned threads, bool verbose, uint64_t &nSeq, uint64_t &nSkipped,
+                        double &tParse, double &tAdd)
+{
+    auto secs = [](std::chrono::steady_clock::time_point x) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - x).count(); };
+    for (const string &file : gatherFiles(input)) {
+        if (verbose) std::cout << "OUT: Reading " << file << std::endl;
+        if (!std::ifstream(file)) throw std::runtime_error("Input file not found");
+        ChunkReader cr(file);
+        const char *chunk; size_t chunkBytes; ReadSet rs; vector<ReadSet> parts;
+        vector<int64_t> off; vector<uint32_t> tax; HugeVec<uint8_t> bases;
+        for (;;) {
+            auto tp = std::chrono::steady_clock::now();
+            if (!cr.next(chunk, chunkBytes, verbose)) break;
+            if (!cr.fasta) throw std::runtime_error("No > found in input.");                  // Read.hpp:2372
+            rs.clear();
+            parsePiece(chunk, chunkBytes, cr.fasta, threads, 8u << 20, rs, parts, cr.chunkStart);
+            // the sequences the content file lists, back to back
+            off.assign(1, 0); tax.clear(); bases.clear(); bases.reserve(rs.bases.size());
+            for (size_t r = 0; r < rs.size(); ++r) {
+                std::string_view nm = rs.name(r);
+                if (!nm.empty() && nm.back() == ' ') nm.remove_suffix(1);                     // (the reader's trailing space)
+                uint32_t t;
+                if (!taxOfHeader(nm, bc.accToTax, t)) { ++nSkipped; continue; }
+                bases.append(rs.bases.data() + rs.off[r], (size_t)(rs.off[r + 1] - rs.off[r]));
+                off.push_back((int64_t)bases.size());
+                tax.push_back(t);
+            }
+            tParse += secs(tp);
+            tp = std::chrono::steady_clock::now();
+            nSeq += tax.size();
+            if (!tax.empty() && kasa_build_add(b, bases.data(), off.data(), (int64_t)tax.size(), tax.data(), cr.protein ? 1 : 0)) throwLast();
+            tAdd += secs(tp);
+        }
+    }
+}
+
+static void writeFreqFile(const string &path, const Content &c, int K, const vector<uint64_t> &freq)
+{
+    string out;
+    for (size_t r = 0; r < c.taxids.size(); ++r) {
+        out += c.names[r];
+        for (int j = 0; j < K; ++j) { out += '\t'; out += std::to_string(freq[r * (size_t)K + j]); }
+        out += '\n';
+    }
+    std::ofstream f(path, std::ios::binary); f << out;
+    if (!f) throw std::runtime_error("writing " + path + " failed");
+}
+
+// the index files of a finished builder under `prefix` (formats.write_index's layout): records (12, 20 or, halved, 6 bytes),
+// _info.txt (count + infoTail), _trie, _trie.txt and, withFreq, _f.txt
+static void writeIndexFiles(kasa_builder *b, const string &index, const Content &c, int K, uint64_t nRec, uint64_t nTrie, const char *infoTail, bool withFreq)
+{
+    const size_t nTaxa = c.taxids.size(), recBytes = string(infoTail) == "\n3" ? 6 : (K == 25 ? 20 : 12);
+    vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie), freq(nTaxa * (size_t)K);
+    if (kasa_build_fetch(b, nullptr, tp.data(), tc.data(), freq.data())) throwLast();
+    {
+        FILE *f = fopen(index.c_str(), "wb");
+        if (!f) throw std::runtime_error("The index file cannot be written: " + index);
+        const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
+        vector<uint8_t> bufs[2] = {vector<uint8_t>((size_t)std::min(step, nRec) * recBytes), vector<uint8_t>((size_t)std::min(step, nRec) * recBytes)};
+        std::future<size_t> pending;                                                          // a range is written while the next one is copied
+        int cur = 0;
+        for (uint64_t first = 0; first < nRec; first += step) {
+            const uint64_t cnt = std::min(step, nRec - first);
+            if (kasa_build_fetch_range(b, first, cnt, bufs[cur].data())) { if (pending.valid()) pending.get(); fclose(f); throwLast(); }
+            if (pending.valid() && pending.get() == 0) { fclose(f); throw std::runtime_error("writing the index file failed"); }
+            const uint8_t *src = bufs[cur].data(); const size_t bytes = (size_t)cnt * recBytes;
+            pending = std::async(std::launch::async, [f, src, bytes] { return fwrite(src, 1, bytes, f) == bytes ? bytes + 1 : (size_t)0; });
+            cur ^= 1;
+        }
+        if (pending.valid() && pending.get() == 0) { fclose(f); throw std::runtime_error("writing the index file failed"); }
+        if (fclose(f) != 0) throw std::runtime_error("writing the index file failed");
+    }
+    { std::ofstream f(index + "_info.txt", std::ios::binary); f << nRec << infoTail; }
+    {
+        vector<uint8_t> t(nTrie * 12);
+        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
+        std::ofstream f(index + "_trie", std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
+        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
+    }
+    if (withFreq) writeFreqFile(index + "_f.txt", c, K, freq);
+}
+
 static int buildMode(const vector<string> &a)
 {
     string input, contentPath, index, codonFile, codonId;
@@ -2055,36 +2140,7 @@ static int buildMode(const vector<string> &a)
     std::unique_ptr<kasa_builder, void (*)(kasa_builder *)> guard(b, kasa_build_destroy);
     double tParse = 0, tAdd = 0;
     uint64_t nSeq = 0, nSkipped = 0;
-    for (const string &file : gatherFiles(input)) {
-        if (verbose) std::cout << "OUT: Reading " << file << std::endl;
-        if (!std::ifstream(file)) throw std::runtime_error("Input file not found");
-        ChunkReader cr(file);
-        const char *chunk; size_t chunkBytes; ReadSet rs; vector<ReadSet> parts;
-        vector<int64_t> off; vector<uint32_t> tax; HugeVec<uint8_t> bases;
-        for (;;) {
-            auto tp = std::chrono::steady_clock::now();
-            if (!cr.next(chunk, chunkBytes, verbose)) break;
-            if (!cr.fasta) throw std::runtime_error("No > found in input.");                  // Read.hpp:2372
-            rs.clear();
-            parsePiece(chunk, chunkBytes, cr.fasta, threads, 8u << 20, rs, parts, cr.chunkStart);
-            // the sequences the content file lists, back to back
-            off.assign(1, 0); tax.clear(); bases.clear(); bases.reserve(rs.bases.size());
-            for (size_t r = 0; r < rs.size(); ++r) {
-                std::string_view nm = rs.name(r);
-                if (!nm.empty() && nm.back() == ' ') nm.remove_suffix(1);                     // (the reader's trailing space)
-                uint32_t t;
-                if (!taxOfHeader(nm, bc.accToTax, t)) { ++nSkipped; continue; }
-                bases.append(rs.bases.data() + rs.off[r], (size_t)(rs.off[r + 1] - rs.off[r]));
-                off.push_back((int64_t)bases.size());
-                tax.push_back(t);
-            }
-            tParse += secs(tp);
-            tp = std::chrono::steady_clock::now();
-            nSeq += tax.size();
-            if (!tax.empty() && kasa_build_add(b, bases.data(), off.data(), (int64_t)tax.size(), tax.data(), cr.protein ? 1 : 0)) throwLast();
-            tAdd += secs(tp);
-        }
-    }
+    addDatabase(b, input, bc, threads, verbose, nSeq, nSkipped, tParse, tAdd);
     if (verbose && nSkipped) std::cout << "OUT: " << nSkipped << " sequence(s) without an accession of the content file were skipped" << std::endl;
     auto tf = std::chrono::steady_clock::now();
     uint64_t nRec = 0, nTrie = 0;
@@ -2093,43 +2149,7 @@ static int buildMode(const vector<string> &a)
     if (nRec == 0) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
     // files: records, _info.txt, _trie, _trie.txt, _f.txt (formats.write_index's layout)
     tf = std::chrono::steady_clock::now();
-    const size_t nTaxa = bc.c.taxids.size(), recBytes = K == 25 ? 20 : 12;
-    vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie), freq(nTaxa * (size_t)K);
-    if (kasa_build_fetch(b, nullptr, tp.data(), tc.data(), freq.data())) throwLast();
-    {
-        FILE *f = fopen(index.c_str(), "wb");
-        if (!f) throw std::runtime_error("The index file cannot be written: " + index);
-        const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
-        vector<uint8_t> bufs[2] = {vector<uint8_t>((size_t)std::min(step, nRec) * recBytes), vector<uint8_t>((size_t)std::min(step, nRec) * recBytes)};
-        std::future<size_t> pending;                                                          // a range is written while the next one is copied
-        int cur = 0;
-        for (uint64_t first = 0; first < nRec; first += step) {
-            const uint64_t cnt = std::min(step, nRec - first);
-            if (kasa_build_fetch_range(b, first, cnt, bufs[cur].data())) throwLast();
-            if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
-            const uint8_t *src = bufs[cur].data(); const size_t bytes = (size_t)cnt * recBytes;
-            pending = std::async(std::launch::async, [f, src, bytes] { return fwrite(src, 1, bytes, f) == bytes ? bytes + 1 : (size_t)0; });
-            cur ^= 1;
-        }
-        if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
-        if (fclose(f) != 0) throw std::runtime_error("writing the index file failed");
-    }
-    { std::ofstream f(index + "_info.txt", std::ios::binary); f << nRec; if (K == 25) f << "\n128"; }
-    {
-        vector<uint8_t> t(nTrie * 12);
-        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
-        std::ofstream f(index + "_trie", std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
-        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
-    }
-    {
-        string out;
-        for (size_t r = 0; r < nTaxa; ++r) {
-            out += bc.c.names[r];
-            for (int j = 0; j < K; ++j) { out += '\t'; out += std::to_string(freq[r * (size_t)K + j]); }
-            out += '\n';
-        }
-        std::ofstream f(index + "_f.txt", std::ios::binary); f << out;
-    }
+    writeIndexFiles(b, index, bc.c, K, nRec, nTrie, K == 25 ? "\n128" : "", true);
     const double tWrite = secs(tf);
     uint64_t st[8] = {0};
     if (kasa_build_stats(b, st)) throwLast();
@@ -2138,6 +2158,207 @@ static int buildMode(const vector<string> &a)
         std::cout << "OUT: build timing: parse " << tParse << " s, add " << tAdd << " s, finish " << tFinish << " s, write " << tWrite << " s, total " << secs(t0)
                   << " s; pairs " << st[0] << ", bricks " << st[1] << ", merges " << st[2] << ", device ms encode " << st[4] / 1e3 << " sort+unique " << st[5] / 1e3
                   << " merge " << st[6] / 1e3 << " emit " << st[7] / 1e3 << std::endl;
+    std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// update | delete | shrink | getFrequency (main.cpp:699-875, 1336-1362; Update.hpp, Shrink.hpp): an existing index edited on
+// the device (kasa_build_add_index / drop_taxa / shrink).  Outputs go under a temporary name and are renamed at the end, so an
+// error leaves an existing index as it was.
+// ---------------------------------------------------------------------------------------------------
+static void readIndexInfo(const string &index, uint64_t &n, uint64_t &kind)
+{
+    std::ifstream f(index + "_info.txt");
+    if (!f) throw std::runtime_error("Info file for this index can not be found!");
+    n = 0; kind = 0;
+    f >> n;
+    if (!(f >> kind)) kind = 0;
+}
+
+// the records of an index file, in ranges of about 256 MB read while the range before is handed to the builder.  The count
+// is _info.txt's: the zero padding the reference's STXXL writes after the records is not read.
+static void loadIndexRun(kasa_builder *b, const string &index, uint64_t n, size_t recBytes, double &tRead, double &tUpload)
+{
+    FILE *f = fopen(index.c_str(), "rb");
+    if (!f) throw std::runtime_error("The index file cannot be found!");
+    std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
+    struct stat st;
+    if (fstat(fileno(f), &st) != 0 || (uint64_t)st.st_size < n * recBytes) throw std::runtime_error("The index file is shorter than _info.txt says: " + index);
+    const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
+    vector<uint8_t> bufs[2] = {vector<uint8_t>((size_t)std::min(step, n) * recBytes), vector<uint8_t>((size_t)std::min(step, n) * recBytes)};
+    auto readRange = [f, recBytes](uint8_t *dst, uint64_t cnt) { return fread(dst, recBytes, (size_t)cnt, f) == (size_t)cnt; };
+    auto secs = [](std::chrono::steady_clock::time_point x) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - x).count(); };
+    auto t = std::chrono::steady_clock::now();
+    bool ok = n == 0 || readRange(bufs[0].data(), std::min(step, n));
+    tRead += secs(t);
+    if (!ok) throw std::runtime_error("reading the index file failed: " + index);
+    if (n == 0) { if (kasa_build_add_index(b, 0, 0, 0, nullptr)) throwLast(); return; }
+    int cur = 0;
+    for (uint64_t first = 0; first < n; first += step) {
+        const uint64_t cnt = std::min(step, n - first), next = first + cnt;
+        std::future<bool> pending;
+        if (next < n) { uint8_t *dst = bufs[cur ^ 1].data(); const uint64_t c2 = std::min(step, n - next); pending = std::async(std::launch::async, [&, dst, c2] { return readRange(dst, c2); }); }
+        t = std::chrono::steady_clock::now();
+        const int rc = kasa_build_add_index(b, first, cnt, n, bufs[cur].data());
+        tUpload += secs(t);
+        t = std::chrono::steady_clock::now();
+        const bool readOk = !pending.valid() || pending.get();
+        tRead += secs(t);
+        if (rc) throwLast();
+        if (!readOk) throw std::runtime_error("reading the index file failed: " + index);
+        cur ^= 1;
+    }
+}
+
+// files written under a temporary prefix and renamed to their names at the end; removed when the edit fails before that
+struct StagedFiles {
+    string tmp;
+    vector<std::pair<string, string>> files;   // (temporary, final)
+    explicit StagedFiles(const string &out) : tmp(out + ".kasa_edit_" + std::to_string((long long)getpid())) {}
+    string add(const string &suffix, const string &finalPath) { files.emplace_back(tmp + suffix, finalPath); return tmp + suffix; }
+    void commit()
+    {
+        for (auto &p : files)
+            if (std::rename(p.first.c_str(), p.second.c_str()) != 0) throw std::runtime_error("cannot rename " + p.first + " to " + p.second);
+        files.clear();
+    }
+    ~StagedFiles() { for (auto &p : files) std::remove(p.first.c_str()); }
+};
+
+static bool hasFiveColumns(const string &path)
+{
+    std::ifstream f(path);
+    string line;
+    while (std::getline(f, line)) if (!line.empty() && splitTabs(line).size() >= 5) return true;
+    return false;
+}
+
+static int editMode(const vector<string> &a)
+{
+    const string mode = a[1];
+    string input, contentPath, index, out, delnodes, codonFile, codonId;
+    int frames = 3, device = 0, strategy = 2;
+    float percentage = 0.f;
+    bool memorySet = false, verbose = false;
+    unsigned threads = 1;
+    int64_t memoryGiB = 5;
+    for (size_t i = 2; i < a.size(); ++i) {
+        const string &s = a[i];
+        auto next = [&]() -> string { if (i + 1 >= a.size()) throw std::runtime_error("missing value after " + s); return a[++i]; };
+        if (s == "-i" || s == "--input") input = next();
+        else if (s == "-c" || s == "--content") contentPath = next();
+        else if (s == "-d" || s == "--database") index = next();
+        else if (s == "-o" || s == "--outgoing") out = next();
+        else if (s == "-l" || s == "--deleted") delnodes = next();
+        else if (s == "-s" || s == "--strategy") strategy = std::stoi(next());
+        else if (s == "-g" || s == "--percentage") percentage = std::stof(next());            // a float (main.cpp:396)
+        else if (s == "-a" || s == "--alphabet") { codonFile = next(); codonId = next(); }
+        else if (s == "--one") frames = 1;
+        else if (s == "--three") frames = 3;
+        else if (s == "-m" || s == "--memory") { const string v = next(); memoryGiB = v == "inf" ? (1 << 30) : std::stoll(v); memorySet = true; }
+        else if (s == "-n" || s == "--threads") threads = (unsigned)std::max(1, std::stoi(next()));
+        else if (s == "--device") device = std::stoi(next());
+        else if (s == "-t" || s == "--temp" || s == "-x" || s == "--callidx") next();
+        else if (s == "-v" || s == "--verbose") verbose = true;
+        else if (s == "-k" || s == "--kL" || s == "--kH")
+            throw std::runtime_error("parameter " + s + " is not supported by " + mode + ": the k-mer lengths of an edited index are those of the index (-k and --kL change the columns of _f.txt)");
+        else if (s == "-f" || s == "--acc2tax" || s == "-y" || s == "--taxonomy" || s == "-u" || s == "--level")
+            throw std::runtime_error("parameter " + s + ": generating a content file from the taxonomy is not supported by the MI355X path; give one with -c");
+        else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
+    }
+    if (index.empty()) throw std::runtime_error("no index given (-d)");
+    bool copyContent = false;
+    if (mode == "update") {
+        if (contentPath.empty()) throw std::runtime_error("update needs a content file (-c) that lists the taxa of the index and of the new sequences: generating one is not supported by the MI355X path");
+        if (input.empty()) throw std::runtime_error("Input file not found");
+        if (out.empty()) out = index;                                                       // default: overwrite
+    } else if (mode == "delete") {
+        if (out.empty()) throw std::runtime_error("No output file given!");
+        if (delnodes.empty()) throw std::runtime_error("no delnodes.dmp given (-l)");
+        if (contentPath.empty()) throw std::runtime_error("delete needs the content file of the index (-c)");
+        if (!std::ifstream(delnodes)) throw std::runtime_error("delnodes.dmp not found");
+    } else if (mode == "shrink") {
+        if (out.empty()) out = index + "_s";
+        if (out == index) throw std::runtime_error("Paths and names of input and output are the same!");
+        if (contentPath.empty()) { contentPath = index + "_content.txt"; copyContent = true; }
+        if (strategy == 4) throw std::runtime_error("shrink strategy 4 is not available: use 1 (-g percentage), 2 (halved) or 3 (entropy)");
+        if (strategy != 1 && strategy != 3) strategy = 2;                                   // main.cpp:448-466
+    } else {                                                                                // getFrequency
+        if (contentPath.empty()) contentPath = index + "_content.txt";
+        out = index;
+    }
+    uint64_t n = 0, kind = 0;
+    readIndexInfo(index, n, kind);
+    if (kind == 3) throw std::runtime_error("Halved indices cannot be modified in this way. Sorry...");
+    const int K = kind == 128 ? 25 : 12;
+    const size_t recBytes = K == 25 ? 20 : 12;
+    if (mode == "shrink" && strategy == 2 && K == 25) throw std::runtime_error("If k is larger than 12, the index can not be halved as of now!");
+    if (!std::ifstream(contentPath)) throw std::runtime_error("Content file not found.");
+    if ((mode == "delete" || mode == "getFrequency") && hasFiveColumns(contentPath))
+        throw std::runtime_error(mode + " reads the tax ID from column 2 of the content file: a content file with five columns is not supported (the reference fails with \"ID not found!\")");
+    if (mode == "shrink" && strategy == 1 && memorySet && percentage == 0.f)                  // main.cpp:839-857: the index shall fit -m GiB
+        percentage = 100.f - 100.f * (float)((double)memoryGiB * 1024. * 1024. * 1024.) / (float)(n * recBytes);
+    vector<uint32_t> dropIds;
+    if (mode == "delete") {
+        std::ifstream f(delnodes); string line;
+        while (std::getline(f, line)) if (!line.empty()) dropIds.push_back((uint32_t)std::stoul(splitTabs(line)[0]));
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto secs = [](std::chrono::steady_clock::time_point x) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - x).count(); };
+    const BuildContent bc = loadBuildContent(contentPath);
+    vector<uint8_t> lut;
+    if (!codonFile.empty()) lut = codonTableFromFile(codonFile, codonId);
+    kasa_builder *b = nullptr;
+    const char *brickEnv = getenv("KASA_BUILD_BRICK_PAIRS");
+    if (kasa_build_create(device, K, frames, lut.empty() ? nullptr : lut.data(), bc.c.taxids.data(), (uint32_t)bc.c.taxids.size(),
+                          brickEnv ? (uint64_t)atoll(brickEnv) : 0, &b)) throwLast();
+    std::unique_ptr<kasa_builder, void (*)(kasa_builder *)> guard(b, kasa_build_destroy);
+    if (mode == "shrink" && kasa_build_shrink(b, strategy, percentage)) throwLast();
+    if (!dropIds.empty() && kasa_build_drop_taxa(b, dropIds.data(), dropIds.size())) throwLast();
+    double tRead = 0, tUpload = 0, tParse = 0, tAdd = 0;
+    loadIndexRun(b, index, n, recBytes, tRead, tUpload);
+    uint64_t nSeq = 0, nSkipped = 0;
+    if (mode == "update") addDatabase(b, input, bc, threads, verbose, nSeq, nSkipped, tParse, tAdd);
+    auto tf = std::chrono::steady_clock::now();
+    uint64_t nRec = 0, nTrie = 0;
+    if (kasa_build_finish(b, &nRec, &nTrie)) throwLast();
+    const double tFinish = secs(tf);
+    tf = std::chrono::steady_clock::now();
+    StagedFiles staged(out);
+    if (mode == "getFrequency") {
+        vector<uint64_t> freq(bc.c.taxids.size() * (size_t)K);
+        if (kasa_build_fetch(b, nullptr, nullptr, nullptr, freq.data())) throwLast();
+        writeFreqFile(staged.add("_f.txt", index + "_f.txt"), bc.c, K, freq);
+    } else {
+        const bool halved = mode == "shrink" && strategy == 2;
+        const string tmp = staged.add("", out);
+        for (const char *suf : {"_info.txt", "_trie", "_trie.txt", "_f.txt"}) staged.add(suf, out + suf);
+        // (delete of a 128-bit index: the reference omits the "128" line, Update.hpp:75, and its own identify would misread the index)
+        writeIndexFiles(b, tmp, bc.c, K, nRec, nTrie, halved ? "\n3" : (K == 25 ? "\n128" : ""), !halved);
+        if (halved) {                                                                       // the frequency file of the full index (Shrink.hpp:381-392)
+            std::ifstream src(index + "_f.txt", std::ios::binary);
+            if (!src) throw std::runtime_error("The frequency file of the index cannot be found: " + index + "_f.txt");
+            std::ofstream dst(tmp + "_f.txt", std::ios::binary); dst << src.rdbuf();
+            if (!dst) throw std::runtime_error("writing " + tmp + "_f.txt failed");
+        }
+        if (copyContent) {                                                                  // main.cpp:866-875
+            std::ifstream src(contentPath, std::ios::binary);
+            std::ofstream dst(staged.add("_content.txt", out + "_content.txt"), std::ios::binary); dst << src.rdbuf();
+            if (!dst) throw std::runtime_error("Content file couldn't be opened for reading/writing!");
+        }
+    }
+    staged.commit();
+    const double tWrite = secs(tf);
+    uint64_t st[8] = {0}, es[4] = {0};
+    if (kasa_build_stats(b, st) || kasa_build_edit_stats(b, es)) throwLast();
+    std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries; " << es[0] << " read from the index, " << es[1] << " deleted, " << es[2] << " shrunk away";
+    if (mode == "update") std::cout << ", " << nSeq << " new sequence(s)";
+    std::cout << std::endl;
+    if (getenv("KASA_BUILD_TIMING") || verbose)
+        std::cout << "OUT: edit timing: read " << tRead << " s, upload " << tUpload << " s, parse " << tParse << " s, add " << tAdd << " s, finish " << tFinish << " s, write " << tWrite
+                  << " s, total " << secs(t0) << " s; device ms load+filters " << es[3] / 1e3 << " encode " << st[4] / 1e3 << " sort+unique " << st[5] / 1e3 << " merge " << st[6] / 1e3
+                  << " emit " << st[7] / 1e3 << std::endl;
     std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
     return 0;
 }
@@ -2194,7 +2415,9 @@ static int run(int argc, char **argv)
         return 0;
     }
     if (argc >= 2 && a[1] == "build") return buildMode(a);
-    if (argc < 2 || (a[1] != "identify" && a[1] != "identify_multiple")) throw std::runtime_error("only the modes `build`, `identify` and `identify_multiple` are available on this path");
+    if (argc >= 2 && (a[1] == "update" || a[1] == "delete" || a[1] == "shrink" || a[1] == "getFrequency")) return editMode(a);
+    if (argc < 2 || (a[1] != "identify" && a[1] != "identify_multiple"))
+        throw std::runtime_error("only the modes `build`, `update`, `delete`, `shrink`, `getFrequency`, `identify` and `identify_multiple` are available on this path");
     Params p;
     p.mode = a[1];
     int frameFlags = 0;
