@@ -2,14 +2,19 @@
 HIPCC ?= /opt/rocm/bin/hipcc
 LIB    = kasa_amd/libkasa_hip.so
 HOST   = kasa_amd/host/kasa_identify
+INDEX  = kasa_amd/host/kasa_index
 
-all: $(LIB) $(HOST) oracle
+all: $(LIB) $(HOST) $(INDEX) oracle
 
 $(LIB): kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp kasa_amd/csrc/stdsort_order.h kasa_amd/csrc/kasa_radix.h kasa_amd/csrc/kasa_text.h kasa_amd/csrc/kasa_replay.h kasa_amd/csrc/kasa_build.h kasa_amd/csrc/kasa_edit.h kasa_amd/host/grisu_powers.inc include/kasa_hip.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wall -Wno-unused-result -o $@ kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp -ldl -Wl,-rpath,/opt/rocm/lib
 
 $(HOST): kasa_amd/host/kasa_identify.cpp kasa_amd/host/grisu_powers.inc include/kasa_hip.h $(LIB)
 	g++ -O2 -std=c++17 -pthread -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o $@ $< -Lkasa_amd -lkasa_hip -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
+
+# merge | redundancy | trie: the same source with -DKASA_INDEX_TOOL
+$(INDEX): kasa_amd/host/kasa_identify.cpp kasa_amd/host/grisu_powers.inc include/kasa_hip.h $(LIB)
+	g++ -O2 -std=c++17 -pthread -DKASA_INDEX_TOOL -I/opt/rocm/include -D__HIP_PLATFORM_AMD__ -o $@ $< -Lkasa_amd -lkasa_hip -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,/opt/rocm/lib
 
 oracle:
 	$(MAKE) -C oracle
@@ -29,7 +34,7 @@ test-gpu:
 	python -m pytest tests -q -m gpu
 
 clean:
-	rm -f $(LIB) $(HOST) kasa_amd/libkasa_hip_asan.so kasa_amd/host/kasa_identify_asan
+	rm -f $(LIB) $(HOST) $(INDEX) kasa_amd/libkasa_hip_asan.so kasa_amd/host/kasa_identify_asan
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle test test-gpu clean asan

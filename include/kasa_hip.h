@@ -490,7 +490,7 @@ int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t count, void
 int kasa_build_stats(kasa_builder *b, uint64_t *stats8);
 void kasa_build_destroy(kasa_builder *b);
 
-/* ---- edit: update, delete and shrink an existing index, on the device ------------------------------------------------
+/* ---- edit: update, delete, shrink and merge existing indices, on the device-----------------------------------------------
  * kASA's `update` (Update.hpp:99-180: the sorted union of the old records and those `build` makes of new sequences),
  * `delete` (Update.hpp:28-90: the records of the taxa delnodes.dmp does not list, in order), `shrink` (Shrink.hpp:152-370)
  * and `getFrequency` (main.cpp:1336-1362) on a builder.  An existing index is one more sorted run: kasa_build_finish merges
@@ -512,11 +512,20 @@ void kasa_build_destroy(kasa_builder *b);
  *                          ('^' included) is 0.5 or less go.  A shrink that leaves no record fails kasa_build_finish
  *                          with KASA_E_ARG.
  *   kasa_build_edit_stats  stats4 = {index records in, dropped by delete, dropped by shrink, device microseconds of the
- *                          loads and the filters}. */
+ *                          loads and the filters}.  With several index runs {0} counts the records of all of them.
+ *   kasa_build_taxa_histogram  `redundancy` (Shrink.hpp:35-72), valid after kasa_build_finish, on the final sorted records:
+ *                          hist[c], 1 <= c < nBins, = the distinct k-mers that carry exactly c records (c tax IDs); hist[0] = 0;
+ *                          *distinctKmers = the sum of the bins.  KASA_E_STATE before the finish and on a halved result
+ *                          (shrink strategy 2: its records keep 30 bits of a k-mer).  KASA_E_ARG when a k-mer carries more
+ *                          than nBins - 1 records, which nBins = nTaxa + 1 rules out: (k-mer, tax ID) pairs are unique.
+ * `merge` is two kasa_build_add_index runs (first = 0 starts the second once the first is complete) and no filter: the finish
+ * merges them and drops the records both hold.  `trie` is one index run whose caller fetches only triePrefix and trieCount
+ * (kasa_build_fetch with records = NULL, freq = NULL copies no record down). */
 int kasa_build_add_index(kasa_builder *b, uint64_t first, uint64_t count, uint64_t total, const void *records);
 int kasa_build_drop_taxa(kasa_builder *b, const uint32_t *taxIds, uint64_t n);
 int kasa_build_shrink(kasa_builder *b, int strategy, float percentage);
 int kasa_build_edit_stats(kasa_builder *b, uint64_t *stats4);
+int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@ def build(force: bool = False) -> str:
 
 HOST_SRC = os.path.join(HERE, "host", "kasa_identify.cpp")
 HOST_BIN = os.path.join(HERE, "host", "kasa_identify")
+INDEX_BIN = os.path.join(HERE, "host", "kasa_index")          # the same source with -DKASA_INDEX_TOOL: merge | redundancy | trie
 
 
 def build_host(force: bool = False) -> str:
@@ -51,6 +52,19 @@ def build_host(force: bool = False) -> str:
     return HOST_BIN
 
 
+def build_index_tool(force: bool = False) -> str:
+    """kasa_index (`merge`, `redundancy`, `trie`): kasa_identify.cpp compiled with -DKASA_INDEX_TOOL."""
+    build()
+    newest = max(os.path.getmtime(p) for p in (HOST_SRC, HEADER, os.path.join(HERE, "host", "grisu_powers.inc")))
+    if not force and os.path.exists(INDEX_BIN) and os.path.getmtime(INDEX_BIN) >= newest:
+        return INDEX_BIN
+    cmd = ["g++", "-O2", "-std=c++17", "-pthread", "-DKASA_INDEX_TOOL", "-o", INDEX_BIN, HOST_SRC, "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-L" + HERE, "-lkasa_hip", "-lz",
+           "-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib"]
+    subprocess.check_call(cmd)
+    return INDEX_BIN
+
+
 if __name__ == "__main__":
     print(build(force=True))
     print(build_host(force=True))
+    print(build_index_tool(force=True))

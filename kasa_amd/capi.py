@@ -33,7 +33,7 @@ EXPORTS = [
     "kasa_ctx_set_taxa_text", "kasa_batch_text", "kasa_batch_text_fetch", "kasa_batch_text_fetch_range", "kasa_text_dtoa", "kasa_ctx_reserve", "kasa_runtime_versions", "kasa_ctx_group_tiles", "kasa_ctx_dense_reads", "kasa_ctx_replay_stats", "kasa_ctx_group_second_chance", "kasa_ctx_record_placement",
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
-    "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats",
+    "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats", "kasa_build_taxa_histogram",
 ]
 
 
@@ -174,6 +174,7 @@ def lib():
         L.kasa_build_drop_taxa.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.kasa_build_shrink.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.kasa_build_edit_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_build_taxa_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         _check_runtime(L)
         _lib = L
     return _lib
@@ -470,7 +471,8 @@ class Builder:
 
     def add_index(self, records: np.ndarray, chunk: int = 0):
         """An existing index as one more sorted run: records = REC_DTYPE (K = 12) or REC128_DTYPE (K = 25), sorted by (k-mer,
-        tax ID) and unique; chunk > 0 hands them over in pieces of that many records (as a host reading a file does)."""
+        tax ID) and unique; chunk > 0 hands them over in pieces of that many records (as a host reading a file does).
+        Every call is a run of its own: two calls and no filter are `merge`."""
         from .formats import REC_DTYPE, REC128_DTYPE
         rec = np.ascontiguousarray(records, dtype=REC128_DTYPE if self.K == 25 else REC_DTYPE)
         n = rec.shape[0]
@@ -495,6 +497,21 @@ class Builder:
         s = np.zeros(4, dtype=np.uint64)
         _check(lib().kasa_build_edit_stats(self.h, _p(s)))
         return dict(zip(self.EDIT_STATS, (int(x) for x in s)))
+
+    def taxa_histogram(self, n_bins: int = 0):
+        """(hist, distinct) after finish(): hist[c] = the distinct k-mers that carry exactly c records, hist[0] = 0, distinct
+        = their sum.  n_bins = 0: taxa + 1 bins, which no run of unique (k-mer, tax ID) pairs can exceed."""
+        hist = np.zeros(n_bins if n_bins > 0 else self.taxids.shape[0] + 1, dtype=np.uint64)
+        distinct = C.c_uint64(0)
+        _check(lib().kasa_build_taxa_histogram(self.h, _p(hist), C.c_uint64(hist.shape[0]), C.byref(distinct)))
+        return hist, int(distinct.value)
+
+    def fetch_trie(self):
+        """(trie prefixes, trie counts) alone: no record and no frequency row comes down."""
+        tp = np.zeros(self.n_trie, dtype=np.uint32)
+        tc = np.zeros(self.n_trie, dtype=np.uint64)
+        _check(lib().kasa_build_fetch(self.h, None, _p(tp), _p(tc), None))
+        return tp, tc
 
     def fetch(self):
         """(k-mers: u64 or KEY128_DTYPE, tax IDs, trie prefixes, trie counts, freq[nTaxa, K]).  After shrink(2) the device

@@ -16,6 +16,10 @@
 //                                                                                                      [edit_entropy_flag]
 //   halved  : kept iff the seventh letter (bits 25-29) is not '^'; 6-byte records {u32 low 30 bits, u16 content row}
 //                                                                                         [edit_half_flag, edit_emit_half]
+//   taxa    : after the finish, over the packed file records: how many distinct k-mers carry exactly c records (redundancy,
+//             Shrink.hpp:35-72).  A record that opens a k-mer's run contributes its index to a running maximum (rocPRIM), so
+//             every record knows where its run began; the run's last record adds one to the bin of its length
+//                                                                                              [EditHeadPos, edit_taxa_hist]
 // Positions are 64-bit: an edited index may hold more than 2^32 records.
 #pragma once
 #include <cmath>
@@ -155,6 +159,85 @@ __global__ void edit_emit_half_kernel(const Key *__restrict__ k, const uint32_t 
         const uint32_t low = (uint32_t)k[i] & 0x3FFFFFFFu;
         rec[3 * i] = (uint16_t)low; rec[3 * i + 1] = (uint16_t)(low >> 16); rec[3 * i + 2] = (uint16_t)rowOfRank[v[i]];
     }
+}
+
+// records i and j of the packed file records carry the same k-mer
+template <class Key>
+__host__ __device__ __forceinline__ bool edit_same_kmer(const uint32_t *__restrict__ rec, uint64_t i, uint64_t j)
+{
+    constexpr int W = sizeof(Key) / 4 + 1;
+    bool same = true;
+#pragma unroll
+    for (int w = 0; w < W - 1; ++w) same &= rec[i * W + w] == rec[j * W + w];
+    return same;
+}
+// i where record i opens the run of a k-mer, 0 elsewhere: the running maximum is the index of the run's first record
+template <class Key>
+struct EditHeadPos {
+    const uint32_t *rec;
+    __host__ __device__ uint64_t operator()(uint64_t i) const { return (i == 0 || !edit_same_kmer<Key>(rec, i, i - 1)) ? i : 0; }
+};
+
+// hist[c] += k-mers with exactly c records, c < nBins.  The last record of a run knows the run's length from head[i].  Nearly every
+// run has length 1: those are counted in a register and summed per wavefront; lengths below TAXA_LDS_BINS go to LDS bins that the
+// block flushes once; longer runs (a crowded index has few) add to the global bins directly.  A run of nBins records or more is
+// reported by the index of its last record in a device word (atomicMin).  Reads rec[0, n * W), head[0, n); writes hist[0, nBins).
+static constexpr int TAXA_LDS_BINS = 1024;
+template <class Key>
+__global__ __launch_bounds__(256) void edit_taxa_hist_kernel(const uint32_t *__restrict__ rec, const uint64_t *__restrict__ head, uint64_t n, uint64_t nBins,
+                                                             unsigned long long *__restrict__ hist, unsigned long long *__restrict__ err)
+{
+    __shared__ uint32_t sh[TAXA_LDS_BINS];
+    for (uint32_t c = threadIdx.x; c < TAXA_LDS_BINS; c += blockDim.x) sh[c] = 0u;
+    __syncthreads();
+    uint32_t ones = 0;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        if (i + 1 < n && edit_same_kmer<Key>(rec, i, i + 1)) continue;
+        const uint64_t len = i - head[i] + 1;
+        if (len >= nBins) atomicMin(err, (unsigned long long)i);
+        else if (len == 1) ++ones;
+        else if (len < (uint64_t)TAXA_LDS_BINS) atomicAdd(&sh[len], 1u);
+        else atomicAdd(&hist[len], 1ull);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ones += __shfl_down(ones, off);
+    if ((threadIdx.x & 63) == 0 && ones) atomicAdd(&sh[1], ones);
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < TAXA_LDS_BINS; c += blockDim.x)
+        if (sh[c] && c < nBins) atomicAdd(&hist[c], (unsigned long long)sh[c]);
+}
+
+template <class Key>
+static int taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers)
+{
+    const uint64_t n = b->result.n;
+    std::fill(hist, hist + nBins, (uint64_t)0);
+    *distinctKmers = 0;
+    if (n == 0) return KASA_OK;
+    int rc;
+    DevBuf head, bins;
+    if ((rc = head.reserve(n * 8 + 64)) || (rc = bins.reserve(nBins * 8 + 64)) || (rc = b->loadErr.reserve(64))) return rc;
+    const uint32_t *rec = b->rec.as<uint32_t>();
+    unsigned long long *err = b->loadErr.as<unsigned long long>(), *d = bins.as<unsigned long long>();
+    unsigned long long bad = ~0ull;
+    HIPCHK(hipMemcpyAsync(err, &bad, 8, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemsetAsync(d, 0, nBins * 8, b->stream));
+    rocprim::transform_iterator<rocprim::counting_iterator<uint64_t>, EditHeadPos<Key>, uint64_t> in(rocprim::counting_iterator<uint64_t>(0), EditHeadPos<Key>{rec});
+    size_t tmp = 0;
+    HIPCHK(rocprim::inclusive_scan(nullptr, tmp, in, head.as<uint64_t>(), (size_t)n, rocprim::maximum<uint64_t>(), b->stream));
+    if ((rc = b->scanTmp.reserve(tmp))) return rc;
+    HIPCHK(rocprim::inclusive_scan(b->scanTmp.p, tmp, in, head.as<uint64_t>(), (size_t)n, rocprim::maximum<uint64_t>(), b->stream));
+    edit_taxa_hist_kernel<Key><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(rec, head.as<uint64_t>(), n, nBins, d, err);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(hist, d, nBins * 8, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));                          // (head and bins go out of scope here)
+    if (bad != ~0ull) {
+        std::fill(hist, hist + nBins, (uint64_t)0);
+        return fail(KASA_E_ARG, "kasa_build_taxa_histogram: the k-mer that ends at record %llu carries %llu records or more; pass nBins = taxa + 1", bad, (unsigned long long)nBins);
+    }
+    for (uint64_t c = 0; c < nBins; ++c) *distinctKmers += hist[c];
+    return KASA_OK;
 }
 
 // the records of b->result with f[i] = 1, in order, become b->result
@@ -434,4 +517,19 @@ extern "C" int kasa_build_edit_stats(kasa_builder *b, uint64_t *stats4)
     stats4[0] = b->indexIn; stats4[1] = b->droppedDelete; stats4[2] = b->droppedShrink;
     stats4[3] = (uint64_t)(b->msEdit * 1000.0 + 0.5);                  // device microseconds of the loads and the filters
     return KASA_OK;
+}
+
+static int build_taxa_histogram_impl(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers)
+{
+    using namespace kasa_build_impl;
+    if (!b || !hist || !distinctKmers || nBins == 0) return fail(KASA_E_ARG, "kasa_build_taxa_histogram: NULL argument or no bins");
+    if (!b->finished) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: kasa_build_finish first");
+    if (b->halved) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: a halved index keeps 30 bits of a k-mer, its records do not tell k-mers apart");
+    HIPCHK(hipSetDevice(b->device));
+    return b->wide ? taxa_histogram<key128>(b, hist, nBins, distinctKmers) : taxa_histogram<uint64_t>(b, hist, nBins, distinctKmers);
+}
+
+extern "C" int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers)
+{
+    KASA_GUARDED(build_taxa_histogram_impl(b, hist, nBins, distinctKmers))
 }

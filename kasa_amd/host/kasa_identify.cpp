@@ -36,6 +36,7 @@
 #include <thread>
 #include <tuple>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <dirent.h>
@@ -2363,9 +2364,256 @@ static int editMode(const vector<string> &a)
     return 0;
 }
 
+#ifdef KASA_INDEX_TOOL
+// ---------------------------------------------------------------------------------------------------
+// kasa_index: merge | redundancy | trie (main.cpp:877-1010, 1364-1460; Build.hpp:153-290, GenerateContentFile.hpp:449-611,
+// Shrink.hpp:35-72).  The same source as kasa_identify, compiled with -DKASA_INDEX_TOOL: the readers, the writers and the
+// staging of the edit modes above are shared.  The host rules below are those of kasa_amd/index_edit.py.
+// ---------------------------------------------------------------------------------------------------
+struct ContentRow { string name, tax, spec, acc; };
+
+// a;b + b;c -> a;b;c: the first list's entries in their order, then the second's new ones
+static string joinLists(const string &x, const string &y)
+{
+    vector<string> out;
+    for (const string *l : {&x, &y}) {
+        std::stringstream ss(*l); string e;
+        while (std::getline(ss, e, ';')) if (std::find(out.begin(), out.end(), e) == out.end()) out.push_back(e);
+    }
+    string r;
+    for (size_t i = 0; i < out.size(); ++i) { if (i) r += ';'; r += out[i]; }
+    return r;
+}
+
+// The sorted union of two content files by numeric tax ID (column 2).  The reference's two-pointer merge gives the same file
+// whenever both inputs are sorted, as it assumes; for a taxon of both files the name is the second file's and columns 3 and
+// 4 are joined (the reference: in hash-table order).  Five columns (--taxidasstr) and EWAN dummy taxa are refused.
+static void mergeContentFiles(const string &p1, const string &p2, const string &outPath)
+{
+    std::map<uint64_t, ContentRow> rows;
+    const char *which[2] = {"First", "Second"};
+    const string *paths[2] = {&p1, &p2};
+    for (int k = 0; k < 2; ++k) {
+        std::ifstream f(*paths[k]);
+        if (!f) throw std::runtime_error(string(which[k]) + " content file couldn't be read!");
+        string line; bool first = true;
+        while (std::getline(f, line)) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (first && line.empty()) throw std::runtime_error("Invalid content files! " + *paths[k] + " has a leading empty line.");
+            first = false;
+            if (line.empty()) continue;
+            const auto cols = splitTabs(line);
+            if (cols.size() < 4) throw std::runtime_error("Content file contains less than 4 columns, it may be damaged... The faulty line was: " + line + "\n");
+            if (cols.size() >= 5) throw std::runtime_error("merge reads the tax ID from column 2 of the content files: a content file with five columns is not supported (" + *paths[k] + ")");
+            if (cols[0].find("EWAN") != string::npos)
+                throw std::runtime_error("merge does not renumber dummy taxa: " + *paths[k] + " lists " + cols[0] + "; give the sequences a taxon first");
+            uint64_t tid; size_t used = 0;
+            try { tid = std::stoull(cols[1], &used); } catch (const std::exception &) { used = 0; tid = 0; }
+            if (used == 0 || used != cols[1].size()) throw std::runtime_error("Content file: the tax ID in column 2 is not a number: " + line);
+            auto it = rows.find(tid);
+            if (it == rows.end()) rows.emplace(tid, ContentRow{cols[0], cols[1], cols[2], cols[3]});
+            else { it->second.name = cols[0]; it->second.spec = joinLists(it->second.spec, cols[2]); it->second.acc = joinLists(it->second.acc, cols[3]); }
+        }
+        if (first) throw std::runtime_error("Invalid content files! " + *paths[k] + " is empty.");
+    }
+    string out;
+    for (const auto &r : rows) out += r.second.name + "\t" + r.second.tax + "\t" + r.second.spec + "\t" + r.second.acc + "\n";
+    std::ofstream f(outPath, std::ios::binary); f << out;
+    if (!f) throw std::runtime_error("Resulting content file couldn't be opened for writing!");
+}
+
+// Shrink.hpp:60-71, literally: the share of the records that k-mers with i taxa hold, summed over i = 1, 2, ... in that order;
+// the first i at which the sum reaches 0.99, 0 if it never does
+static uint32_t redundancyCutoff(const vector<uint64_t> &hist, uint64_t nRecords)
+{
+    double percentage = 0.0;
+    for (size_t i = 1; i < hist.size(); ++i) {
+        percentage += static_cast<double>(hist[i]) * i / nRecords;
+        if (percentage >= 0.99) return (uint32_t)i;
+    }
+    return 0;
+}
+
+// the reference's text (Shrink.hpp:55-65, main.cpp:1409-1419).  "Number of unique k-mers" is distinct - 1 as the reference
+// prints it: its loop counts a k-mer when the next one begins, so the last one is never counted.
+static string redundancyReport(const vector<uint64_t> &hist, uint64_t nRecords, bool verbose)
+{
+    std::ostringstream o;
+    if (verbose) {
+        uint64_t distinct = 0;
+        for (size_t i = 1; i < hist.size(); ++i) distinct += hist[i];
+        o << "Number of unique k-mers: " << (distinct ? distinct - 1 : 0) << "\nHistogram\nFrequency Counts Percentage\n";
+        for (size_t i = 1; i < hist.size(); ++i)
+            if (hist[i] != 0) o << i << " " << hist[i] << " " << 100.0 * static_cast<double>(hist[i]) * i / nRecords << "\n";
+    }
+    const uint32_t cut = redundancyCutoff(hist, nRecords);
+    if (cut == 1) o << "OUT: 99% of the k-mers in your index have only one taxon. Using unique frequencies makes sense.\n";
+    else if (cut < 4) o << "OUT: 99% of the k-mers in your index have " << cut << " or less taxa. Using unique frequencies could make sense.\n";
+    else o << "OUT: 99% of the k-mers in your index have " << cut << " or less taxa. You should consider looking at the non-unique frequencies as well.\n";
+    return o.str();
+}
+
+static int indexToolMode(const vector<string> &a)
+{
+    if (a.size() < 2 || (a[1] != "merge" && a[1] != "redundancy" && a[1] != "trie"))
+        throw std::runtime_error("only the modes `merge`, `redundancy` and `trie` are available in kasa_index (kasa_identify has the others)");
+    const string mode = a[1];
+    string first, second, out, c1, c2, co, contentPath, index;
+    int device = 0;
+    bool verbose = false;
+    for (size_t i = 2; i < a.size(); ++i) {
+        const string &s = a[i];
+        auto next = [&]() -> string { if (i + 1 >= a.size()) throw std::runtime_error("missing value after " + s); return a[++i]; };
+        if (s == "--firstIndex" && mode == "merge") first = next();
+        else if (s == "--secondIndex" && mode == "merge") second = next();
+        else if ((s == "-o" || s == "--outgoing") && mode == "merge") out = next();
+        else if (s == "-c1" && mode == "merge") c1 = next();
+        else if (s == "-c2" && mode == "merge") c2 = next();
+        else if (s == "-co" && mode == "merge") co = next();
+        else if ((s == "-c" || s == "--content") && mode != "trie") contentPath = next();
+        else if ((s == "-d" || s == "--database") && mode != "merge") index = next();
+        else if (s == "--device") device = std::stoi(next());
+        else if (s == "-m" || s == "--memory" || s == "-n" || s == "--threads" || s == "-t" || s == "--temp") next();
+        else if (s == "-v" || s == "--verbose") verbose = true;
+        else if (s == "-k" || s == "--kL" || s == "--kH")
+            throw std::runtime_error("parameter " + s + " is not supported by " + mode + ": the k-mer lengths are those of the index, and the trie holds the first 6 letters as `build` writes it");
+        else if (s == "-f" || s == "--acc2tax" || s == "-y" || s == "--taxonomy" || s == "-u" || s == "--level")
+            throw std::runtime_error("parameter " + s + ": generating a content file from the taxonomy is not supported by the MI355X path; give one with -c");
+        else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto secs = [](std::chrono::steady_clock::time_point x) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - x).count(); };
+    auto create = [&](const BuildContent &bc, int K) {
+        kasa_builder *b = nullptr;
+        if (kasa_build_create(device, K, 3, nullptr, bc.c.taxids.data(), (uint32_t)bc.c.taxids.size(), 0, &b)) throwLast();
+        return std::unique_ptr<kasa_builder, void (*)(kasa_builder *)>(b, kasa_build_destroy);
+    };
+    double tRead = 0, tUpload = 0;
+    if (mode == "merge") {
+        if (first.empty() || second.empty()) throw std::runtime_error("merge needs two indices (--firstIndex, --secondIndex)");
+        if (out.empty()) throw std::runtime_error("No output file given!");
+        if (first == second) throw std::runtime_error("-d and -i must point to different indices!");                  // main.cpp:880-885
+        if (first == out || second == out) throw std::runtime_error("You can't overwrite indices (yet)!");
+        uint64_t n1 = 0, kind1 = 0, n2 = 0, kind2 = 0;
+        { std::ifstream f(first + "_info.txt"); if (!f) throw std::runtime_error("Info file for the first index can not be found!"); }
+        { std::ifstream f(second + "_info.txt"); if (!f) throw std::runtime_error("Info file for the second index can not be found!"); }
+        readIndexInfo(first, n1, kind1);
+        readIndexInfo(second, n2, kind2);
+        if (kind1 == 3 || kind2 == 3) throw std::runtime_error("Halved indices cannot be modified in this way. Sorry...");
+        if ((kind1 == 128) != (kind2 == 128))                                                                         // main.cpp:953-956
+            throw std::runtime_error("Indices are not of the same format! One of them was created with a k larger than 12, unlike the other. These data structures cannot be merged (yet). Sorry...");
+        for (const string *ix : {&first, &second}) if (!std::ifstream(*ix)) throw std::runtime_error("The index file cannot be found! (" + *ix + ")");
+        const int K = kind1 == 128 ? 25 : 12;
+        const size_t recBytes = K == 25 ? 20 : 12;
+        StagedFiles staged(out);
+        string merged = contentPath;
+        if (contentPath.empty()) {                                                                                    // main.cpp:913-923
+            if (c1.empty()) c1 = first + "_content.txt";
+            if (c2.empty()) c2 = second + "_content.txt";
+            if (co.empty()) co = out + "_content.txt";
+            merged = staged.add("_content.txt", co);
+            mergeContentFiles(c1, c2, merged);
+        } else {
+            if (!std::ifstream(contentPath)) throw std::runtime_error("Content file not found.");
+            if (hasFiveColumns(contentPath)) throw std::runtime_error("merge reads the tax ID from column 2 of the content file: a content file with five columns is not supported");
+        }
+        const BuildContent bc = loadBuildContent(merged);
+        auto b = create(bc, K);
+        loadIndexRun(b.get(), first, n1, recBytes, tRead, tUpload);
+        loadIndexRun(b.get(), second, n2, recBytes, tRead, tUpload);
+        auto tf = std::chrono::steady_clock::now();
+        uint64_t nRec = 0, nTrie = 0;
+        if (kasa_build_finish(b.get(), &nRec, &nTrie)) throwLast();
+        const double tFinish = secs(tf);
+        tf = std::chrono::steady_clock::now();
+        const string tmp = staged.add("", out);
+        for (const char *suf : {"_info.txt", "_trie", "_trie.txt", "_f.txt"}) staged.add(suf, out + suf);
+        // (the reference writes no _info.txt and an _f.txt of zeros, Read.hpp:3221,3238: here the result can be identified against at once)
+        writeIndexFiles(b.get(), tmp, bc.c, K, nRec, nTrie, K == 25 ? "\n128" : "", true);
+        staged.commit();
+        const double tWrite = secs(tf);
+        uint64_t st[8] = {0}, es[4] = {0};
+        if (kasa_build_stats(b.get(), st) || kasa_build_edit_stats(b.get(), es)) throwLast();
+        std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries; " << es[0] << " read from the two indices, " << es[0] - nRec << " in both" << std::endl;
+        if (getenv("KASA_BUILD_TIMING") || verbose)
+            std::cout << "OUT: merge timing: read " << tRead << " s, upload " << tUpload << " s, finish " << tFinish << " s, write " << tWrite << " s, total " << secs(t0)
+                      << " s; device ms load " << es[3] / 1e3 << " merge " << st[6] / 1e3 << " emit " << st[7] / 1e3 << std::endl;
+        std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
+        return 0;
+    }
+    if (index.empty()) throw std::runtime_error("no index given (-d)");
+    uint64_t n = 0, kind = 0;
+    readIndexInfo(index, n, kind);
+    if (kind == 3) throw std::runtime_error(mode == "redundancy" ? "redundancy cannot be called on shrunken indices!" : "Halved indices cannot be modified in this way. Sorry...");
+    const int K = kind == 128 ? 25 : 12;
+    const size_t recBytes = K == 25 ? 20 : 12;
+    if (!std::ifstream(index)) throw std::runtime_error("The index file cannot be found!");
+    if (mode == "redundancy") {
+        if (contentPath.empty()) contentPath = index + "_content.txt";
+        if (!std::ifstream(contentPath)) throw std::runtime_error("Content file not found.");
+        if (n == 0) throw std::runtime_error("Index is empty, are all input files okay?");
+        const BuildContent bc = loadBuildContent(contentPath);
+        auto b = create(bc, K);
+        loadIndexRun(b.get(), index, n, recBytes, tRead, tUpload);
+        uint64_t nRec = 0, nTrie = 0, distinct = 0;
+        if (kasa_build_finish(b.get(), &nRec, &nTrie)) throwLast();
+        vector<uint64_t> hist(bc.c.taxids.size() + 1);
+        const auto th = std::chrono::steady_clock::now();
+        if (kasa_build_taxa_histogram(b.get(), hist.data(), hist.size(), &distinct)) throwLast();
+        if (getenv("KASA_BUILD_TIMING"))
+            std::cout << "OUT: redundancy timing: read " << tRead << " s, upload " << tUpload << " s, histogram " << secs(th) << " s, total " << secs(t0) << " s" << std::endl;
+        std::cout << redundancyReport(hist, nRec, verbose) << std::flush;
+        return 0;
+    }
+    // trie (main.cpp:1422-1460): _trie and _trie.txt of the index as `build` writes them; the keys alone decide, so no content file
+    BuildContent bc;
+    {
+        // every tax ID the records carry must be known to the builder: the records' own IDs, gathered in a first pass over the file
+        FILE *f = fopen(index.c_str(), "rb");
+        if (!f) throw std::runtime_error("The index file cannot be found!");
+        std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
+        std::unordered_set<uint32_t> ids;
+        vector<uint8_t> buf((size_t)std::min<uint64_t>(n, 1u << 20) * recBytes);
+        for (uint64_t done = 0; done < n;) {
+            const uint64_t cnt = std::min<uint64_t>(n - done, 1u << 20);
+            if (fread(buf.data(), recBytes, (size_t)cnt, f) != (size_t)cnt) throw std::runtime_error("The index file is shorter than _info.txt says: " + index);
+            for (uint64_t j = 0; j < cnt; ++j) { uint32_t t; memcpy(&t, &buf[(size_t)(j + 1) * recBytes - 4], 4); ids.insert(t); }
+            done += cnt;
+        }
+        bc.c.names.push_back("non_unique"); bc.c.taxids.push_back(0);
+        for (uint32_t t : ids) if (t != 0) { bc.c.names.push_back(std::to_string(t)); bc.c.taxids.push_back(t); }
+        if (bc.c.taxids.size() < 2) { bc.c.names.push_back("none"); bc.c.taxids.push_back(ids.count(1) ? 2 : 1); }
+    }
+    auto b = create(bc, K);
+    loadIndexRun(b.get(), index, n, recBytes, tRead, tUpload);
+    uint64_t nRec = 0, nTrie = 0;
+    if (kasa_build_finish(b.get(), &nRec, &nTrie)) throwLast();
+    vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie);
+    if (kasa_build_fetch(b.get(), nullptr, tp.data(), tc.data(), nullptr)) throwLast();                               // (no record comes down)
+    StagedFiles staged(index);
+    {
+        vector<uint8_t> t(nTrie * 12);
+        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
+        std::ofstream f(staged.add("_trie", index + "_trie"), std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
+        std::ofstream g(staged.add("_trie.txt", index + "_trie.txt"), std::ios::binary); g << nTrie;
+        if (!f || !g) throw std::runtime_error("writing the trie of " + index + " failed");
+    }
+    staged.commit();
+    std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries" << std::endl;
+    std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
+    return 0;
+}
+#endif
+
 static int run(int argc, char **argv)
 {
     vector<string> a(argv, argv + argc);
+#ifdef KASA_INDEX_TOOL
+    std::cout << "OUT: kasa_index (MI355X path of kASA merge, redundancy and trie)\nOUT: ";
+    for (auto &s : a) std::cout << s << " ";
+    std::cout << std::endl;
+    return indexToolMode(a);
+#endif
     if (argc >= 3 && a[1] == "--parameters") {                   // source/main.cpp:264
         a = argsFromYaml(a[0], a[2]);
         argc = (int)a.size();

@@ -1,4 +1,4 @@
-"""`kASA update | delete | shrink | getFrequency` for the device path: an existing index edited by the builder
+"""`kASA update | delete | shrink | getFrequency | merge | redundancy | trie` for the device path: an existing index edited by the builder
 (kasa_amd/csrc/kasa_edit.h behind kasa_build_add_index / drop_taxa / shrink, capi.Builder).
 
 Every function loads the index's records as a sorted run of a builder, lets the device merge and filter them, and returns
@@ -81,6 +81,49 @@ def frequencies(ix: formats.Index, device: int = 0) -> np.ndarray:
     return _run(ix, ix.content, lambda b: None, device).freq
 
 
+def merge_indices(ix1: formats.Index, ix2: formats.Index, content: formats.Content, device: int = 0, chunk: int = 0) -> formats.Index:
+    """merge (Build.hpp:153-290): the sorted unique union of the records of two indices of the same width; content lists the
+    taxa of both (merge_content writes its file).  Each index is a run of its own, the finish merges them."""
+    if ix1.K != ix2.K:
+        raise ValueError("Indices are not of the same format! One of them was created with a k larger than 12, unlike the other.")
+    b = capi.Builder(content.taxids, ix1.K, 3, None, 0, device)
+    try:
+        b.add_index(_records(ix1), chunk)
+        b.add_index(_records(ix2), chunk)
+        b.finish()
+        km, taxid, tp, tc, freq = b.fetch()
+        stats = b.edit_stats()
+    finally:
+        b.close()
+    out = formats.Index(km, taxid, formats.dense_tax(taxid, content), tp, tc, content, freq)
+    out.edit_stats = stats
+    return out
+
+
+def redundancy(ix: formats.Index, device: int = 0):
+    """redundancy (main.cpp:1364-1420, Shrink.hpp:35-72): (hist, cutoff) with hist[c] = the distinct k-mers of c taxa, counted
+    on the device, and cutoff = redundancy_cutoff(hist, ix.n)."""
+    b = capi.Builder(ix.content.taxids, ix.K, 3, None, 0, device)
+    try:
+        b.add_index(_records(ix))
+        b.finish()
+        hist, _ = b.taxa_histogram()
+    finally:
+        b.close()
+    return hist, redundancy_cutoff(hist, ix.n)
+
+
+def rebuild_trie(ix: formats.Index, device: int = 0):
+    """trie (main.cpp:1422-1460): (prefix, count) of the `_trie` file, from the index's k-mers alone."""
+    b = capi.Builder(ix.content.taxids, ix.K, 3, None, 0, device)
+    try:
+        b.add_index(_records(ix))
+        b.finish()
+        return b.fetch_trie()
+    finally:
+        b.close()
+
+
 # ---- host rules -------------------------------------------------------------------------------------------------------
 
 def read_delnodes(path: str) -> np.ndarray:
@@ -128,3 +171,90 @@ def entropy_keeps(counts, K: int) -> bool:
         p = np.float32(np.float32(c) / np.float32(K))
         h += float(np.float32(p * np.log2(p, dtype=np.float32)))
     return (-h * math.log(2) / math.log(22)) > 0.5
+
+
+def redundancy_cutoff(hist, n_records: int) -> int:
+    """Shrink.hpp:60-71, literally: double(hist[i]) * i / n_records summed over i = 1, 2, ... in that order; the first i at
+    which the sum is >= 0.99, 0 if it never is."""
+    percentage = 0.0
+    for i in range(1, len(hist)):
+        percentage += float(int(hist[i])) * i / n_records
+        if percentage >= 0.99:
+            return i
+    return 0
+
+
+def _cout_double(x: float) -> str:
+    """a double as std::cout writes it: precision 6, %g"""
+    return "%g" % x
+
+
+def redundancy_report(hist, n_records: int, verbose: bool = False) -> str:
+    """The text `redundancy [-v]` prints (Shrink.hpp:55-65, main.cpp:1409-1419).  "Number of unique k-mers" is the distinct
+    k-mers MINUS ONE, as the reference prints it: its loop counts a k-mer when the next one begins, so the last k-mer is
+    never counted, while the histogram below it holds every k-mer."""
+    out = []
+    if verbose:
+        distinct = sum(int(x) for x in hist[1:])
+        out.append("Number of unique k-mers: %d" % max(distinct - 1, 0))
+        out.append("Histogram")
+        out.append("Frequency Counts Percentage")
+        for i in range(1, len(hist)):
+            if int(hist[i]) != 0:
+                out.append("%d %d %s" % (i, int(hist[i]), _cout_double(100.0 * float(int(hist[i])) * i / n_records)))
+    cut = redundancy_cutoff(hist, n_records)
+    if cut == 1:
+        out.append("OUT: 99% of the k-mers in your index have only one taxon. Using unique frequencies makes sense.")
+    elif cut < 4:
+        out.append("OUT: 99%% of the k-mers in your index have %d or less taxa. Using unique frequencies could make sense." % cut)
+    else:
+        out.append("OUT: 99%% of the k-mers in your index have %d or less taxa. You should consider looking at the non-unique frequencies as well." % cut)
+    return "\n".join(out) + "\n"
+
+
+def _join_lists(a: str, b: str) -> str:
+    out = []
+    for e in a.split(";") + b.split(";"):
+        if e not in out:
+            out.append(e)
+    return ";".join(out)
+
+
+def merge_content(path1: str, path2: str, out_path: str) -> None:
+    """The content file of a merged index (GenerateContentFile.hpp:449-611): the rows of both files keyed by the numeric tax
+    ID of column 2, ascending.  That is the reference's output whenever both inputs are sorted, as its two-pointer merge
+    assumes; for unsorted inputs the reference interleaves wrongly, here the result is the sorted union all the same.  A taxon
+    of both files takes the second file's name, and its columns 3 and 4 are the ';'-joined lists without repeats: the first
+    file's entries in their order, then the second's new ones (the reference: in the order of a hash table).  Refused: a
+    leading empty line, fewer than 4 columns, five columns (--taxidasstr) and EWAN dummy taxa, which the reference
+    renumbers so that the dummies of the two indices collide."""
+    rows = {}
+    for path in (path1, path2):
+        with open(path) as f:
+            lines = f.read().split("\n")
+        if lines and lines[-1] == "":
+            lines.pop()
+        if not lines or lines[0].rstrip("\r") == "":
+            raise ValueError("Invalid content files! %s has a leading empty line." % path)
+        for line in lines:
+            line = line.rstrip("\r")
+            if line == "":
+                continue
+            cols = line.split("\t")
+            if len(cols) < 4:
+                raise ValueError("Content file contains less than 4 columns, it may be damaged... The faulty line was: " + line)
+            if len(cols) >= 5:
+                raise ValueError("merge reads the tax ID from column 2 of the content files: a content file with five columns is not supported (%s)" % path)
+            if "EWAN" in cols[0]:
+                raise ValueError("merge does not renumber dummy taxa: %s lists %s; give the sequences a taxon first" % (path, cols[0]))
+            if not cols[1].isdigit():
+                raise ValueError("Content file: the tax ID in column 2 is not a number: " + line)
+            tid = int(cols[1])
+            if tid in rows:
+                old = rows[tid]
+                rows[tid] = [cols[0], old[1], _join_lists(old[2], cols[2]), _join_lists(old[3], cols[3])]
+            else:
+                rows[tid] = cols[:4]
+    with open(out_path, "w") as f:
+        for tid in sorted(rows):
+            f.write("\t".join(rows[tid]) + "\n")
