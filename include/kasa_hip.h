@@ -122,6 +122,9 @@ int kasa_batch_upload_segments(kasa_ctx *ctx, const uint8_t *bases, const int64_
 
 /* Read::convertAndSort (Read.hpp:763-827): every read -> packed k-mers + read id, device resident. */
 int kasa_batch_encode(kasa_ctx *ctx, uint64_t *nKmers);
+/* Reads a wavefront of the encoder takes together when a batch is DNA in three frames with at most 192 k-mers per read
+ * (the group form of the encoder; every other batch: one read per wavefront). */
+int kasa_encode_group_reads(void);
 
 /* Compare::sortInputAndCheckInvalidkMers_sta (Compare.hpp:1074-1260): sort by k-mer and find each
  * query's place in the index.  unique != 0 is -e/--unique (Compare.hpp:3167-3178): records equal in

@@ -34,7 +34,13 @@ EXPORTS = [
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
     "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats", "kasa_build_taxa_histogram",
+    "kasa_encode_group_reads",
 ]
+
+
+def encode_group_reads() -> int:
+    """Reads one wavefront of the encoder's group form takes together (short DNA reads in three frames)."""
+    return int(lib().kasa_encode_group_reads())
 
 
 _share_torch = False

@@ -943,7 +943,10 @@ extern "C" int kasa_batch_upload_segments(kasa_ctx *c, const uint8_t *bases, con
     KASA_GUARDED(upload_impl(c, bases, offsets, nSegments, segmentRead, nReads))
 }
 
-// One wavefront per read.  The cleaned bases of a window chunk are staged in LDS as 3-bit codes, the
+// The encoder has two forms.  Batches of short DNA reads in three frames -- at most ENC_GROUP_RM k-mers per read, every read
+// ranked by the encoder -- take encode_group_kernel (below): one wavefront per GROUP of consecutive reads.  Everything else
+// (six frames, --one, amino-acid input, paired-end segments, a read of more k-mers, 128-bit keys, the long sequences) takes
+// encode_kernel: one wavefront per read.  The cleaned bases of a window chunk are staged in LDS as 3-bit codes, the
 // codon letters are computed once per start position, each lane then packs K letters: window w starts at
 // base w * ws and takes its letters at stride ls (DNA: ws 1, ls 3; --one: ws 3, ls 3, Read.hpp:223-261;
 // amino-acid input: ws 1, ls 1 and the letters are the input itself, Read.hpp:60-81).
@@ -1108,7 +1111,203 @@ __global__ __launch_bounds__(64 * ENC_WAVES, RM <= 192 ? 6 : 1) void encode_kern
         }
     }
 }
+
+// The group form of the encoder: DNA in three frames (one strand), every read of the batch ranked by the encoder and none
+// with more than ENC_GROUP_RM k-mers -- the batch of short reads.  One wavefront per GROUP of G consecutive reads: a
+// 150-bp read has 130 k-mers and stages 165 bases, so a wavefront that owns one read runs the third round of every loop on
+// 2 (37) of its 64 lanes.  Here the bases, the windows and the ranking items of the group's reads are each ONE flat list that
+// the lanes stride over (4 reads: 520 windows in 9 rounds where one read at a time takes 12).  Reads lie behind each other
+// in the input and in the output, so a window's place in the output is the group's first place plus its number in the
+// list; what depends on the read (where its bases begin, how many there are) is looked up in a table of the group's
+// prefix sums (sTab: k-mers, staged bases) by the read's number in the group, which a lane finds by comparing its item
+// number with the G - 1 inner prefix sums (uniform values, scalar registers).  Reads of unequal length, reads too short
+// for a window and a last group of fewer reads need nothing special.  A group whose reads have more than CAPK k-mers
+// together is taken in several parts of consecutive reads (a read has at most ENC_GROUP_RM <= CAPK).
+//
+// Ranking (payload = slot, as in encode_kernel) stays per read: rank = k-mers of the read that are smaller, equal ones in
+// window order.  The k-mers of a read are dealt into 256 buckets by their top eight key bits (the first letter and three
+// bits of the second): with 64 buckets by six bits the most common first letter filled a bucket with a dozen members and
+// every lane of the wavefront waited for the longest walk of the 64; with 256 the longest bucket a wavefront meets has a
+// few.  Counts are bytes (a read has at most 192 k-mers), four to a word, one row of 256 per read of the group: a lane
+// owns the four buckets of one word, their running sums are one multiplication, the lanes' sums one wave scan.  The
+// members of a bucket lie behind each other in LDS as (key << 8) | window: inside a bucket the top eight bits are equal, so
+// that word orders members by key, then window, and a member's rank is a count of one unsigned compare per other member.
+// The keys wait in registers between the counting and the placing: LDS holds one word per k-mer, not two.
+static constexpr int ENC_GROUP_WGS = 5;                     // workgroups per CU: 96 registers per lane (six: 80, and nine of them spilled)
+static constexpr int ENC_GROUP = 4;                         // reads per wavefront (kasa_encode_group_reads)
+static constexpr int ENC_GROUP_RM = 192;                    // most k-mers of a read the group form takes
+template <class Key, int G>
+__global__ __launch_bounds__(64 * ENC_WAVES, ENC_GROUP_WGS) void encode_group_kernel(
+    const uint8_t *__restrict__ bases, const int64_t *__restrict__ baseOff, const uint64_t *__restrict__ kmerOff, int64_t nReads,
+    const uint8_t *__restrict__ lutG, Key *__restrict__ outKmer, uint32_t *__restrict__ outRead)
+{
+    constexpr int KLETTERS = KeyTraits<Key>::LETTERS;
+    constexpr int PADB = 3 * KLETTERS - 1;                  // bases a read stages beyond its k-mer count (last window: 3 K)
+    constexpr int ROUNDS = (G * 136 + 63) / 64;             // (150/151-bp reads: 130/131 k-mers)
+    constexpr int CAPK = ROUNDS * 64;                       // k-mers of one part
+    constexpr int CAPB = CAPK + G * PADB;                   // bases of one part
+    constexpr int BROUNDS = (CAPB + 63) / 64;
+    constexpr int TOPSH = 8 * (int)sizeof(Key) - 8;
+    static_assert(ENC_GROUP_RM <= CAPK && ENC_GROUP_RM < 256 && G >= 2 && G <= 16, "encode_group_kernel: byte counters, one read fits a part");
+    __shared__ uint8_t sLut[384];
+    __shared__ uint8_t sLetter[ENC_WAVES][BROUNDS * 64 + 8];          // the 3-bit codes of the bases, then (in place) the codon letters
+    __shared__ Key sComp[ENC_WAVES][CAPK];                           // per read and bucket: (key << 8) | window of the members
+    __shared__ uint32_t sCnt[ENC_WAVES][G][65];                      // per read: 256 byte counters, then bucket starts; [64] = the read's k-mers
+    __shared__ uint4 sTab[ENC_WAVES][G + 1];                         // per read: {k-mers before, staged bases before, raw bases before, raw bases}
+    for (int i = threadIdx.x; i < 366; i += blockDim.x) sLut[i] = lutG[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wv = threadIdx.x >> 6;
+    const int64_t wavesTotal = (int64_t)gridDim.x * ENC_WAVES;
+    const int64_t nGroups = (nReads + G - 1) / G;
+    uint8_t *const letters = &sLetter[wv][0];
+    for (int64_t g = (int64_t)blockIdx.x * ENC_WAVES + wv; g < nGroups; g += wavesTotal) {
+        const int64_t r0 = g * G;
+        const int nr = (int)((nReads - r0 < G) ? nReads - r0 : G);
+        // lane t <= nr holds the prefix sums before read t of the group (lane nr: behind the last)
+        const int64_t rr = r0 + (lane < nr ? lane : nr);
+        const uint64_t kAbs = kmerOff[rr];
+        const int64_t bAbs = baseOff[rr];
+        const uint64_t K0 = lane_value<0>((unsigned long long)kAbs);
+        const int64_t B0 = (int64_t)lane_value<0>((unsigned long long)bAbs);
+        const uint32_t k32 = (uint32_t)(kAbs - K0), b32 = (uint32_t)(bAbs - B0);
+        const uint32_t kNext = (uint32_t)__shfl_down((int)k32, 1), bNext = (uint32_t)__shfl_down((int)b32, 1);
+        const uint32_t cntL = lane < nr ? kNext - k32 : 0u, rawL = lane < nr ? bNext - b32 : 0u;
+        const unsigned long long nzMask = __ballot(cntL != 0u);
+        int a = 0;
+        while (a < nr) {                                              // parts of the group: reads [a, e)
+            const uint32_t kA = (uint32_t)__builtin_amdgcn_readlane((int)k32, a);
+            const unsigned long long fit = __ballot(lane > a && lane <= nr && k32 - kA <= (uint32_t)CAPK);
+            if (!fit) break;                                          // (a read of more than CAPK k-mers: the host never launches this form then)
+            const int e = 63 - __builtin_clzll(fit);
+            const int ng = e - a;
+            const uint32_t totK = (uint32_t)__builtin_amdgcn_readlane((int)k32, e) - kA;
+            if (totK == 0u) { a = e; continue; }
+            const unsigned long long before = nzMask & ((1ull << lane) - 1ull) & ~((1ull << a) - 1ull);   // reads with k-mers in [a, lane)
+            const uint32_t kRel = k32 - kA;
+            const uint32_t sRel = kRel + (uint32_t)PADB * (uint32_t)__popcll(before);
+            const uint32_t totSpan = (uint32_t)__builtin_amdgcn_readlane((int)sRel, e);
+            uint32_t thrK[G - 1], thrS[G - 1];                        // the inner prefix sums: item i is of read #{t : i >= thr[t]}
+#pragma unroll
+            for (int t = 1; t < G; ++t) {
+                const uint32_t vk = (uint32_t)__builtin_amdgcn_readlane((int)kRel, (a + t) & 63);
+                const uint32_t vs = (uint32_t)__builtin_amdgcn_readlane((int)sRel, (a + t) & 63);
+                thrK[t - 1] = t < ng ? vk : 0xFFFFFFFFu;
+                thrS[t - 1] = t < ng ? vs : 0xFFFFFFFFu;
+            }
+            if (lane >= a && lane <= e) sTab[wv][lane - a] = make_uint4(kRel, sRel, b32, rawL);
+            for (int i = lane; i < G * 65; i += 64) (&sCnt[wv][0][0])[i] = 0u;
+            LDS_WAVE_SYNC_ENC();
+            // ---- the cleaned bases of the part's reads as 3-bit codes, read behind read; behind a read's bases its padding X
+#pragma unroll
+            for (int q = 0; q < BROUNDS; ++q) {
+                const uint32_t p = (uint32_t)lane + 64u * q;
+                if (p < totSpan) {
+                    uint32_t j = 0;
+#pragma unroll
+                    for (int t = 0; t < G - 1; ++t) j += p >= thrS[t] ? 1u : 0u;
+                    const uint4 T = sTab[wv][j];
+                    const uint32_t pos = p - T.y;
+                    uint8_t code = 4;                                 // X: padding and marker
+                    if (pos < T.w) {
+                        const uint8_t ch = bases[B0 + (int64_t)(T.z + pos)];
+                        const uint8_t up = ch & 0xDF;
+                        const bool ok = (up == 'A') | (up == 'C') | (up == 'G') | (up == 'T');
+                        code = ok ? (uint8_t)((ch & 14) >> 1) : (uint8_t)5;   // everything else is Z
+                    }
+                    letters[p] = code;
+                }
+            }
+            LDS_WAVE_SYNC_ENC();
+            // ---- codon letters, in place: all codes are read (three per position) before the first letter is written
+            // (the last two positions of a read take codes of the next: no window reads them)
+            uint32_t codon[BROUNDS];
+#pragma unroll
+            for (int q = 0; q < BROUNDS; ++q) {
+                const uint32_t p = (uint32_t)lane + 64u * q;
+                codon[q] = p + 2u < totSpan ? letters[p] * 64u + letters[p + 1] * 8u + letters[p + 2] : 0u;
+            }
+            LDS_WAVE_SYNC_ENC();
+#pragma unroll
+            for (int q = 0; q < BROUNDS; ++q) {
+                const uint32_t p = (uint32_t)lane + 64u * q;
+                if (p + 2u < totSpan) letters[p] = sLut[codon[q]];
+            }
+            LDS_WAVE_SYNC_ENC();
+            // ---- pack, store the key, count the k-mer in its read's bucket
+            Key kk[ROUNDS];
+            uint32_t meta[ROUNDS];                                    // arrival number in the bucket | bucket << 8 | window << 16 | read << 24
+#pragma unroll
+            for (int q = 0; q < ROUNDS; ++q) {
+                const uint32_t i = (uint32_t)lane + 64u * q;
+                kk[q] = 0; meta[q] = 0u;
+                if (i < totK) {
+                    uint32_t j = 0;
+#pragma unroll
+                    for (int t = 0; t < G - 1; ++t) j += i >= thrK[t] ? 1u : 0u;
+                    const uint4 T = sTab[wv][j];
+                    const uint8_t *lt = &letters[i + (T.y - T.x)];
+                    Key v = 0;
+#pragma unroll
+                    for (int j0 = 0; j0 < KLETTERS; j0 += 6) {        // (six letters at a time in 32 bits, then one wide shift per group)
+                        uint32_t part = 0;
+#pragma unroll
+                        for (int x = j0; x < j0 + 6 && x < KLETTERS; ++x) part = (part << 5) | lt[x * 3];
+                        const int got = KLETTERS - j0 < 6 ? KLETTERS - j0 : 6;
+                        v = (v << (5 * got)) | (Key)part;
+                    }
+                    outKmer[K0 + kA + i] = v;
+                    const Key top = v << KeyTraits<Key>::SHIFT;
+                    const uint32_t b = (uint32_t)(top >> TOPSH);
+                    const uint32_t sh = 8u * (b & 3u);
+                    const uint32_t old = atomicAdd(&sCnt[wv][j][b >> 2], 1u << sh);
+                    kk[q] = top;
+                    meta[q] = ((old >> sh) & 255u) | (b << 8) | ((i - T.x) << 16) | (j << 24);
+                }
+            }
+            LDS_WAVE_SYNC_ENC();
+            // ---- counts -> bucket starts inside the read (bytes: a read has at most 192 k-mers, no sum carries)
+            for (int j = 0; j < ng; ++j) {
+                const uint32_t w = sCnt[wv][j][lane];
+                const uint32_t tot = (w * 0x01010101u) >> 24;
+                const uint32_t incl = wave_incl_sum(tot);
+                sCnt[wv][j][lane] = w * 0x01010100u + (incl - tot) * 0x01010101u;
+                if (lane == 63) sCnt[wv][j][64] = incl;
+            }
+            LDS_WAVE_SYNC_ENC();
+#pragma unroll
+            for (int q = 0; q < ROUNDS; ++q) {
+                const uint32_t i = (uint32_t)lane + 64u * q;
+                if (i < totK) {
+                    const uint32_t m = meta[q], b = (m >> 8) & 255u, w = (m >> 16) & 255u;
+                    const uint8_t *row = reinterpret_cast<const uint8_t *>(&sCnt[wv][m >> 24][0]);
+                    sComp[wv][i - w + row[b] + (m & 255u)] = (Key)(kk[q] << 8) | (Key)w;
+                }
+            }
+            LDS_WAVE_SYNC_ENC();
+#pragma unroll
+            for (int q = 0; q < ROUNDS; ++q) {
+                const uint32_t i = (uint32_t)lane + 64u * q;
+                if (i < totK) {
+                    const uint32_t m = meta[q], b = (m >> 8) & 255u, w = (m >> 16) & 255u;
+                    const uint8_t *row = reinterpret_cast<const uint8_t *>(&sCnt[wv][m >> 24][0]);
+                    const uint32_t first = row[b], end = row[b + 1u];
+                    const Key me = (Key)(kk[q] << 8) | (Key)w;
+                    const Key *mem = &sComp[wv][i - w];
+                    uint32_t rk = first;
+                    for (uint32_t x = first; x < end; ++x) rk += mem[x] < me ? 1u : 0u;
+                    const uint64_t o0 = K0 + kA + (i - w);            // the read's first slot
+                    outRead[K0 + kA + i] = (uint32_t)(o0 + rk);
+                }
+            }
+            LDS_WAVE_SYNC_ENC();
+            a = e;
+        }
+    }
+}
 #undef LDS_WAVE_SYNC_ENC
+
+extern "C" int kasa_encode_group_reads(void) { return ENC_GROUP; }
 
 extern "C" int kasa_batch_encode(kasa_ctx *c, uint64_t *nKmers)
 {
@@ -1135,7 +1334,13 @@ extern "C" int kasa_batch_encode(kasa_ctx *c, uint64_t *nKmers)
             encode_kernel<key128><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(),
                 c->seqOff.as<uint64_t>(), c->haveSeqRead ? c->seqRead.as<uint32_t>() : nullptr, c->nSeq, c->kLow, c->strands(), c->enc_mode(),
                 c->lut.as<uint8_t>(), c->qKmerA.as<key128>(), c->qReadA.as<uint32_t>(), rankSlots, nullptr, nullptr, longMin);
-        else if (rankSlots && c->maxCnt <= 192u)
+        else if (rankSlots && c->maxCnt <= (uint32_t)ENC_GROUP_RM && c->enc_mode() == ENC_DNA && c->strands() == 1) {
+            // short DNA reads in three frames: a wavefront per group of reads (rankSlots: every sequence is a read)
+            const int64_t groups = (c->nSeq + ENC_GROUP - 1) / ENC_GROUP;
+            const unsigned gblocks = (unsigned)std::min<int64_t>((groups + ENC_WAVES - 1) / ENC_WAVES, 256 * 16);
+            encode_group_kernel<uint64_t, ENC_GROUP><<<gblocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(),
+                c->seqOff.as<uint64_t>(), c->nSeq, c->lut.as<uint8_t>(), c->qKmerA.as<uint64_t>(), c->qReadA.as<uint32_t>());
+        } else if (rankSlots && c->maxCnt <= 192u)
             encode_kernel<uint64_t, 192><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(),
                 c->seqOff.as<uint64_t>(), c->haveSeqRead ? c->seqRead.as<uint32_t>() : nullptr, c->nSeq, c->kLow, c->strands(), c->enc_mode(),
                 c->lut.as<uint8_t>(), c->qKmerA.as<uint64_t>(), c->qReadA.as<uint32_t>(), rankSlots, nullptr, nullptr, longMin);
