@@ -215,6 +215,33 @@ int kasa_batch_scores_fetch(kasa_ctx *ctx, uint64_t *readOffsets, uint32_t *taxI
  * others depend on its unstable sorts): KASA_E_ARG otherwise. */
 int kasa_batch_coherence(kasa_ctx *ctx, float *scores, uint64_t *throwsAt);
 
+/* The same over a range-partitioned index (C5; the reference streams an index of any size through the same walk,
+ * Compare.hpp:182-328, so the seam is ours): kasa_batch_coherence cut at the one step that reads the index.  A k-mer's match
+ * length (setMatchLength, Compare.hpp:847-848,882-884,912-914,948) needs at least the 6 letters of a `_trie` entry
+ * (Trie.hpp:494-520) in common with an index entry, and partitions are cut between `_trie` entries: its depth against the
+ * whole index is its depth against the partition that owns its 30-bit prefix, and 0 against every other one.
+ *   kasa_batch_coherence_begin     on the context that owns the reads, after kasa_batch_score: the preconditions and errors
+ *                                  of kasa_batch_coherence; encodes the batch once more in emission order (read, strand,
+ *                                  window; Compare.hpp:2609-2628 sorts it back into that order) and hands out the k-mers
+ *                                  (8 or 16 bytes each), their number *n (what kasa_batch_encode reported) and *n depth
+ *                                  bytes, all zero.  The pointers stay valid until the context's next batch call.
+ *   kasa_batch_match_depth_device  on a context bound to ONE partition (or to the whole index: [0, 2^30)): for every k-mer
+ *                                  whose 6-letter prefix p satisfies firstPrefix <= p < endPrefix -- the units of
+ *                                  kasa_batch_slice_starts' `cuts`; 2^30 ends the last partition -- depthDev[i] = the deepest
+ *                                  level of k-mer i that this context's index matches, by this context's -k (at least 6
+ *                                  letters, cut before the first '^', 0 below the lowest level: Compare.hpp:803-829,847-948).
+ *                                  K-mers of other prefixes are skipped before the index is touched and their bytes are
+ *                                  left as they are.  kmersDev and depthDev may lie on a peer device; the batch this
+ *                                  context holds is not disturbed.  n must be the n of _begin.
+ *   kasa_batch_coherence_finish    on the owner, once every partition has had its call: finds the first matching k-mer
+ *                                  (Compare.hpp:2630-2646) from the depth bytes and walks them (Compare.hpp:2663-2728);
+ *                                  scores, *throwsAt and the effect on kasa_batch_text as kasa_batch_coherence.
+ * Each call returns with its stream idle, so a host needs no synchronisation of its own between contexts.  KASA_E_STATE:
+ * _finish without _begin on this batch; KASA_E_ARG: firstPrefix > endPrefix or beyond 2^30, an n that is not the batch's. */
+int kasa_batch_coherence_begin(kasa_ctx *owner, const void **kmersDev, uint64_t *n, uint8_t **depthDev);
+int kasa_batch_match_depth_device(kasa_ctx *part, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev);
+int kasa_batch_coherence_finish(kasa_ctx *owner, float *scores, uint64_t *throwsAt);
+
 /* Ranking on the device (Compare::scoringFunc, Compare.hpp:1495-1594 and the printing loops
  * :1721-1754): instead of the whole CSR only what the per-read file can print leaves the device.
  *   den        [nClasses][nTaxa] doubles, row c = 1 + log2(freq[t] * double(uint32(len_c - 3K + 1))) for the c-th distinct

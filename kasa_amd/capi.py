@@ -30,6 +30,7 @@ EXPORTS = [
     "kasa_batch_rank", "kasa_batch_rank_fetch", "kasa_host_alloc", "kasa_host_free", "kasa_thread_device",
     "kasa_batch_queries_device", "kasa_batch_slice_starts", "kasa_batch_set_sorted_device", "kasa_batch_records_device",
     "kasa_batch_records_import_device", "kasa_batch_records_inbox", "kasa_batch_coherence",
+    "kasa_batch_coherence_begin", "kasa_batch_match_depth_device", "kasa_batch_coherence_finish",
     "kasa_ctx_set_taxa_text", "kasa_batch_text", "kasa_batch_text_fetch", "kasa_batch_text_fetch_range", "kasa_text_dtoa", "kasa_ctx_reserve", "kasa_runtime_versions", "kasa_ctx_group_tiles", "kasa_ctx_dense_reads", "kasa_ctx_replay_stats", "kasa_ctx_group_second_chance", "kasa_ctx_record_placement",
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
@@ -795,6 +796,27 @@ class Context:
         sc = np.zeros(self.n_reads, dtype=np.float32)
         at = C.c_uint64(0)
         _check(lib().kasa_batch_coherence(self.h, _p(sc), C.byref(at)))
+        if at.value != 0xFFFFFFFFFFFFFFFF:
+            raise RuntimeError(f"vector::_M_range_check: __n (which is {at.value}) >= this->size() (which is {at.value})")
+        return sc
+
+    # ---- the same in three steps, for a range-partitioned index: begin / finish on the context that owns the reads, the
+    # depth step on every partition's context (kasa_hip.h)
+    def coherence_begin(self):
+        """(device pointer of the batch's k-mers in emission order, their number, device pointer of as many zero depth bytes)."""
+        km, n, dp = C.c_void_p(0), C.c_uint64(0), C.c_void_p(0)
+        _check(lib().kasa_batch_coherence_begin(self.h, C.byref(km), C.byref(n), C.byref(dp)))
+        return int(km.value or 0), int(n.value), int(dp.value or 0)
+
+    def match_depth_device(self, first: int, end: int, ptr: int, n: int, depth_ptr: int):
+        """depth bytes of the k-mers at `ptr` whose 30-bit prefix is in [first, end), against THIS context's index and -k."""
+        _check(lib().kasa_batch_match_depth_device(self.h, C.c_uint64(int(first)), C.c_uint64(int(end)), C.c_void_p(ptr), C.c_uint64(int(n)), C.c_void_p(depth_ptr)))
+
+    def coherence_finish(self) -> np.ndarray:
+        """The walk over the depth bytes: float32[n_reads].  Raises where the reference throws, as coherence() does."""
+        sc = np.zeros(self.n_reads, dtype=np.float32)
+        at = C.c_uint64(0)
+        _check(lib().kasa_batch_coherence_finish(self.h, _p(sc), C.byref(at)))
         if at.value != 0xFFFFFFFFFFFFFFFF:
             raise RuntimeError(f"vector::_M_range_check: __n (which is {at.value}) >= this->size() (which is {at.value})")
         return sc

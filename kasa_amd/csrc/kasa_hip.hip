@@ -31,6 +31,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
@@ -597,6 +598,7 @@ struct kasa_ctx {
     DevBuf txtNames, txtNameOff, txtLen, txtBest, txtBytes, txtOff, txtOut, txtFlags;   // kasa_batch_text
     uint64_t txtTotal = 0; bool txtValid = false;
     const float *cohScores = nullptr;                          // device: the scores of the last kasa_batch_coherence of this batch
+    const void *cohKey = nullptr; bool cohBegun = false;       // kasa_batch_coherence_begin handed this batch's k-mers (cohKey) and depth bytes out; _finish not yet
     bool grouped = false; uint32_t poolUsed = 1; // event records + pool of this batch are in place (group stage or import)
     bool groupCoop = false;                     // group_kernel's cooperative form (long taxon lists were met; sticky)
     bool recSorted = false;                     // ... in sorted order (exported for another rank), not in their slots
@@ -668,6 +670,19 @@ struct kasa_ctx {
                 &esrChainScore, &esrBig};
     }
 };
+
+// The seams kasa_batch_coherence_begin has open in this process: k-mer buffer -> number of k-mers.  kasa_batch_match_depth_device
+// runs on ANOTHER context than the one that owns the buffer; this is how it recognises a wrong `n` for a buffer of ours.
+static std::mutex g_cohMu;
+static std::map<const void *, uint64_t> g_cohSeams;
+static void coh_forget(kasa_ctx *c)                                  // the batch is gone: its scores and its open seam
+{
+    c->cohScores = nullptr;
+    if (!c->cohBegun) return;
+    c->cohBegun = false;
+    std::lock_guard<std::mutex> lk(g_cohMu);
+    g_cohSeams.erase(c->cohKey);
+}
 
 static int timer_begin(kasa_ctx *c, StageTimer &t, hipEvent_t *a, hipEvent_t *b)
 {
@@ -774,6 +789,7 @@ extern "C" void kasa_ctx_destroy(kasa_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device); // the index may already be gone: never touch it here
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    coh_forget(c);
     std::vector<DevBuf *> all = c->buffers();
     for (DevBuf *b : all) b->release();
     auto drop = [](StageTimer &t) {
@@ -866,7 +882,7 @@ static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets
     if (nSeq < 0 || nReads < 0 || (nSeq > 0 && (!offsets || !bases))) return fail(KASA_E_ARG, "kasa_batch_upload: bad arguments");
     if ((uint64_t)nReads >= 0xFFFFFFF0ull || (uint64_t)nSeq >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_upload: more than 2^32 reads in one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->cohScores = nullptr; c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
     c->recOut = nullptr; c->recSorted = false;
     const int64_t zero = 0;
     if (nSeq == 0) { offsets = &zero; resident = false; }
@@ -1316,6 +1332,7 @@ extern "C" int kasa_batch_encode(kasa_ctx *c, uint64_t *nKmers)
     HIPCHK(hipSetDevice(c->ix->device));
     int rc;
     const uint64_t nQ = c->nQ;
+    coh_forget(c);                                                          // (an open coherence seam points into qKmerA)
     if ((rc = c->qKmerA.reserve(nQ * c->keyBytes() + 64)) || (rc = c->qReadA.reserve(nQ * 4 + 64))) return rc;
     hipEvent_t a, b;
     if ((rc = timer_begin(c, c->timers[KASA_STAGE_ENCODE], &a, &b))) return rc;
@@ -6801,7 +6818,7 @@ extern "C" int kasa_batch_set_sorted_device(kasa_ctx *c, const void *kmersDev, u
     if (!c || (n && !kmersDev)) return fail(KASA_E_ARG, "kasa_batch_set_sorted_device: bad arguments");
     if (n >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_set_sorted_device: too many queries for one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->cohScores = nullptr;
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c);
     c->recOut = nullptr; c->recSorted = false;                       // the last batch's exported records (the caller's buffer) are not this batch's
     int rc;
     if ((rc = c->qKmerB.reserve(n * c->keyBytes() + 64))) return rc;
@@ -7645,14 +7662,19 @@ extern "C" int kasa_text_dtoa(int device, const double *values, uint32_t n, char
 static constexpr uint32_t COH_CHUNK = 64;
 static constexpr unsigned long long COH_NONE = ~0ull;
 
+// Depth of every emitted k-mer whose 6-letter prefix lies in [firstPrefix, endPrefix) against ONE index -- the whole one
+// (the range is everything) or a range partition of it.  A depth needs RANGE_LETTERS letters in common with an index
+// neighbour and partitions are cut between `_trie` entries, so only the partition that owns a k-mer's prefix can give it a
+// depth: the others skip it before they touch their index and leave its byte alone.
 template <class Key>
-__global__ void coh_depth_kernel(const Key *__restrict__ q, uint64_t nQ, const Key *__restrict__ idxKmer, uint32_t nIdx,
-                                 const uint32_t *__restrict__ table, int tb, int kHigh, int kLow, uint8_t *__restrict__ len,
-                                 unsigned long long *__restrict__ firstMatch)
+__global__ void coh_depth_kernel(const Key *__restrict__ q, uint64_t nQ, uint64_t firstPrefix, uint64_t endPrefix, const Key *__restrict__ idxKmer,
+                                 uint32_t nIdx, const uint32_t *__restrict__ table, int tb, int kHigh, int kLow, uint8_t *__restrict__ len)
 {
     const uint64_t o = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
     if (o >= nQ) return;
     const Key k = q[o];
+    const uint64_t pre = (uint64_t)(k >> (5 * (KeyTraits<Key>::LETTERS - RANGE_LETTERS)));
+    if (pre < firstPrefix || pre >= endPrefix) return;
     const uint32_t lo = lower_bound_global<Key>(idxKmer, table, tb, k);
     const int la = (lo < nIdx) ? lcp_letters<Key>(k, idxKmer[lo]) : 0;
     const int lb = (lo > 0) ? lcp_letters<Key>(k, idxKmer[lo - 1]) : 0;
@@ -7665,7 +7687,31 @@ __global__ void coh_depth_kernel(const Key *__restrict__ q, uint64_t nQ, const K
         if (d < kLow) d = 0;
     }
     len[o] = (uint8_t)d;
-    if (d) atomicMin(firstMatch, (unsigned long long)o);
+}
+
+// the first k-mer with a depth (where the reference's walk begins, Compare.hpp:2630-2646), from the depth bytes alone: 16
+// bytes per thread, the lowest matching lane of a wavefront holds its minimum, one atomic per block
+static constexpr uint32_t COH_FIRST_BYTES = 16;
+__global__ void coh_first_kernel(const uint8_t *__restrict__ len, uint64_t n, unsigned long long *__restrict__ firstMatch)
+{
+    __shared__ unsigned long long sMin;
+    if (threadIdx.x == 0) sMin = COH_NONE;
+    __syncthreads();
+    const uint64_t o = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * COH_FIRST_BYTES;
+    unsigned long long mine = COH_NONE;
+    if (o + COH_FIRST_BYTES <= n) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(len + o);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 3; i >= 0; --i) if (w[i]) mine = o + 4u * i + ((uint32_t)__builtin_ctz(w[i]) >> 3);
+    } else {
+        for (uint64_t i = o; i < n; ++i) if (len[i]) { mine = i; break; }
+    }
+    const bool has = mine != COH_NONE;
+    const unsigned long long m = __ballot(has);
+    if (has && (m & ((1ull << (threadIdx.x & 63)) - 1ull)) == 0ull) atomicMin(&sMin, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && sMin != COH_NONE) atomicMin(firstMatch, sMin);
 }
 
 // where the walk stands among the emitted k-mers: element idx, the read it belongs to and that read's k-mers
@@ -7775,21 +7821,65 @@ __global__ void coh_any_kernel(const uint32_t *__restrict__ failed, uint32_t n, 
     if (t < n && failed[t]) atomicOr(any, 1u);
 }
 
-extern "C" int kasa_batch_coherence(kasa_ctx *c, float *scores, uint64_t *throwsAt)
+// what kasa_batch_coherence and kasa_batch_coherence_begin ask of the batch (`who`: the call's name in the message)
+static int coh_check_batch(kasa_ctx *c, const char *who)
 {
-    if (!c || !scores || !throwsAt) return fail(KASA_E_ARG, "kasa_batch_coherence: NULL argument");
-    *throwsAt = ~0ull;
-    if (c->state < 3) return fail(KASA_E_STATE, "kasa_batch_coherence: batch not sorted");
-    if (c->haveSeqRead) return fail(KASA_E_ARG, "kasa_batch_coherence: paired-end input is not supported (the reference's result depends on its unstable sort of the mates' k-mers)");
-    if (c->uniqueDone) return fail(KASA_E_ARG, "kasa_batch_coherence: not together with -e (the reference's result depends on which duplicates its unstable sort leaves)");
-    if (!c->readsUploaded || c->nSeq != c->nReads) return fail(KASA_E_STATE, "kasa_batch_coherence: the batch was not uploaded as reads");
+    if (c->state < 3) return fail(KASA_E_STATE, "%s: batch not sorted", who);
+    if (c->haveSeqRead) return fail(KASA_E_ARG, "%s: paired-end input is not supported (the reference's result depends on its unstable sort of the mates' k-mers)", who);
+    if (c->uniqueDone) return fail(KASA_E_ARG, "%s: not together with -e (the reference's result depends on which duplicates its unstable sort leaves)", who);
+    if (!c->readsUploaded || c->nSeq != c->nReads) return fail(KASA_E_STATE, "%s: the batch was not uploaded as reads", who);
+    return KASA_OK;
+}
+
+// (1a) the k-mers once more, in emission order (the sort has consumed them), and a zero depth for each
+static int coh_begin(kasa_ctx *c)
+{
     HIPCHK(hipSetDevice(c->ix->device));
-    const uint32_t nReads = (uint32_t)c->nReads;
-    if (nReads == 0) return KASA_OK;
-    // (1) the k-mers once more, in emission order (the sort has consumed them), and the depth of each
+    coh_forget(c);
     const uint64_t nE = c->nEmitted;
     int rc;
     if ((rc = c->qKmerA.reserve(nE * c->keyBytes() + 64)) || (rc = c->qReadA.reserve(nE * 4 + 64)) || (rc = c->cohLen.reserve(nE + 64))) return rc;
+    if (nE > 0 && c->nSeq > 0) {
+        const unsigned blocks = (unsigned)std::min<int64_t>((c->nSeq + ENC_WAVES - 1) / ENC_WAVES, 256 * 16);
+        if (c->ix->wide)
+            encode_kernel<key128><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(), c->seqOff.as<uint64_t>(), nullptr, c->nSeq,
+                c->kLow, c->strands(), c->enc_mode(), c->lut.as<uint8_t>(), c->qKmerA.as<key128>(), c->qReadA.as<uint32_t>(), 0, nullptr, nullptr, ~0ull);
+        else
+            encode_kernel<uint64_t><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(), c->seqOff.as<uint64_t>(), nullptr, c->nSeq,
+                c->kLow, c->strands(), c->enc_mode(), c->lut.as<uint8_t>(), c->qKmerA.as<uint64_t>(), c->qReadA.as<uint32_t>(), 0, nullptr, nullptr, ~0ull);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(c->cohLen.p, 0, nE, c->stream));
+    }
+    c->cohBegun = true; c->cohKey = c->qKmerA.p;
+    std::lock_guard<std::mutex> lk(g_cohMu);
+    g_cohSeams[c->cohKey] = nE;
+    return KASA_OK;
+}
+
+// (1b) the depth of the k-mers whose prefix is in [firstPrefix, endPrefix) against p's index, on p's stream
+static int coh_depth(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev)
+{
+    if (n == 0 || firstPrefix == endPrefix) return KASA_OK;
+    if (p->ix->wide)
+        coh_depth_kernel<key128><<<blocks_for(n, 256), 256, 0, p->stream>>>(static_cast<const key128 *>(kmersDev), n, firstPrefix, endPrefix, p->ix->kmer.as<key128>(),
+            (uint32_t)p->ix->n, p->ix->table.as<uint32_t>(), p->ix->tb, p->kHigh, p->kLow, depthDev);
+    else
+        coh_depth_kernel<uint64_t><<<blocks_for(n, 256), 256, 0, p->stream>>>(static_cast<const uint64_t *>(kmersDev), n, firstPrefix, endPrefix, p->ix->kmer.as<uint64_t>(),
+            (uint32_t)p->ix->n, p->ix->table.as<uint32_t>(), p->ix->tb, p->kHigh, p->kLow, depthDev);
+    HIPCHK(hipGetLastError());
+    return KASA_OK;
+}
+
+// (1c) the first match from the depth bytes; (2), (3) the walk: all chunks, then the chunks whose entry was not what their
+// predecessor left, until none is
+static int coh_finish(kasa_ctx *c, float *scores, uint64_t *throwsAt, const char *who)
+{
+    HIPCHK(hipSetDevice(c->ix->device));
+    coh_forget(c);
+    const uint32_t nReads = (uint32_t)c->nReads;
+    if (nReads == 0) return KASA_OK;
+    const uint64_t nE = c->nEmitted;
+    int rc;
     const uint32_t nChunks = (nReads + COH_CHUNK - 1) / COH_CHUNK;
     if ((rc = c->cohState.reserve((size_t)nChunks * 20 + (size_t)nReads * 4 + 256))) return rc;
     unsigned long long *entryUsed = c->cohState.as<unsigned long long>(), *exitIdx = entryUsed + nChunks;
@@ -7800,21 +7890,9 @@ extern "C" int kasa_batch_coherence(kasa_ctx *c, float *scores, uint64_t *throws
     HIPCHK(hipMemsetAsync(firstMatch, 0xFF, 8, c->stream));
     HIPCHK(hipMemsetAsync(changed, 0, 12, c->stream));
     if (nE > 0) {
-        const unsigned blocks = (unsigned)std::min<int64_t>((c->nSeq + ENC_WAVES - 1) / ENC_WAVES, 256 * 16);
-        if (c->ix->wide) {
-            encode_kernel<key128><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(), c->seqOff.as<uint64_t>(), nullptr, c->nSeq,
-                c->kLow, c->strands(), c->enc_mode(), c->lut.as<uint8_t>(), c->qKmerA.as<key128>(), c->qReadA.as<uint32_t>(), 0, nullptr, nullptr, ~0ull);
-            coh_depth_kernel<key128><<<blocks_for(nE, 256), 256, 0, c->stream>>>(c->qKmerA.as<key128>(), nE, c->ix->kmer.as<key128>(), (uint32_t)c->ix->n,
-                c->ix->table.as<uint32_t>(), c->ix->tb, c->kHigh, c->kLow, c->cohLen.as<uint8_t>(), firstMatch);
-        } else {
-            encode_kernel<uint64_t><<<blocks, 64 * ENC_WAVES, 0, c->stream>>>(c->basesPtr, c->baseOff.as<int64_t>(), c->seqOff.as<uint64_t>(), nullptr, c->nSeq,
-                c->kLow, c->strands(), c->enc_mode(), c->lut.as<uint8_t>(), c->qKmerA.as<uint64_t>(), c->qReadA.as<uint32_t>(), 0, nullptr, nullptr, ~0ull);
-            coh_depth_kernel<uint64_t><<<blocks_for(nE, 256), 256, 0, c->stream>>>(c->qKmerA.as<uint64_t>(), nE, c->ix->kmer.as<uint64_t>(), (uint32_t)c->ix->n,
-                c->ix->table.as<uint32_t>(), c->ix->tb, c->kHigh, c->kLow, c->cohLen.as<uint8_t>(), firstMatch);
-        }
+        coh_first_kernel<<<blocks_for(nE, 256 * COH_FIRST_BYTES), 256, 0, c->stream>>>(c->cohLen.as<uint8_t>(), nE, firstMatch);
         HIPCHK(hipGetLastError());
     }
-    // (2), (3) the walk: all chunks, then the chunks whose entry was not what their predecessor left, until none is
     const uint64_t *emitOff = c->seqOff.as<uint64_t>();                                // k-mers before every read, as emitted (kmerOff follows -e)
     for (int round = 0;; ++round) {
         coh_chunk_kernel<<<blocks_for(nChunks, 64), 64, 0, c->stream>>>(c->cohLen.as<uint8_t>(), emitOff, nReads, nE, (uint32_t)c->strands(), firstMatch, round,
@@ -7826,7 +7904,7 @@ extern "C" int kasa_batch_coherence(kasa_ctx *c, float *scores, uint64_t *throws
         HIPCHK(hipMemsetAsync(changed, 0, 8, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (h[0] == 0u) break;                                                         // every recomputed chunk left where it had left before
-        if (round > (int)nChunks + 2) return fail(KASA_E_LIMIT, "kasa_batch_coherence: the walk did not settle");
+        if (round > (int)nChunks + 2) return fail(KASA_E_LIMIT, "%s: the walk did not settle", who);
     }
     coh_any_kernel<<<blocks_for(nChunks, 256), 256, 0, c->stream>>>(failed, nChunks, changed + 2);
     uint32_t anyFail = 0;
@@ -7836,6 +7914,59 @@ extern "C" int kasa_batch_coherence(kasa_ctx *c, float *scores, uint64_t *throws
     if (anyFail) *throwsAt = nE;
     c->cohScores = dScores;
     return KASA_OK;
+}
+
+extern "C" int kasa_batch_coherence(kasa_ctx *c, float *scores, uint64_t *throwsAt)
+{
+    if (!c || !scores || !throwsAt) return fail(KASA_E_ARG, "kasa_batch_coherence: NULL argument");
+    *throwsAt = ~0ull;
+    int rc;
+    if ((rc = coh_check_batch(c, "kasa_batch_coherence"))) return rc;
+    if (c->nReads == 0) { HIPCHK(hipSetDevice(c->ix->device)); return KASA_OK; }
+    // begin, the depth of every k-mer against the context's own index, finish: all on the context's stream, nothing to wait for
+    if ((rc = coh_begin(c)) || (rc = coh_depth(c, 0, 1ull << (5 * RANGE_LETTERS), c->qKmerA.p, c->nEmitted, c->cohLen.as<uint8_t>()))) { coh_forget(c); return rc; }
+    return coh_finish(c, scores, throwsAt, "kasa_batch_coherence");
+}
+
+// The same in three steps for a range-partitioned index (C5): begin and finish on the context that owns the reads, the
+// depth step once per partition on that partition's context.  Every call leaves its stream idle, so the next one -- on
+// another context, later on another device -- finds its input complete (as the other *_device calls do).
+extern "C" int kasa_batch_coherence_begin(kasa_ctx *c, const void **kmersDev, uint64_t *n, uint8_t **depthDev)
+{
+    if (!c || !kmersDev || !n || !depthDev) return fail(KASA_E_ARG, "kasa_batch_coherence_begin: NULL argument");
+    *kmersDev = nullptr; *n = 0; *depthDev = nullptr;
+    int rc;
+    if ((rc = coh_check_batch(c, "kasa_batch_coherence_begin"))) return rc;
+    if ((rc = coh_begin(c))) { coh_forget(c); return rc; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *kmersDev = c->qKmerA.p; *n = c->nEmitted; *depthDev = c->cohLen.as<uint8_t>();
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_match_depth_device(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev)
+{
+    if (!p || (n && (!kmersDev || !depthDev))) return fail(KASA_E_ARG, "kasa_batch_match_depth_device: NULL argument");
+    if (firstPrefix > endPrefix || endPrefix > (1ull << (5 * RANGE_LETTERS)))
+        return fail(KASA_E_ARG, "kasa_batch_match_depth_device: [%llu, %llu) is not a range of 30-bit prefixes", (unsigned long long)firstPrefix, (unsigned long long)endPrefix);
+    {
+        std::lock_guard<std::mutex> lk(g_cohMu);
+        auto it = g_cohSeams.find(kmersDev);
+        if (it != g_cohSeams.end() && it->second != n)
+            return fail(KASA_E_ARG, "kasa_batch_match_depth_device: n = %llu, the batch these k-mers belong to has %llu", (unsigned long long)n, (unsigned long long)it->second);
+    }
+    HIPCHK(hipSetDevice(p->ix->device));
+    int rc;
+    if ((rc = coh_depth(p, firstPrefix, endPrefix, kmersDev, n, depthDev))) return rc;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_coherence_finish(kasa_ctx *c, float *scores, uint64_t *throwsAt)
+{
+    if (!c || !scores || !throwsAt) return fail(KASA_E_ARG, "kasa_batch_coherence_finish: NULL argument");
+    *throwsAt = ~0ull;
+    if (!c->cohBegun || c->state < 3) return fail(KASA_E_STATE, "kasa_batch_coherence_finish: no kasa_batch_coherence_begin on this batch");
+    return coh_finish(c, scores, throwsAt, "kasa_batch_coherence_finish");
 }
 
 // Page-locked host memory for the buffers that cross PCIe (reads in, ranked hits or CSR out): transfers from pageable
@@ -8247,7 +8378,7 @@ static int batch_set_queries_impl(kasa_ctx *c, const void *kmers, const uint32_t
     if (nReads < 0 || (n && (!kmers || !reads))) return fail(KASA_E_ARG, "kasa_batch_set_queries: bad arguments");
     if (n >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_set_queries: too many queries for one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->cohScores = nullptr; c->readsUploaded = false; c->recOut = nullptr; c->recSorted = false;
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->readsUploaded = false; c->recOut = nullptr; c->recSorted = false;
     std::vector<uint64_t> koff((size_t)nReads + 1, 0);
     uint32_t maxCnt = 0;
     for (uint64_t i = 0; i < n; ++i) {

@@ -10,7 +10,8 @@
 // (main.cpp:699-875, 1336-1362: an existing index edited on the device), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
 // (index replicated, one RCCL all-reduce of the profile tables).  Input is streamed in chunks, batches are cut where the
 // reference cuts them (-m) and parsed / computed / written in a pipeline.
-// Not supported here (reported as errors, never silently ignored): --visualize; --coherence together with -e or paired-end input.  128-bit indices (build --kH 25) are read as they are (20-byte records).
+// Not supported here (reported as errors, never silently ignored): --visualize; --coherence together with -e, with paired-end input or over sequences
+// read in pieces (over an index in range partitions -- 2^32 records and more -- it runs: one depth call per partition).  128-bit indices (build --kH 25) are read as they are (20-byte records).
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -216,7 +217,7 @@ static vector<uint64_t> loadFreq(const string &prefix, size_t nTaxa, int kHigh, 
 }
 
 // KASA_HOST_TIMING=1: where the host spends the time of "Time fastq" (seconds, summed over the file)
-struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, encode = 0, sort = 0, score = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
+struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
 static HostTimers g_ht;
 static std::chrono::steady_clock::time_point g_t0 = std::chrono::steady_clock::now();
 static void mark(const char *what, uint64_t id = ~0ull)          // KASA_HOST_TIMING: a time line of the file's pipeline
@@ -1529,7 +1530,22 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, cons
     if (p.coherence) {
         coherence.assign(nr, 0.f);
         uint64_t throwsAt = ~0ull;
-        if (kasa_batch_coherence(ctx, coherence.data(), &throwsAt)) throwLast();
+        ScopedTimerMt tm(g_ht.coherence, g_ht.mu);
+        if (partCtx.empty()) { if (kasa_batch_coherence(ctx, coherence.data(), &throwsAt)) throwLast(); }
+        else {
+            // a partitioned index: only the partition that owns a k-mer's 6-letter prefix can give it a match length, so every
+            // partition's context fills in the depths of its own prefix range and the walk runs here (kasa_hip.h)
+            const size_t nP = partCtx.size();
+            const void *km = nullptr; uint64_t ne = 0; uint8_t *depth = nullptr;
+            { ScopedTimerMt t2(g_ht.cohBegin, g_ht.mu); if (kasa_batch_coherence_begin(ctx, &km, &ne, &depth)) throwLast(); }
+            {
+                ScopedTimerMt t2(g_ht.cohDepth, g_ht.mu);
+                for (size_t j = 0; j < nP; ++j)
+                    if (kasa_batch_match_depth_device(partCtx[j], ixf.cuts[j], j + 1 < nP ? ixf.cuts[j + 1] : (uint64_t)1 << 30, km, ne, depth)) throwLast();
+            }
+            ScopedTimerMt t2(g_ht.cohFinish, g_ht.mu);
+            if (kasa_batch_coherence_finish(ctx, coherence.data(), &throwsAt)) throwLast();
+        }
         if (throwsAt != ~0ull)                                   // the reference's walk runs off the end of its vector here (vector::at)
             throw std::runtime_error("vector::_M_range_check: __n (which is " + std::to_string(throwsAt) + ") >= this->size() (which is " + std::to_string(throwsAt) + ")");
     }
@@ -1842,6 +1858,11 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         std::cout << "OUT: host timing: read " << g_ht.read << " s, cut " << g_ht.cut << " s, parse " << g_ht.parse << " s, merge " << g_ht.merge
                   << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
                   << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s" << std::endl;
+    if (p.verbose && g_ht.on && p.coherence) {                   // (every call of the step returns with the device idle: host clock = device time + launches)
+        std::cout << "OUT: coherence: " << g_ht.coherence << " s";
+        if (!ixf.parts.empty()) std::cout << " (begin " << g_ht.cohBegin << ", depth over the partitions " << g_ht.cohDepth << ", finish " << g_ht.cohFinish << ")";
+        std::cout << std::endl;
+    }
     if (p.verbose && g_ht.on) {
         std::cout << "OUT: device stages (HIP events, ms):";
         const char *nm[] = {"encode", "sort", "lookup", "group", "regroup", "score"};
@@ -2776,7 +2797,6 @@ static int run(int argc, char **argv)
             if (ok) { if (r != ixf.nRec) throw std::runtime_error("the trie file does not add up to the index's records"); break; }
             if (nParts >= m) throw std::runtime_error("the index cannot be cut into partitions of at most " + std::to_string(maxPart) + " records between its trie entries");
         }
-        if (p.coherence) throw std::runtime_error("--coherence over an index of 2^32 records and more is not supported");
         ixf.parts.resize(p.devices.size());
         for (uint64_t j = 0; j < nParts; ++j) ixf.cuts.push_back(j == 0 ? 0 : (uint64_t)ixf.tp[tLo[j]]);
         for (size_t d = 0; d < p.devices.size(); ++d) {

@@ -11,6 +11,10 @@ The sorted index is cut at 30-bit prefix boundaries -- a prefix range of the ref
     owner   : concatenate the event records in partition order (= global sorted order), shift positions
               by the slice start and segment-list offsets by the pool offset, file them by read, score
                                                                         (kasa_batch_records_import/score)
+    --coherence, after the score:
+    owner   : the k-mers once more in emission order, a zero depth byte each   (kasa_batch_coherence_begin)
+    worker j: the depth of the k-mers whose prefix partition j owns            (kasa_batch_match_depth_device)
+    owner   : the reference's walk over the depth bytes                        (kasa_batch_coherence_finish)
 
 A slice is a batch of its own for the worker: its first query opens a new prefix range, so nothing of
 the grouping reaches across a cut, and the result equals the run against the unpartitioned index bit for
@@ -171,6 +175,17 @@ class LocalExchange:
         ctx.records_import(rec, pool)
         ctx.score(want_per_read)
         return ctx
+
+    def coherence(self) -> np.ndarray:
+        """--coherence scores of the batch run_batch has just scored: float32[n_reads], equal to Context.coherence() on the
+        whole index.  Only the partition that owns a k-mer's 30-bit prefix can give it a match length (at least 6 letters
+        in common with an index entry; cuts lie between `_trie` entries), so every worker fills in the depths of its own
+        prefix range and the owner walks them.  The depth bytes stay on the device for both settings of device_resident."""
+        ptr, n, depth = self.owner.coherence_begin()
+        ends = [int(c) for c in self.cuts[1:]] + [1 << (5 * formats.TRIE_LETTERS)]
+        for j, w in enumerate(self.workers):
+            w.ctx.match_depth_device(int(self.cuts[j]), ends[j], ptr, n, depth)
+        return self.owner.coherence_finish()
 
     def close(self):
         self.owner.close()

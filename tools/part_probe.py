@@ -1,6 +1,9 @@
 """kasa_identify over the bench's synthetic index (4.2e8 records) as ONE index object and as range partitions of at most
 --part-records records (KASA_INDEX_PART_RECORDS): same bytes out, and what the partitions cost.  Files in /dev/shm.
-    python tools/part_probe.py [--reads 2000000] [--part-records 100000000]
+    python tools/part_probe.py [--reads 2000000] [--part-records 100000000] [--coherence]
+--coherence: both runs with --coherence; the JSON then carries the time of the coherence step (the driver's clock around
+kasa_batch_coherence, or around begin + one kasa_batch_match_depth_device per partition + finish: every one of these calls
+returns with the device idle) and of the same runs' other device work.
 Prints one JSON object."""
 import argparse
 import hashlib
@@ -20,6 +23,7 @@ def main():
     ap.add_argument("--reads", type=int, default=2_000_000)
     ap.add_argument("--part-records", type=int, default=100_000_000)
     ap.add_argument("--memory", type=int, default=1024)
+    ap.add_argument("--coherence", action="store_true")
     args = ap.parse_args()
     import numpy as np
     from kasa_amd import build, formats, synth
@@ -36,13 +40,13 @@ def main():
             for a in range(0, reads.n, 200000):
                 blk = bases[a:a + 200000]
                 f.write(b"".join(b"@r%d\n%s\n+\n%s\n" % (a + i, blk[i].tobytes(), b"I" * 150) for i in range(blk.shape[0])))
-        res = {"reads": reads.n, "index_records": int(ix.n)}
+        res = {"reads": reads.n, "index_records": int(ix.n), "coherence": bool(args.coherence)}
         sums = {}
         for name, env in (("one_index", {}), ("partitions", {"KASA_INDEX_PART_RECORDS": str(args.part_records)})):
             out, prof = os.path.join(d, "out_%s.jsonl" % name), os.path.join(d, "prof_%s.csv" % name)
             t0 = time.perf_counter()
             r = subprocess.run([exe, "identify", "-c", os.path.join(d, "content.txt"), "-d", os.path.join(d, "idx"), "-i", fq, "-q", out, "-p", prof,
-                                "--jsonl", "-v", "-m", str(args.memory)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
+                                "--jsonl", "-v", "-m", str(args.memory)] + (["--coherence"] if args.coherence else []), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1200,
                                env=dict(os.environ, KASA_HOST_TIMING="1", **env))
             wall = time.perf_counter() - t0
             if r.returncode != 0:
@@ -55,11 +59,20 @@ def main():
                         t[key] = float(line.split(":")[2].split()[0])
                 if line.startswith("OUT: Index of"):
                     t["partitions"] = int(line.split()[6])
+                if line.startswith("OUT: coherence"):
+                    w = line.replace(",", " ").replace(")", " ").split()
+                    t["coherence_s"] = float(w[2])
+                    if "begin" in w:                                  # partitions: begin / one depth call per partition / finish
+                        t["coherence_parts_s"] = {"begin": float(w[w.index("begin") + 1]), "depth": float(w[w.index("partitions") + 1]), "finish": float(w[w.index("finish") + 1])}
                 if line.startswith("OUT: device stages"):
                     t["device_stages_ms"] = line.split(":", 2)[2].strip()
             sums[name] = [hashlib.sha256(open(p, "rb").read()).hexdigest() for p in (out, prof)]
             res[name] = {"file_s": t.get("Time file"), "device_s": t.get("Time compare"), "partitions": t.get("partitions", 1), "wall_s_incl_index_load": round(wall, 2),
                          "device_stages_ms": t.get("device_stages_ms")}
+            if args.coherence:
+                res[name]["coherence_s"] = t.get("coherence_s")
+                if "coherence_parts_s" in t:
+                    res[name]["coherence_parts_s"] = t["coherence_parts_s"]
             os.unlink(out)
         res["same_bytes"] = len(sums) == 2 and sums["one_index"] == sums["partitions"]
         print(json.dumps(res))
