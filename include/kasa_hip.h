@@ -156,6 +156,7 @@ int kasa_batch_group(kasa_ctx *ctx, int coverage);
 /* kasa_batch_group with the records written straight into the caller's device buffer (room for
  * number of queries x record words u32): the partition worker groups a slice into the tensor its collective sends, no copy
  * in between.  kasa_batch_records_device then reports that pointer; the pool stays the context's. */
+/* (recordsOutDev must lie on the context's device -- group_kernel stores into it: KASA_E_ARG names the two devices otherwise) */
 int kasa_batch_group_to(kasa_ctx *ctx, int coverage, uint32_t *recordsOutDev);
 int kasa_batch_score(kasa_ctx *ctx, int wantPerRead);
 int kasa_batch_records_size(kasa_ctx *ctx, uint64_t *nRecordWords, uint64_t *nPoolWords);
@@ -165,7 +166,11 @@ int kasa_batch_records_import(kasa_ctx *ctx, const uint32_t *records, uint64_t n
 /* The same exchange without the host: slices of the sorted queries and the records made from
  * them are handed over as DEVICE pointers, so the caller's collective (RCCL all_to_all over xGMI) moves them from HBM to
  * HBM.  Pointers returned by the *_device getters point into the context's own buffers and stay valid until its next
- * batch call; pointers passed in may live on the context's device or on a peer whose memory it can address.
+ * batch call.  Pointers passed in may lie on ANY device of the process: what they name is copied to (or from) a buffer on the
+ * context's own device before (after) a kernel works on it, so no kernel ever touches another device's memory and peer access
+ * is neither needed nor enabled.  The few calls whose kernels work in the caller's buffer itself (kasa_batch_group_to,
+ * kasa_batch_records_pack_size / _pack / _unpack, kasa_batch_upload_device) return KASA_E_ARG, naming both devices, for a
+ * buffer that lies elsewhere.
  *   kasa_batch_queries_device         the sorted k-mers of the batch (8 or 16 bytes each) and their number
  *   kasa_batch_slice_starts           starts[j] = first sorted query whose 30-bit prefix is >= cuts[j] (starts[0] = 0,
  *                                     starts[nParts] = number of queries): slice j goes to the owner of partition j
@@ -175,7 +180,8 @@ int kasa_batch_records_import(kasa_ctx *ctx, const uint32_t *records, uint64_t n
  *   kasa_batch_records_device         records (sorted order) and pool of the grouped slice
  *   kasa_batch_records_import_device  the slices' records, in partition order, become the batch's records: positions
  *                                     move by the slice starts and pool offsets by the pool bases on the device
- *                                     (what kasa_amd/partition.py:assemble_records does for the host path) */
+ *                                     (what kasa_amd/partition.py:assemble_records does for the host path); records that
+ *                                     are not in their place of the inbox yet are copied there first, pools are copied */
 int kasa_batch_queries_device(kasa_ctx *ctx, const void **kmers, uint64_t *n);
 int kasa_batch_slice_starts(kasa_ctx *ctx, const uint64_t *cuts, uint32_t nParts, uint64_t *starts);
 int kasa_batch_set_sorted_device(kasa_ctx *ctx, const void *kmersDev, uint64_t n);
@@ -231,15 +237,29 @@ int kasa_batch_coherence(kasa_ctx *ctx, float *scores, uint64_t *throwsAt);
  *                                  level of k-mer i that this context's index matches, by this context's -k (at least 6
  *                                  letters, cut before the first '^', 0 below the lowest level: Compare.hpp:803-829,847-948).
  *                                  K-mers of other prefixes are skipped before the index is touched and their bytes are
- *                                  left as they are.  kmersDev and depthDev may lie on a peer device; the batch this
+ *                                  left as they are.  kmersDev and depthDev may lie on any device; the batch this
  *                                  context holds is not disturbed.  n must be the n of _begin.
  *   kasa_batch_coherence_finish    on the owner, once every partition has had its call: finds the first matching k-mer
  *                                  (Compare.hpp:2630-2646) from the depth bytes and walks them (Compare.hpp:2663-2728);
  *                                  scores, *throwsAt and the effect on kasa_batch_text as kasa_batch_coherence.
+ * kmersDev and depthDev are copied to the partition's device and the bytes back (no kernel of `part` reads or writes them in
+ * place), so they may lie anywhere.  With the partitions on several devices the same step in two halves, one per device:
+ *   kasa_batch_match_depth_stage   on the partition context: copies the n k-mers to its own device, zeroes n depth bytes of its
+ *                                  own, runs the same kernel over [firstPrefix, endPrefix) and hands those bytes out
+ *                                  (*depthDev: valid until the context's next depth call; a byte is non-zero only where this
+ *                                  partition gave a depth).  Arguments and errors as kasa_batch_match_depth_device.
+ *   kasa_batch_coherence_fold      on the owner, between _begin and _finish: copies such bytes to its device and takes the
+ *                                  bytewise maximum with the batch's depth bytes.  A k-mer has a depth in at most one
+ *                                  partition, so after one fold per partition the bytes are what one
+ *                                  kasa_batch_match_depth_device per partition leaves.  n must be the n of _begin.
+ *                                  Stages of different partition contexts may run at the same time (one host thread
+ *                                  each); the folds are the owner's calls, one after the other.
  * Each call returns with its stream idle, so a host needs no synchronisation of its own between contexts.  KASA_E_STATE:
- * _finish without _begin on this batch; KASA_E_ARG: firstPrefix > endPrefix or beyond 2^30, an n that is not the batch's. */
+ * _finish or _fold without _begin on this batch; KASA_E_ARG: firstPrefix > endPrefix or beyond 2^30, an n that is not the batch's. */
 int kasa_batch_coherence_begin(kasa_ctx *owner, const void **kmersDev, uint64_t *n, uint8_t **depthDev);
 int kasa_batch_match_depth_device(kasa_ctx *part, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev);
+int kasa_batch_match_depth_stage(kasa_ctx *part, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, const uint8_t **depthDev);
+int kasa_batch_coherence_fold(kasa_ctx *owner, const uint8_t *depthDev, uint64_t n);
 int kasa_batch_coherence_finish(kasa_ctx *owner, float *scores, uint64_t *throwsAt);
 
 /* Ranking on the device (Compare::scoringFunc, Compare.hpp:1495-1594 and the printing loops
@@ -314,6 +334,10 @@ int kasa_device_alloc(int device, size_t bytes, void **out);
 int kasa_device_free(int device, void *p);
 int kasa_device_write(int device, void *dst, const void *src, size_t bytes);
 int kasa_device_read(int device, void *dst, const void *src, size_t bytes);
+/* Device memory to device memory, on one device or between two; no peer access is needed (or enabled).  Returns when the bytes
+ * are there.  Not a context call: host threads may copy into disjoint places of one buffer at the same time (the partitions'
+ * records into the owner's kasa_batch_records_inbox). */
+int kasa_device_copy(int dstDevice, void *dst, int srcDevice, const void *src, size_t bytes);
 /* Binds the CALLING host thread to a device.  A fresh thread stands on device 0, and kasa_host_alloc page-locks for the
  * thread's current device: a helper thread that prepares a worker's buffers calls this first (the kasa_ctx_* / kasa_batch_*
  * calls select their context's device themselves). */
@@ -325,7 +349,9 @@ int kasa_profile_reset(kasa_ctx *ctx);
  * a sum over (group, taxon) of the group's hits (Compare.hpp:922-925), from the sorted queries -- with 32-byte records (up to 8
  * levels) kasa_batch_score adds nothing to the tables; with 64-byte records (9-25 levels, the 128-bit index's default k range)
  * the profile still comes from the per-read side, i.e. from kasa_batch_score.  A context that groups slices for another one
- * (the partition worker of a range-partitioned index) hands its tables on with this call.  Same device, k range and taxa. */
+ * (the partition worker of a range-partitioned index) hands its tables on with this call.  Same k range and taxa; the two
+ * contexts may sit on different devices (src's tables are copied to dst's device and added there -- one path for both cases,
+ * exact integer sums).  This is also how the owners of a file's batches are summed in one process without a communicator. */
 int kasa_profile_absorb(kasa_ctx *dst, kasa_ctx *src);
 /* countAll as double (exact 64.64 fixed-point sums rounded once), countUnique, countTotal; any may
  * be NULL.  nK * nTaxa entries each. */

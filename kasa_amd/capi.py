@@ -31,6 +31,7 @@ EXPORTS = [
     "kasa_batch_queries_device", "kasa_batch_slice_starts", "kasa_batch_set_sorted_device", "kasa_batch_records_device",
     "kasa_batch_records_import_device", "kasa_batch_records_inbox", "kasa_batch_coherence",
     "kasa_batch_coherence_begin", "kasa_batch_match_depth_device", "kasa_batch_coherence_finish",
+    "kasa_batch_match_depth_stage", "kasa_batch_coherence_fold", "kasa_device_copy",
     "kasa_ctx_set_taxa_text", "kasa_batch_text", "kasa_batch_text_fetch", "kasa_batch_text_fetch_range", "kasa_text_dtoa", "kasa_ctx_reserve", "kasa_runtime_versions", "kasa_ctx_group_tiles", "kasa_ctx_dense_reads", "kasa_ctx_replay_stats", "kasa_ctx_group_second_chance", "kasa_ctx_record_placement",
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
@@ -372,6 +373,11 @@ class DeviceBuffer:
             self.close()
         except Exception:
             pass
+
+
+def device_copy(dst_device: int, dst_ptr: int, src_device: int, src_ptr: int, nbytes: int):
+    """Device memory to device memory, on one device or between two, without peer access (kasa_device_copy)."""
+    _check(lib().kasa_device_copy(C.c_int(int(dst_device)), C.c_void_p(int(dst_ptr)), C.c_int(int(src_device)), C.c_void_p(int(src_ptr)), C.c_size_t(int(nbytes))))
 
 
 def device_memory(device: int = 0):
@@ -812,6 +818,20 @@ class Context:
         """depth bytes of the k-mers at `ptr` whose 30-bit prefix is in [first, end), against THIS context's index and -k."""
         _check(lib().kasa_batch_match_depth_device(self.h, C.c_uint64(int(first)), C.c_uint64(int(end)), C.c_void_p(ptr), C.c_uint64(int(n)), C.c_void_p(depth_ptr)))
 
+    # ---- the depth step in two halves, for partitions on other devices than the owner's: no kernel touches another
+    # device's memory, the k-mers and the depth bytes are copied (kasa_hip.h)
+    def match_depth_stage(self, first: int, end: int, ptr: int, n: int) -> int:
+        """On a partition's context: the k-mers at `ptr` (any device) are copied here and looked up for the prefixes
+        [first, end); returns the device pointer of this context's own n depth bytes (zero where it gave no depth)."""
+        dp = C.c_void_p(0)
+        _check(lib().kasa_batch_match_depth_stage(self.h, C.c_uint64(int(first)), C.c_uint64(int(end)), C.c_void_p(ptr), C.c_uint64(int(n)), C.byref(dp)))
+        return int(dp.value or 0)
+
+    def coherence_fold(self, depth_ptr: int, n: int):
+        """On the owner, between coherence_begin and coherence_finish: a partition's depth bytes (any device) are copied here
+        and folded into the batch's by a bytewise maximum."""
+        _check(lib().kasa_batch_coherence_fold(self.h, C.c_void_p(depth_ptr), C.c_uint64(int(n))))
+
     def coherence_finish(self) -> np.ndarray:
         """The walk over the depth bytes: float32[n_reads].  Raises where the reference throws, as coherence() does."""
         sc = np.zeros(self.n_reads, dtype=np.float32)
@@ -832,7 +852,8 @@ class Context:
         _check(lib().kasa_profile_reset(self.h))
 
     def profile_absorb(self, other: "Context"):
-        """self += other, other = 0 (kasa_profile_absorb): the tables of a context that grouped slices for this one."""
+        """self += other, other = 0 (kasa_profile_absorb): the tables of a context that grouped slices for this one, or of
+        another owner of the same file's batches; the two may sit on different devices (the tables are copied, then added)."""
         _check(lib().kasa_profile_absorb(self.h, other.h))
 
     def profile(self):

@@ -657,6 +657,9 @@ struct kasa_ctx {
     uint64_t lastStaged = 0, lastKeys = 0, lastContrib = 0;   // of the last batch: staging records, profile keys, (event, taxon) contributions
     DevBuf rawOff;                             // the caller's sequence offsets as uploaded
     DevBuf cohLen, cohState;                   // kasa_batch_coherence: match length of every emitted k-mer; walk state per chunk of reads + scores
+    DevBuf cohKmIn, cohPart;                   // a partition context's own copy of the owner's emitted k-mers, and the depth bytes it makes of them (kasa_batch_match_depth_stage)
+    DevBuf cohIn;                              // the owner's copy of a partition's depth bytes, before they are folded into cohLen (kasa_batch_coherence_fold)
+    DevBuf absorbIn;                           // kasa_profile_absorb: the five tables of the other context, brought to this device
     uint64_t nEmitted = 0; bool uniqueDone = false, readsUploaded = false;   // k-mers the encoder emitted (nQ shrinks with -e); -e was applied to this batch
     // every device buffer of the context: what kasa_ctx_destroy releases and kasa_ctx_device_bytes adds up (ONE list)
     std::vector<DevBuf *> buffers()
@@ -667,9 +670,29 @@ struct kasa_ctx {
                 &outScore, &cntUnique, &cntTotal, &cntAllHi, &cntAllLo, &rawOff, &cohLen, &cohState, &sortBig, &rankDen, &rankClass, &rankMeta, &rankOut,
                 &rankList, &rankScratch, &scanTmp, &taxText, &taxTextOff, &taxTextIds, &txtNames, &txtNameOff, &txtLen, &txtBest, &txtBytes, &txtOff, &txtOut,
                 &txtFlags, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
-                &esrChainScore, &esrBig};
+                &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn};
     }
 };
+
+// No kernel of a context is handed memory of another device (include/kasa_hip.h, "the same exchange without the host"):
+// what a caller's pointer names is copied to or from a buffer of the context's own device, and an entry point whose
+// kernels work in the caller's buffer itself refuses a buffer that lies elsewhere.  Peer access is never enabled.
+// The device a pointer lies on, or -1 when this runtime does not know it (page-locked or plain host memory, the allocation
+// of another runtime in the process): such a pointer is taken as before.
+static int pointer_device(const void *p)
+{
+    if (!p) return -1;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return a.type == hipMemoryTypeDevice ? a.device : -1;
+}
+static int refuse_foreign(const kasa_ctx *c, const void *p, const char *who, const char *what)
+{
+    const int d = pointer_device(p);
+    if (d >= 0 && d != c->ix->device)
+        return fail(KASA_E_ARG, "%s: %s lies on device %d, the context works on device %d (copy it there first: its kernels touch no other device's memory)", who, what, d, c->ix->device);
+    return KASA_OK;
+}
 
 // The seams kasa_batch_coherence_begin has open in this process: k-mer buffer -> number of k-mers.  kasa_batch_match_depth_device
 // runs on ANOTHER context than the one that owns the buffer; this is how it recognises a wrong `n` for a buffer of ours.
@@ -949,6 +972,10 @@ extern "C" int kasa_batch_upload(kasa_ctx *c, const uint8_t *bases, const int64_
 
 extern "C" int kasa_batch_upload_device(kasa_ctx *c, const uint8_t *basesDev, const int64_t *offsetsDev, int64_t nReads)
 {
+    if (c && nReads > 0) {                                               // the bases are read in place
+        int rc;
+        if ((rc = refuse_foreign(c, basesDev, "kasa_batch_upload_device", "basesDev")) || (rc = refuse_foreign(c, offsetsDev, "kasa_batch_upload_device", "offsetsDev"))) return rc;
+    }
     KASA_GUARDED(upload_impl(c, basesDev, offsetsDev, nReads, nullptr, nReads, true))
 }
 
@@ -6659,6 +6686,7 @@ extern "C" int kasa_batch_group(kasa_ctx *c, int coverage)
 extern "C" int kasa_batch_group_to(kasa_ctx *c, int coverage, uint32_t *recordsOut)
 {
     if (!c || !recordsOut) return fail(KASA_E_ARG, "kasa_batch_group_to: NULL argument");
+    if (int rc = refuse_foreign(c, recordsOut, "kasa_batch_group_to", "recordsOutDev")) return rc;   // group_kernel stores into it
     return group_stage(c, coverage, true, recordsOut);
 }
 
@@ -6969,6 +6997,7 @@ extern "C" int kasa_batch_records_pack_size(kasa_ctx *c, const uint32_t *records
 {
     if (!c || !nBytes || (nQueries && !recordsDev)) return fail(KASA_E_ARG, "kasa_batch_records_pack_size: NULL argument");
     if (nQueries >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_records_pack_size: a slice holds fewer than 2^32 queries");
+    if (int rc = refuse_foreign(c, recordsDev, "kasa_batch_records_pack_size", "recordsDev")) return rc;
     HIPCHK(hipSetDevice(c->ix->device));
     uint64_t words = 0;
     int rc = wire_offsets<true>(c, recordsDev, nullptr, nQueries, &words);
@@ -6984,6 +7013,7 @@ extern "C" int kasa_batch_records_pack(kasa_ctx *c, const uint32_t *recordsDev, 
     if (c->wireQueries != nQueries || c->wireRecords != recordsDev) return fail(KASA_E_STATE, "kasa_batch_records_pack: call kasa_batch_records_pack_size for these records first");
     if (wire_class_bytes(nQueries) + c->wireWords * 4 > capBytes) return fail(KASA_E_ARG, "kasa_batch_records_pack: the buffer is too small");
     if (nQueries == 0) return KASA_OK;
+    if (int rc = refuse_foreign(c, outDev, "kasa_batch_records_pack", "outDev")) return rc;       // (recordsDev: checked by _pack_size)
     HIPCHK(hipSetDevice(c->ix->device));
     const uint64_t nBlocks = (nQueries + WIRE_BLOCK - 1) / WIRE_BLOCK;
     uint8_t *classes = static_cast<uint8_t *>(outDev);
@@ -7003,6 +7033,10 @@ extern "C" int kasa_batch_records_unpack(kasa_ctx *c, const void *packedDev, uin
     if (!c || (nQueries && (!packedDev || !recordsOutDev))) return fail(KASA_E_ARG, "kasa_batch_records_unpack: NULL argument");
     if (nQueries == 0) return KASA_OK;
     if (nBytes < wire_class_bytes(nQueries)) return fail(KASA_E_ARG, "kasa_batch_records_unpack: %llu bytes cannot hold the classes of %llu queries", (unsigned long long)nBytes, (unsigned long long)nQueries);
+    {                                                                    // the kernels read the one and write the other in place
+        int rc;
+        if ((rc = refuse_foreign(c, packedDev, "kasa_batch_records_unpack", "packedDev")) || (rc = refuse_foreign(c, recordsOutDev, "kasa_batch_records_unpack", "recordsOutDev"))) return rc;
+    }
     HIPCHK(hipSetDevice(c->ix->device));
     const uint8_t *classes = static_cast<const uint8_t *>(packedDev);
     const uint32_t *words = reinterpret_cast<const uint32_t *>(classes + wire_class_bytes(nQueries));
@@ -7055,8 +7089,16 @@ extern "C" int kasa_batch_records_import_device(kasa_ctx *c, uint32_t nParts, co
         if (n) {
             if (!records[j]) return fail(KASA_E_ARG, "kasa_batch_records_import_device: part %u has no records pointer", j);
             uint4 *out = c->recIn.as<uint4>() + start * (RW / 4);
-            if (RW == 8) shift_records_kernel<8><<<blocks_for(n, 256), 256, 0, c->stream>>>(reinterpret_cast<const uint4 *>(records[j]), (uint32_t)n, (uint32_t)start, (uint32_t)(base - 1), out);
-            else shift_records_kernel<16><<<blocks_for(n, 256), 256, 0, c->stream>>>(reinterpret_cast<const uint4 *>(records[j]), (uint32_t)n, (uint32_t)start, (uint32_t)(base - 1), out);
+            // records that are not in their place of the inbox yet are COPIED there (from this device or any other), then all
+            // are shifted in place: the kernel reads this context's own buffer only
+            if ((const void *)records[j] != (const void *)out) {
+                const char *r0 = reinterpret_cast<const char *>(records[j]), *b0 = c->recIn.as<char>();
+                if (r0 + nRecordWords[j] * 4 > b0 && r0 < b0 + totalRec * 4)
+                    return fail(KASA_E_ARG, "kasa_batch_records_import_device: part %u lies in the inbox but not at its place (the parts go there back to back, in partition order)", j);
+                HIPCHK(hipMemcpyAsync(out, records[j], nRecordWords[j] * 4, hipMemcpyDefault, c->stream));
+            }
+            if (RW == 8) shift_records_kernel<8><<<blocks_for(n, 256), 256, 0, c->stream>>>(out, (uint32_t)n, (uint32_t)start, (uint32_t)(base - 1), out);
+            else shift_records_kernel<16><<<blocks_for(n, 256), 256, 0, c->stream>>>(out, (uint32_t)n, (uint32_t)start, (uint32_t)(base - 1), out);
             HIPCHK(hipGetLastError());
         }
         if (nPoolWords[j] > 1) {
@@ -7943,21 +7985,91 @@ extern "C" int kasa_batch_coherence_begin(kasa_ctx *c, const void **kmersDev, ui
     return KASA_OK;
 }
 
-extern "C" int kasa_batch_match_depth_device(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev)
+// The depth step of a partition context never hands the owner's memory to its kernel (the owner may sit on another device):
+// the n k-mers are copied into the context's own cohKmIn, the depth bytes it starts from -- the caller's (depthInit), or
+// zeros -- into its own cohPart, and coh_depth_kernel runs over those two.  Copies cross devices without peer access.
+static int coh_depth_staged(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, const uint8_t *depthInit, const char *who)
 {
-    if (!p || (n && (!kmersDev || !depthDev))) return fail(KASA_E_ARG, "kasa_batch_match_depth_device: NULL argument");
     if (firstPrefix > endPrefix || endPrefix > (1ull << (5 * RANGE_LETTERS)))
-        return fail(KASA_E_ARG, "kasa_batch_match_depth_device: [%llu, %llu) is not a range of 30-bit prefixes", (unsigned long long)firstPrefix, (unsigned long long)endPrefix);
+        return fail(KASA_E_ARG, "%s: [%llu, %llu) is not a range of 30-bit prefixes", who, (unsigned long long)firstPrefix, (unsigned long long)endPrefix);
     {
         std::lock_guard<std::mutex> lk(g_cohMu);
         auto it = g_cohSeams.find(kmersDev);
         if (it != g_cohSeams.end() && it->second != n)
-            return fail(KASA_E_ARG, "kasa_batch_match_depth_device: n = %llu, the batch these k-mers belong to has %llu", (unsigned long long)n, (unsigned long long)it->second);
+            return fail(KASA_E_ARG, "%s: n = %llu, the batch these k-mers belong to has %llu", who, (unsigned long long)n, (unsigned long long)it->second);
     }
     HIPCHK(hipSetDevice(p->ix->device));
     int rc;
-    if ((rc = coh_depth(p, firstPrefix, endPrefix, kmersDev, n, depthDev))) return rc;
+    if ((rc = p->cohKmIn.reserve(n * p->keyBytes() + 64)) || (rc = p->cohPart.reserve(n + 64))) return rc;
+    if (n == 0) return KASA_OK;
+    if (depthInit) HIPCHK(hipMemcpyAsync(p->cohPart.p, depthInit, n, hipMemcpyDefault, p->stream));
+    else HIPCHK(hipMemsetAsync(p->cohPart.p, 0, n, p->stream));
+    if (firstPrefix == endPrefix) return KASA_OK;                        // (no k-mer is in an empty range: nothing to bring over)
+    HIPCHK(hipMemcpyAsync(p->cohKmIn.p, kmersDev, n * p->keyBytes(), hipMemcpyDefault, p->stream));
+    return coh_depth(p, firstPrefix, endPrefix, p->cohKmIn.p, n, p->cohPart.as<uint8_t>());
+}
+
+extern "C" int kasa_batch_match_depth_device(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, uint8_t *depthDev)
+{
+    if (!p || (n && (!kmersDev || !depthDev))) return fail(KASA_E_ARG, "kasa_batch_match_depth_device: NULL argument");
+    // the caller's bytes come over, the kernel writes those of this range among them, and they go back: the bytes of other
+    // prefixes return as they came
+    int rc;
+    if ((rc = coh_depth_staged(p, firstPrefix, endPrefix, kmersDev, n, depthDev, "kasa_batch_match_depth_device"))) return rc;
+    if (n && firstPrefix != endPrefix) HIPCHK(hipMemcpyAsync(depthDev, p->cohPart.p, n, hipMemcpyDefault, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_match_depth_stage(kasa_ctx *p, uint64_t firstPrefix, uint64_t endPrefix, const void *kmersDev, uint64_t n, const uint8_t **depthDev)
+{
+    if (!p || !depthDev || (n && !kmersDev)) return fail(KASA_E_ARG, "kasa_batch_match_depth_stage: NULL argument");
+    *depthDev = nullptr;
+    int rc;
+    if ((rc = coh_depth_staged(p, firstPrefix, endPrefix, kmersDev, n, nullptr, "kasa_batch_match_depth_stage"))) return rc;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    *depthDev = p->cohPart.as<uint8_t>();
+    return KASA_OK;
+}
+
+// dst[i] = max(dst[i], src[i]) byte by byte, 16 bytes per thread (the bytes behind the last whole 16 one by one): a k-mer has
+// a depth in at most one partition, so the maximum over the partitions' bytes is what single-byte
+// stores into one buffer gave.  No LDS, no scratch: two loads, sixteen byte maxima, one store.
+static constexpr uint32_t COH_FOLD_BYTES = 16;
+__device__ __forceinline__ uint32_t max_bytes(uint32_t a, uint32_t b)
+{
+    uint32_t r = 0;
+#pragma unroll
+    for (int s = 0; s < 32; s += 8) { const uint32_t x = (a >> s) & 255u, y = (b >> s) & 255u; r |= (x > y ? x : y) << s; }
+    return r;
+}
+__global__ void coh_fold_kernel(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n)
+{
+    const uint64_t o = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * COH_FOLD_BYTES;
+    if (o >= n) return;
+    if (o + COH_FOLD_BYTES <= n) {
+        uint4 d = *reinterpret_cast<const uint4 *>(dst + o);
+        const uint4 v = *reinterpret_cast<const uint4 *>(src + o);
+        d.x = max_bytes(d.x, v.x); d.y = max_bytes(d.y, v.y); d.z = max_bytes(d.z, v.z); d.w = max_bytes(d.w, v.w);
+        *reinterpret_cast<uint4 *>(dst + o) = d;
+    } else {
+        for (uint64_t i = o; i < n; ++i) { const uint8_t x = dst[i], y = src[i]; dst[i] = x > y ? x : y; }
+    }
+}
+
+extern "C" int kasa_batch_coherence_fold(kasa_ctx *c, const uint8_t *depthDev, uint64_t n)
+{
+    if (!c || (n && !depthDev)) return fail(KASA_E_ARG, "kasa_batch_coherence_fold: NULL argument");
+    if (!c->cohBegun || c->state < 3) return fail(KASA_E_STATE, "kasa_batch_coherence_fold: no kasa_batch_coherence_begin on this batch");
+    if (n != c->nEmitted) return fail(KASA_E_ARG, "kasa_batch_coherence_fold: n = %llu, the batch has %llu k-mers", (unsigned long long)n, (unsigned long long)c->nEmitted);
+    HIPCHK(hipSetDevice(c->ix->device));
+    if (n == 0 || c->nSeq == 0) return KASA_OK;
+    int rc;
+    if ((rc = c->cohIn.reserve(n + 64))) return rc;
+    HIPCHK(hipMemcpyAsync(c->cohIn.p, depthDev, n, hipMemcpyDefault, c->stream));
+    coh_fold_kernel<<<blocks_for(n, 256 * COH_FOLD_BYTES), 256, 0, c->stream>>>(c->cohLen.as<uint8_t>(), c->cohIn.as<uint8_t>(), n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
     return KASA_OK;
 }
 
@@ -8010,6 +8122,16 @@ extern "C" int kasa_device_write(int device, void *dst, const void *src, size_t 
     if (bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     return KASA_OK;
 }
+// Device memory to device memory, on one device or between two, without peer access (the runtime stages what the devices
+// cannot hand over directly); returns when the bytes are there.  Not a context call: threads may copy into disjoint
+// places of one buffer at the same time (the partitions' records into the owner's inbox).
+extern "C" int kasa_device_copy(int dstDevice, void *dst, int srcDevice, const void *src, size_t bytes)
+{
+    if (bytes && (!dst || !src)) return fail(KASA_E_ARG, "kasa_device_copy: NULL argument");
+    HIPCHK(hipSetDevice(dstDevice));
+    if (bytes) HIPCHK(hipMemcpyPeer(dst, dstDevice, src, srcDevice, bytes));
+    return KASA_OK;
+}
 extern "C" int kasa_thread_device(int device)
 {
     HIPCHK(hipSetDevice(device));
@@ -8060,20 +8182,29 @@ __global__ void tables_absorb_kernel(uint64_t *__restrict__ dst, uint64_t *__res
 }
 
 // dst += src, src = 0: the tables of a context that only grouped (a partition worker: the profile is made where the
-// queries are grouped) go to the context that owns the file's profile.  Same device, same k range, same index content.
+// queries are grouped) go to the context that owns the file's profile -- on the same device or on another one.  ONE path:
+// src's five tables are copied into a buffer of dst's device, src's are cleared on src's stream, and the kernel adds the
+// copies on dst's stream.  Integer limbs: the sums do not depend on where or in which order they are made.
 extern "C" int kasa_profile_absorb(kasa_ctx *dst, kasa_ctx *src)
 {
     if (!dst || !src) return fail(KASA_E_ARG, "kasa_profile_absorb: NULL argument");
     if (dst == src) return KASA_OK;
-    if (dst->device != src->device || dst->nK != src->nK || dst->kHigh != src->kHigh || dst->ix->nTaxa != src->ix->nTaxa)
-        return fail(KASA_E_ARG, "kasa_profile_absorb: the contexts differ in device, k range or number of taxa");
-    HIPCHK(hipSetDevice(dst->device));
-    HIPCHK(hipStreamSynchronize(src->stream));
+    if (dst->nK != src->nK || dst->kHigh != src->kHigh || dst->ix->nTaxa != src->ix->nTaxa)
+        return fail(KASA_E_ARG, "kasa_profile_absorb: the contexts differ in k range or number of taxa");
     const size_t cells = (size_t)dst->nK * dst->ix->nTaxa;
     DevBuf *d[5] = {&dst->cntUnique, &dst->cntTotal, &dst->cntAllHi, &dst->cntAllMid, &dst->cntAllLo};
     DevBuf *q[5] = {&src->cntUnique, &src->cntTotal, &src->cntAllHi, &src->cntAllMid, &src->cntAllLo};
+    HIPCHK(hipSetDevice(dst->ix->device));
+    int rc;
+    if ((rc = dst->absorbIn.reserve(5 * cells * 8))) return rc;
+    HIPCHK(hipSetDevice(src->ix->device));
+    HIPCHK(hipStreamSynchronize(src->stream));                           // src's tables are complete
+    for (int k = 0; k < 5; ++k) HIPCHK(hipMemcpyAsync(dst->absorbIn.as<uint64_t>() + (size_t)k * cells, q[k]->p, cells * 8, hipMemcpyDefault, src->stream));
+    for (int k = 0; k < 5; ++k) HIPCHK(hipMemsetAsync(q[k]->p, 0, cells * 8, src->stream));
+    HIPCHK(hipStreamSynchronize(src->stream));                           // the copies have arrived
+    HIPCHK(hipSetDevice(dst->ix->device));
     for (int k = 0; k < 5; ++k)
-        tables_absorb_kernel<<<blocks_for(cells, 256), 256, 0, dst->stream>>>(d[k]->as<uint64_t>(), q[k]->as<uint64_t>(), cells);
+        tables_absorb_kernel<<<blocks_for(cells, 256), 256, 0, dst->stream>>>(d[k]->as<uint64_t>(), dst->absorbIn.as<uint64_t>() + (size_t)k * cells, cells);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(dst->stream));
     return KASA_OK;

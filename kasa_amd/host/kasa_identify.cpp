@@ -7,7 +7,7 @@
 // file is host logic: argument parsing, file formats, FASTA/FASTQ reading, ranking, text.
 //
 // Modes: build (main.cpp:628-686, the index files made on the device: kasa_build_*), update, delete, shrink and getFrequency
-// (main.cpp:699-875, 1336-1362: an existing index edited on the device), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs
+// (main.cpp:699-875, 1336-1362: an existing index edited on the device), identify and identify_multiple (main.cpp:979-1334); --devices a,b,... shards the batches of a file over several GPUs, --partition-devices a,b,... spreads a range-partitioned index over them
 // (index replicated, one RCCL all-reduce of the profile tables).  Input is streamed in chunks, batches are cut where the
 // reference cuts them (-m) and parsed / computed / written in a pipeline.
 // Not supported here (reported as errors, never silently ignored): --visualize; --coherence together with -e, with paired-end input or over sequences
@@ -631,6 +631,10 @@ struct Params {
     string content, index, input, input2, rtt, profile;   // input2: second file of paired-end input (-1 / -2)
     int kHigh = 12, kLow = 7, beasts = 3, frames = 3, K = 12;   // K: letters per index k-mer (25 for a 128-bit index)
     vector<int> devices{0};                      // --device d / --devices a,b,...: read shards go to the devices in turn (index replicated)
+    // --partition-devices a,b,...: device SLOTS (a device may be named more than once; every slot counts as a device of its
+    // own).  The index is cut into range partitions, contiguous runs of them live on the slots -- each partition ONCE -- and
+    // every slot also owns batches of reads as a --devices worker does.  `devices` is this list then.
+    bool partitionDevices = false, devicesGiven = false;
     bool kSetByUser = false;
     string codonFile, codonId;                   // -a/--alphabet <gc.prt> <id>
     bool filter = false; string filterClean, filterCont; float errorThreshold = 0.5f;   // --filter <clean> <contaminants>, --errorThreshold
@@ -660,9 +664,16 @@ struct IndexFiles {                               // what Compare::ReadIndex loa
     // streams an index of any size from disk (Compare.hpp:286-318).  onDevice[d] = parts[d][0] then.
     vector<vector<kasa_index *>> parts;
     vector<uint64_t> cuts;
+    // --partition-devices: the partitions spread over the device slots instead, every one created once: spread[j] on the
+    // device spreadDev[j] of slot j * nSlots / nParts (contiguous runs: a slot holds about nRec / nSlots records).
+    // onDevice[d] = the first partition of slot d (an owner's context needs an index of its own device for its key width).
+    vector<kasa_index *> spread;
+    vector<int> spreadDev;
+    size_t nPartitions() const { return spread.empty() ? (parts.empty() ? 0 : parts[0].size()) : spread.size(); }
     ~IndexFiles()
     {
-        if (parts.empty()) { for (auto *ix : onDevice) kasa_index_destroy(ix); }
+        if (!spread.empty()) { for (auto *ix : spread) kasa_index_destroy(ix); }
+        else if (parts.empty()) { for (auto *ix : onDevice) kasa_index_destroy(ix); }
         else for (auto &v : parts) for (auto *ix : v) kasa_index_destroy(ix);
     }
 };
@@ -1486,7 +1497,22 @@ struct WorkerBuffers {
     ~WorkerBuffers() { for (auto &f : written) if (f.valid()) f.wait(); }      // the writer still reads the buffers
 };
 
-static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, const vector<kasa_ctx *> &partCtx, Batch &b, bool wantRows, double &tDevice, double &tText, WorkerBuffers &wb, OrderedOut &out)
+// A step that every partition's context takes for one batch, all partitions at once: one host thread per partition (the ABI
+// calls return with their stream idle, so host threads are what overlaps the devices).  The first statement of a thread
+// binds it to its partition's device; kasa_last_error is per thread, so a failure's message is taken there.
+static void overPartitions(const IndexFiles &ixf, size_t nP, const std::function<int(size_t)> &step)
+{
+    vector<string> msgs(nP); vector<int> rcs(nP, 0);
+    vector<std::thread> pool;
+    for (size_t j = 0; j < nP; ++j)
+        pool.emplace_back([&, j] {
+            if ((rcs[j] = kasa_thread_device(ixf.spreadDev[j])) || (rcs[j] = step(j))) msgs[j] = kasa_last_error();
+        });
+    for (auto &t : pool) t.join();
+    for (size_t j = 0; j < nP; ++j) if (rcs[j]) throw std::runtime_error(msgs[j]);
+}
+
+static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int ownerDev, const vector<kasa_ctx *> &partCtx, Batch &b, bool wantRows, double &tDevice, double &tText, WorkerBuffers &wb, OrderedOut &out)
 {
     const auto tDev = std::chrono::steady_clock::now();
     auto secondsSince = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -1514,7 +1540,26 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, cons
             if (kasa_batch_slice_starts(ctx, ixf.cuts.data(), (uint32_t)nP, starts.data())) throwLast();
             const size_t keyBytes = p.K > 12 ? 16 : 8;
             vector<const uint32_t *> recs(nP), pools(nP); vector<uint64_t> nRecW(nP), nPoolW(nP);
-            for (size_t j = 0; j < nP; ++j) {
+            if (!ixf.spread.empty()) {
+                // --partition-devices: the partitions' contexts sit on their own devices.  Every slice is grouped there by a
+                // thread of its own, and its records come back by a device-to-device copy into their place of this batch's
+                // inbox (whole records: the packed wire format waits for a measurement on several devices);
+                // the pools are copied by the import.  Then, in partition order, the profiles and the records are taken in.
+                const size_t RW = (p.kHigh - p.kLow + 1) <= 8 ? 8 : 16;   // 32-bit words per record (kasa_hip.h: kasa_batch_group)
+                uint32_t *inbox = nullptr;
+                if (kasa_batch_records_inbox(ctx, nq * RW, &inbox)) throwLast();
+                overPartitions(ixf, nP, [&](size_t j) -> int {
+                    int rc;
+                    if ((rc = kasa_batch_set_sorted_device(partCtx[j], (const char *)km + starts[j] * keyBytes, starts[j + 1] - starts[j]))) return rc;
+                    if ((rc = kasa_batch_group(partCtx[j], p.coverage))) return rc;
+                    if ((rc = kasa_batch_records_device(partCtx[j], &recs[j], &nRecW[j], &pools[j], &nPoolW[j]))) return rc;
+                    uint32_t *place = inbox + starts[j] * RW;
+                    if ((rc = kasa_device_copy(ownerDev, place, ixf.spreadDev[j], recs[j], (size_t)nRecW[j] * 4))) return rc;
+                    recs[j] = place;
+                    return 0;
+                });
+                for (size_t j = 0; j < nP; ++j) if (kasa_profile_absorb(ctx, partCtx[j])) throwLast();
+            } else for (size_t j = 0; j < nP; ++j) {
                 if (kasa_batch_set_sorted_device(partCtx[j], (const char *)km + starts[j] * keyBytes, starts[j + 1] - starts[j])) throwLast();
                 if (kasa_batch_group(partCtx[j], p.coverage)) throwLast();
                 if (kasa_profile_absorb(ctx, partCtx[j])) throwLast();
@@ -1540,6 +1585,15 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, cons
             { ScopedTimerMt t2(g_ht.cohBegin, g_ht.mu); if (kasa_batch_coherence_begin(ctx, &km, &ne, &depth)) throwLast(); }
             {
                 ScopedTimerMt t2(g_ht.cohDepth, g_ht.mu);
+                if (!ixf.spread.empty()) {
+                    // --partition-devices: every partition makes the depth bytes of its prefix range on its own device (all
+                    // at once), then they are folded into the batch's, one partition after the other
+                    vector<const uint8_t *> theirs(nP, nullptr);
+                    overPartitions(ixf, nP, [&](size_t j) -> int {
+                        return kasa_batch_match_depth_stage(partCtx[j], ixf.cuts[j], j + 1 < nP ? ixf.cuts[j + 1] : (uint64_t)1 << 30, km, ne, &theirs[j]);
+                    });
+                    for (size_t j = 0; j < nP; ++j) if (kasa_batch_coherence_fold(ctx, theirs[j], ne)) throwLast();
+                } else
                 for (size_t j = 0; j < nP; ++j)
                     if (kasa_batch_match_depth_device(partCtx[j], ixf.cuts[j], j + 1 < nP ? ixf.cuts[j + 1] : (uint64_t)1 << 30, km, ne, depth)) throwLast();
             }
@@ -1695,7 +1749,15 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         if (kasa_ctx_create(ixf.onDevice[(size_t)devSlots[d]], p.kHigh, p.kLow, p.frames, ixf.lut.empty() ? nullptr : ixf.lut.data(), &ctx[d])) throwLast();
     vector<vector<kasa_ctx *>> partCtx(nDev);                          // a partitioned index: one context per partition and device
     struct PartGuard { vector<vector<kasa_ctx *>> &c; ~PartGuard() { for (auto &v : c) for (auto *x : v) kasa_ctx_destroy(x); } } partGuard{partCtx};
-    if (!ixf.parts.empty())
+    if (!ixf.spread.empty()) {
+        // --partition-devices: owner d has one context per partition, made on THAT partition's device and bound to its index
+        for (size_t d = 0; d < nDev; ++d)
+            for (kasa_index *ix : ixf.spread) {
+                kasa_ctx *c = nullptr;
+                if (kasa_ctx_create(ix, p.kHigh, p.kLow, p.frames, ixf.lut.empty() ? nullptr : ixf.lut.data(), &c)) throwLast();
+                partCtx[d].push_back(c);
+            }
+    } else if (!ixf.parts.empty())
         for (size_t d = 0; d < nDev; ++d)
             for (kasa_index *ix : ixf.parts[(size_t)devSlots[d]]) {
                 kasa_ctx *c = nullptr;
@@ -1709,6 +1771,23 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         if (kasa_device_memory(p.devices[(size_t)devSlots[0]], &freeB, &totalB)) throwLast();
         const uint64_t per = kasa_batch_bytes_per_query(ctx[0]);
         if (per) maxKmersPerBatch = std::max<uint64_t>(1u << 20, std::min<uint64_t>(maxKmersPerBatch, (uint64_t)(0.8 * (double)freeB) / per));
+        if (per && !ixf.spread.empty()) {
+            // --partition-devices: the smallest device decides.  On device D every owner slot there holds a batch (`per` bytes
+            // a query) and its inbox (a record a query); and every owner of the run -- on D or not -- has its contexts for D's
+            // partitions there, whose slices of one batch add up to at most that batch (`per` again: a slice needs less).
+            // Free memory is read now, with the index parts loaded.  Buffers only grow: a run whose batches lean on one
+            // partition after the other can need more, and then fails with the library's out-of-memory message.
+            const uint64_t recBytes = (p.kHigh - p.kLow + 1) <= 8 ? 32 : 64;
+            std::map<int, uint64_t> slotsOn;
+            for (int dev : p.devices) ++slotsOn[dev];
+            uint64_t fit = 3000000000ull;
+            for (const auto &kv : slotsOn) {
+                if (kasa_device_memory(kv.first, &freeB, &totalB)) throwLast();
+                const uint64_t bytesPerQuery = kv.second * (per + recBytes) + (uint64_t)p.devices.size() * per;
+                fit = std::min<uint64_t>(fit, (uint64_t)(0.8 * (double)freeB) / bytesPerQuery);
+            }
+            maxKmersPerBatch = std::max<uint64_t>(1u << 20, fit);
+        }
         if (const char *e = getenv("KASA_MAX_BATCH_KMERS")) maxKmersPerBatch = std::max<uint64_t>(1, (uint64_t)atoll(e));   // tests: force several batches
     }
     mark("contexts made");
@@ -1757,6 +1836,10 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     vector<double> tDevice(nDev, 0.0), tText(nDev, 0.0);
     std::atomic<uint64_t> totalKmers{0};
     SplitCarry carry;
+    // --partition-devices: of the owners that wait for a batch, the one that has had the fewest takes the next (every slot
+    // holds a part of the index, so every slot should also carry its share of the reads; `taken` is printed with -v)
+    const bool fair = !ixf.spread.empty();
+    vector<uint64_t> taken(nDev, 0); vector<char> idle(nDev, 0);
     auto worker = [&](size_t d) {
         WorkerBuffers &wb = wbs[d];
         try {
@@ -1764,13 +1847,18 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                 std::unique_ptr<Batch> b;
                 {
                     std::unique_lock<std::mutex> lk(mu);
-                    cvWork.wait(lk, [&] { return !todo.empty() || noMore || failure; });
-                    if (failure || todo.empty()) return;
+                    idle[d] = 1;
+                    auto myTurn = [&] { if (fair) for (size_t e = 0; e < nDev; ++e) if (e != d && idle[e] && taken[e] < taken[d]) return false; return true; };
+                    cvWork.wait(lk, [&] { return (!todo.empty() && myTurn()) || (todo.empty() && noMore) || failure; });
+                    idle[d] = 0;
+                    if (failure || todo.empty()) { cvWork.notify_all(); return; }
                     b = std::move(todo.front()); todo.pop_front();
+                    ++taken[d];
                     cvSpace.notify_all();
+                    if (fair) cvWork.notify_all();
                 }
                 mark("device takes batch", b->id);
-                runBatch(p, ixf, ctx[d], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out);
+                runBatch(p, ixf, ctx[d], p.devices[(size_t)devSlots[d]], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out);
                 mark("device done with batch", b->id);
                 totalKmers += b->kmers;
                 b->rs = ReadSet();                                   // the reads are done with
@@ -1821,7 +1909,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                 cvSpace.wait(lk, [&] { return todo.size() < nDev || failure; });
                 if (failure) break;
                 todo.push_back(std::move(b));
-                cvWork.notify_one();
+                if (fair) cvWork.notify_all(); else cvWork.notify_one();
             }
             drain(false);
         }
@@ -1838,7 +1926,12 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     if (!p.rtt.empty()) { out.drainWriter(); out.stopWriter(); mark("writer drained"); if (p.fmt == Params::Json) out.put("\n]"); ::close(out.fd); out.fd = -1; }
     if (p.filter) filterReads(p, contaminants);
     // profile: one RCCL all-reduce over the devices' tables, then device 0's copy
-    if (nDev > 1 || getenv("KASA_FORCE_ALLREDUCE")) {        // (the variable: tests run the reduce with a single rank)
+    if (!ixf.spread.empty()) {
+        // --partition-devices: no communicator (ncclCommInitAll refuses a device named twice, and integer tables need no
+        // collective inside one process): the owners' tables are added to the first owner's, in the order 1, 2, ...
+        for (size_t d = 1; d < nDev; ++d) if (kasa_profile_absorb(ctx[0], ctx[d])) throwLast();
+        if (p.verbose) { std::cout << "OUT: Batches per owner:"; for (size_t d = 0; d < nDev; ++d) std::cout << " " << taken[d]; std::cout << std::endl; }
+    } else if (nDev > 1 || getenv("KASA_FORCE_ALLREDUCE")) {        // (the variable: tests run the reduce with a single rank)
         vector<ncclComm_t> comms(nDev);
         vector<int> devs;
         for (size_t d = 0; d < nDev; ++d) devs.push_back(p.devices[(size_t)devSlots[d]]);
@@ -1860,7 +1953,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                   << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s" << std::endl;
     if (p.verbose && g_ht.on && p.coherence) {                   // (every call of the step returns with the device idle: host clock = device time + launches)
         std::cout << "OUT: coherence: " << g_ht.coherence << " s";
-        if (!ixf.parts.empty()) std::cout << " (begin " << g_ht.cohBegin << ", depth over the partitions " << g_ht.cohDepth << ", finish " << g_ht.cohFinish << ")";
+        if (ixf.nPartitions()) std::cout << " (begin " << g_ht.cohBegin << ", depth over the partitions " << g_ht.cohDepth << ", finish " << g_ht.cohFinish << ")";
         std::cout << std::endl;
     }
     if (p.verbose && g_ht.on) {
@@ -2714,8 +2807,24 @@ static int run(int argc, char **argv)
         else if (s == "-e" || s == "--unique") p.unique = true;
         else if (s == "--coverage") p.coverage = true;
         else if (s == "-v" || s == "--verbose") p.verbose = true;
-        else if (s == "--device") p.devices = {std::stoi(next())};
+        else if (s == "--device") { p.devices = {std::stoi(next())}; p.devicesGiven = true; }
+        else if (s == "--partition-devices") {                                // the index in range partitions over device slots (a device may come twice)
+            const string v = next();
+            vector<int> slots;
+            size_t at = 0;
+            for (bool more = !v.empty(); more;) {
+                const size_t comma = v.find(',', at);
+                const string tok = v.substr(at, comma == string::npos ? string::npos : comma - at);
+                if (tok.empty() || tok.size() > 6 || tok.find_first_not_of("0123456789") != string::npos) { slots.clear(); break; }
+                slots.push_back(std::stoi(tok));
+                more = comma != string::npos; at = comma + 1;
+            }
+            if (slots.empty()) throw std::runtime_error("--partition-devices needs a list of device slots like 0,1,2,3 (a device may be named more than once), not \"" + v + "\"");
+            p.devices = slots; p.partitionDevices = true;
+        }
         else if (s == "--devices") {                                          // read shards over several GPUs, index replicated
+            p.devicesGiven = true;
+            if (p.partitionDevices) throw std::runtime_error("--partition-devices cannot be combined with --device or --devices: its slots are the devices of the run");
             p.devices.clear();
             std::stringstream ss(next()); string tok;
             while (std::getline(ss, tok, ',')) if (!tok.empty()) p.devices.push_back(std::stoi(tok));
@@ -2738,6 +2847,7 @@ static int run(int argc, char **argv)
             throw std::runtime_error("parameter " + s + " is not supported by the MI355X identify path");
         else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
     }
+    if (p.partitionDevices && p.devicesGiven) throw std::runtime_error("--partition-devices cannot be combined with --device or --devices: its slots are the devices of the run");
     if (frameFlags >= 2) throw std::runtime_error("You'll have to decide between using one, three, or six frames. Currently, more than one option was chosen. Please check your parameters!"); // main.cpp:618-620
     std::ifstream info(p.index + "_info.txt");
     if (!info) throw std::runtime_error("Info file for this index can not be found!");
@@ -2772,7 +2882,8 @@ static int run(int argc, char **argv)
     }
     uint64_t maxPart = 0xFFFFFFF0ull - 1;                               // what one index object holds (kasa_index_create)
     if (const char *e = getenv("KASA_INDEX_PART_RECORDS")) maxPart = std::max<uint64_t>(1, (uint64_t)atoll(e));   // tests: partitions of a small index
-    if (ixf.nRec <= maxPart) {
+    const size_t nSlots = p.partitionDevices ? p.devices.size() : 0;
+    if (ixf.nRec <= maxPart && !p.partitionDevices) {
         for (int dev : p.devices) {
             kasa_index *ix = nullptr;
             if (kasa_index_create(dev, rec, ixf.nRec, ixf.recBytes, ixf.tp.data(), ixf.tc.data(), ixf.tp.size(), ixf.content.taxids.data(),
@@ -2782,7 +2893,7 @@ static int run(int argc, char **argv)
     } else {
         // about equal partitions, as few as hold the index, cut between `_trie` entries
         const uint64_t m = ixf.tp.size();
-        uint64_t nParts = (ixf.nRec + maxPart - 1) / maxPart;
+        uint64_t nParts = std::max<uint64_t>((ixf.nRec + maxPart - 1) / maxPart, nSlots);   // (--partition-devices: at least one per slot)
         vector<uint64_t> tLo, rLo;                                         // first trie entry and first record of every partition, + the ends
         for (;; ++nParts) {
             tLo.assign(1, 0); rLo.assign(1, 0);
@@ -2795,20 +2906,41 @@ static int run(int argc, char **argv)
                 tLo.push_back(t); rLo.push_back(r);
             }
             if (ok) { if (r != ixf.nRec) throw std::runtime_error("the trie file does not add up to the index's records"); break; }
+            if (nParts >= m && nSlots)
+                throw std::runtime_error("--partition-devices: the index (" + std::to_string(ixf.nRec) + " records, " + std::to_string(m) + " trie entries) cannot be cut between its trie entries into at least one partition for each of the "
+                                         + std::to_string(nSlots) + " device slots, of at most " + std::to_string(maxPart) + " records each");
             if (nParts >= m) throw std::runtime_error("the index cannot be cut into partitions of at most " + std::to_string(maxPart) + " records between its trie entries");
         }
-        ixf.parts.resize(p.devices.size());
         for (uint64_t j = 0; j < nParts; ++j) ixf.cuts.push_back(j == 0 ? 0 : (uint64_t)ixf.tp[tLo[j]]);
-        for (size_t d = 0; d < p.devices.size(); ++d) {
+        if (nSlots) {
+            // partition j lives on slot j * nSlots / nParts: contiguous runs, every partition created once
+            ixf.onDevice.assign(nSlots, nullptr);
             for (uint64_t j = 0; j < nParts; ++j) {
+                const size_t slot = (size_t)(j * nSlots / nParts);
                 kasa_index *ix = nullptr;
-                if (kasa_index_create(p.devices[d], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
+                if (kasa_index_create(p.devices[slot], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
                                       tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix)) throwLast();
-                ixf.parts[d].push_back(ix);
+                ixf.spread.push_back(ix); ixf.spreadDev.push_back(p.devices[slot]);
+                if (!ixf.onDevice[slot]) ixf.onDevice[slot] = ix;
             }
-            ixf.onDevice.push_back(ixf.parts[d][0]);
+            if (p.verbose) {
+                std::cout << "OUT: Index of " << ixf.nRec << " records in " << nParts << " partitions over " << nSlots << " device slots (";
+                for (size_t d = 0; d < nSlots; ++d) std::cout << (d ? "," : "") << p.devices[d];
+                std::cout << ")" << std::endl;
+            }
+        } else {
+            ixf.parts.resize(p.devices.size());
+            for (size_t d = 0; d < p.devices.size(); ++d) {
+                for (uint64_t j = 0; j < nParts; ++j) {
+                    kasa_index *ix = nullptr;
+                    if (kasa_index_create(p.devices[d], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
+                                          tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix)) throwLast();
+                    ixf.parts[d].push_back(ix);
+                }
+                ixf.onDevice.push_back(ixf.parts[d][0]);
+            }
+            if (p.verbose) std::cout << "OUT: Index of " << ixf.nRec << " records in " << nParts << " partitions on every device" << std::endl;
         }
-        if (p.verbose) std::cout << "OUT: Index of " << ixf.nRec << " records in " << nParts << " partitions on every device" << std::endl;
     }
     munmap(rec, ixf.nRec * ixf.recBytes); close(fd);
     if (p.threads == 0) {
