@@ -110,7 +110,8 @@ int kasa_batch_upload(kasa_ctx *ctx, const uint8_t *bases, const int64_t *offset
  * parses on the device): `basesDev` AND `offsetsDev` (int64[nReads+1], relative to basesDev) lie in device memory.  Nothing
  * crosses PCIe and the bases are NOT copied: the context reads them in place, so they must stay valid and unchanged until
  * the batch's last call (kasa_batch_coherence re-reads them).  What is left of the upload is the geometry of Read.hpp:36-57,
- * 633-675 on the device (k-mers per read, running sums) and one 8-byte read-back of the batch's k-mer count. */
+ * 633-675 on the device (k-mers per read, running sums) and one 8-byte read-back of the batch's k-mer count.  A host
+ * that parses on the device gets such reads from kasa_parse_append and hands them on with kasa_parse_take (below). */
 int kasa_batch_upload_device(kasa_ctx *ctx, const uint8_t *basesDev, const int64_t *offsetsDev, int64_t nReads);
 
 /* The same for reads made of several sequences: paired-end input (-1/-2; Read::readFastqa_pairedEnd,
@@ -582,6 +583,61 @@ int kasa_build_drop_taxa(kasa_builder *b, const uint32_t *taxIds, uint64_t n);
 int kasa_build_shrink(kasa_builder *b, int strategy, float percentage);
 int kasa_build_edit_stats(kasa_builder *b, uint64_t *stats4);
 int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers);
+
+/* ---- parse: FASTA / FASTQ text -> reads, on the device ------------------------------------------------------------------
+ * The producer of what kasa_batch_upload_device takes: the text of whole records goes in, the reads come out in device
+ * memory -- what Read::readFastqa / readFasta (Read.hpp:699-760) hand on for reads that fit one chunk, byte for byte what the
+ * host driver's parseRecords makes of the same text:
+ *   bases    the sequence lines back to back without their line feeds, untouched (a '\r' stays part of its line; cleaning and
+ *            case folding are the encoder's, Read.hpp:633-675)
+ *   off      [nReads + 1] running offsets into bases
+ *   names    header without its first character plus one space (Read.hpp:711-714), back to back, with nameOff[nReads + 1]
+ *   lengths  letters plus one per sequence line (Read.hpp:723-731); FASTA counts the non-empty sequence lines
+ * A kasa_parser is a POOL of parsed reads on one device, single-threaded like a context.
+ *   kasa_parse_create   longSequence: records of that many letters and more are not taken (the reference reads them in
+ *                       pieces, Read.hpp:371-600; the host driver's KASA_LONG_SEQUENCE, 1000000 by default).
+ *   kasa_parse_append   text: host memory (page-locked memory crosses PCIe fastest), nBytes of WHOLE records: it starts at a
+ *                       header line and only its last line may lack a line feed.  fasta: '>' records, else '@' records of
+ *                       strictly four lines.  The reads go behind those pooled so far: consecutive chunks of a file form one
+ *                       running read set.  *parsable = 0: the chunk is not in the form the device takes -- the pool is left
+ *                       exactly as it was, *nReadsAdded = 0, the call returns KASA_OK, and the caller parses the chunk itself
+ *                       (so every message about malformed input keeps coming from the host parser).  kasa_parse_status names
+ *                       the first offending property (KASA_PARSE_*) and its chunk position: the start of the line that has it
+ *                       (KASA_PARSE_LONG: of the record's header), for KASA_PARSE_BLANK the space or tab itself.
+ *   kasa_parse_sizes    reads, letters and name bytes pooled right now.
+ *   kasa_parse_fetch    reads [first, first + n) of the pool to host memory; any pointer may be NULL; off and nameOff are
+ *                       rebased to `first` (off[0] = nameOff[0] = 0).  One 32-byte read-back for the range's ends, then the copies.
+ *   kasa_parse_take     the first nReads pooled reads become ctx's batch and leave the pool: the context gets its own
+ *                       device-to-device copy of the bases (the pool's memory is reused by the next append, while a batch's
+ *                       bases must stay valid until its last call) and goes on as kasa_batch_upload_device does (geometry on the
+ *                       device, one 8-byte read-back), after one 32-byte read-back of its own for where the reads left behind
+ *                       start.  KASA_E_ARG when the context is on another device than the pool.
+ *   kasa_parse_tile_bytes  bytes of text (and of output) one wavefront owns: tests size their inputs by it.
+ *   kasa_parse_stage_ms  HIP-event milliseconds, summed over the appends: text upload, and the kernels from line table to gather. */
+enum {
+    KASA_PARSE_OK = 0,
+    KASA_PARSE_FASTQ_LINES = 1,     /* the line count of a FASTQ chunk is not a multiple of 4 */
+    KASA_PARSE_FASTQ_HEADER = 2,    /* line 0 of a FASTQ record does not start with '@' */
+    KASA_PARSE_FASTQ_PLUS = 3,      /* line 2 of a FASTQ record does not start with '+' */
+    KASA_PARSE_FASTQ_QUALITY = 4,   /* the quality line differs in length from the sequence line */
+    KASA_PARSE_EMPTY_LINE = 5,      /* an empty line in a FASTQ chunk */
+    KASA_PARSE_BLANK = 6,           /* a space or tab in a sequence line */
+    KASA_PARSE_LONG = 7,            /* a record of longSequence letters or more */
+    KASA_PARSE_FASTA_HEADER = 8,    /* a FASTA chunk that does not start with '>' */
+    KASA_PARSE_FASTQ_SEQ_PLUS = 9,  /* a FASTQ sequence line that starts with '+' (the host parser takes it for the '+' line) */
+    KASA_PARSE_TOO_LARGE = 10       /* a chunk of 4 GiB or more (positions in a chunk are 32-bit) */
+};
+typedef struct kasa_parser kasa_parser;
+int kasa_parse_create(int device, uint64_t longSequence, kasa_parser **out);
+int kasa_parse_append(kasa_parser *p, const char *text, uint64_t nBytes, int fasta, uint64_t *nReadsAdded, int *parsable);
+int kasa_parse_status(kasa_parser *p, int *code, uint64_t *at);
+const char *kasa_parse_status_text(int code);
+int kasa_parse_sizes(kasa_parser *p, uint64_t *nReads, uint64_t *nBases, uint64_t *nNameBytes);
+int kasa_parse_fetch(kasa_parser *p, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases);
+int kasa_parse_take(kasa_parser *p, kasa_ctx *ctx, uint64_t nReads);
+int kasa_parse_tile_bytes(void);
+int kasa_parse_stage_ms(kasa_parser *p, double *uploadMs, double *parseMs);
+void kasa_parse_destroy(kasa_parser *p);
 
 #ifdef __cplusplus
 }

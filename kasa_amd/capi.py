@@ -37,6 +37,8 @@ EXPORTS = [
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
     "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats", "kasa_build_taxa_histogram",
     "kasa_encode_group_reads",
+    "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
+    "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
 ]
 
 
@@ -183,6 +185,18 @@ def lib():
         L.kasa_build_shrink.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.kasa_build_edit_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_build_taxa_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kasa_parse_create.argtypes = [C.c_int, C.c_uint64, C.c_void_p]
+        L.kasa_parse_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+        L.kasa_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_parse_status_text.argtypes = [C.c_int]
+        L.kasa_parse_status_text.restype = C.c_char_p
+        L.kasa_parse_sizes.argtypes = [C.c_void_p] * 4
+        L.kasa_parse_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
+        L.kasa_parse_take.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.kasa_parse_tile_bytes.argtypes = []
+        L.kasa_parse_stage_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_parse_destroy.argtypes = [C.c_void_p]
+        L.kasa_parse_destroy.restype = None
         _check_runtime(L)
         _lib = L
     return _lib
@@ -556,6 +570,80 @@ class Builder:
     def close(self):
         if getattr(self, "h", None):
             lib().kasa_build_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_tile_bytes() -> int:
+    """Bytes of text one wavefront of the device parser owns (kasa_parse_tile_bytes)."""
+    return int(lib().kasa_parse_tile_bytes())
+
+
+class Parser:
+    """A pool of reads parsed from FASTA / FASTQ text on the device (kasa_parse_*): `append` puts the reads of a chunk of
+    whole records behind those pooled, `fetch` copies reads back, `take` hands the first reads to a Context as its batch."""
+
+    def __init__(self, device: int = 0, long_sequence: int = 1_000_000):
+        self.device = device
+        h = C.c_void_p()
+        _check(lib().kasa_parse_create(C.c_int(device), C.c_uint64(long_sequence), C.byref(h)))
+        self.h = h
+
+    def append(self, text: bytes, fasta: bool):
+        """(reads added, parsable).  parsable False: the chunk is not in the form the device takes and the pool is as it was;
+        `status()` says why."""
+        buf = np.frombuffer(text, dtype=np.uint8)
+        n, ok = C.c_uint64(0), C.c_int(0)
+        _check(lib().kasa_parse_append(self.h, _p(buf) if buf.shape[0] else None, C.c_uint64(buf.shape[0]), C.c_int(1 if fasta else 0),
+                                       C.byref(n), C.byref(ok)))
+        return int(n.value), bool(ok.value)
+
+    def status(self):
+        """(KASA_PARSE_* code, its text, chunk position of the offending line) of the last append."""
+        code, at = C.c_int(0), C.c_uint64(0)
+        _check(lib().kasa_parse_status(self.h, C.byref(code), C.byref(at)))
+        return int(code.value), lib().kasa_parse_status_text(code).decode(), int(at.value)
+
+    def sizes(self):
+        """(reads, letters, name bytes) pooled right now."""
+        r, b, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_parse_sizes(self.h, C.byref(r), C.byref(b), C.byref(m)))
+        return int(r.value), int(b.value), int(m.value)
+
+    def fetch(self, first: int = 0, n: int = None, want_bases: bool = True):
+        """Reads [first, first + n) of the pool: (lengths u32[n], name_off u64[n+1], names u8[...], off i64[n+1], bases u8[...]
+        or None); the offsets are rebased to `first`."""
+        pooled = self.sizes()[0]
+        n = pooled - first if n is None else n
+        lengths = np.zeros(n, dtype=np.uint32)
+        name_off = np.zeros(n + 1, dtype=np.uint64)
+        off = np.zeros(n + 1, dtype=np.int64)
+        L = lib()
+        _check(L.kasa_parse_fetch(self.h, C.c_uint64(first), C.c_uint64(n), _p(lengths), _p(name_off), None, _p(off), None))
+        names = np.zeros(int(name_off[-1]), dtype=np.uint8)
+        bases = np.zeros(int(off[-1]), dtype=np.uint8) if want_bases else None
+        _check(L.kasa_parse_fetch(self.h, C.c_uint64(first), C.c_uint64(n), None, None, _p(names), None, _p(bases)))
+        return lengths, name_off, names, off, bases
+
+    def take(self, ctx: "Context", n_reads: int):
+        """The first n_reads pooled reads become ctx's batch (as Context.upload does) and leave the pool."""
+        _check(lib().kasa_parse_take(self.h, ctx.h, C.c_uint64(n_reads)))
+        ctx.n_reads = int(n_reads)
+
+    def stage_ms(self):
+        """(text upload, kernels) in HIP-event milliseconds, summed over the appends."""
+        u, k = C.c_double(0), C.c_double(0)
+        _check(lib().kasa_parse_stage_ms(self.h, C.byref(u), C.byref(k)))
+        return float(u.value), float(k.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().kasa_parse_destroy(self.h)
             self.h = None
 
     def __del__(self):

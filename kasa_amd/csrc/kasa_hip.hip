@@ -898,8 +898,10 @@ __global__ void upload_max_kernel(const uint64_t *__restrict__ readCnt, int64_t 
 // Paired-end input hands both mates of a pair over as two sequences of one read (Read.hpp:834-1049): their k-mers
 // carry the same read id, none spans the junction.  The host only copies: the tables (offsets relative to the batch,
 // k-mers before every sequence and read) are made on the device -- the host loop over ten million reads took 0.1 s.
-// resident: `bases` and `offsets` both lie in device memory and stay the caller's; the bases are read in place.
-static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets, int64_t nSeq, const uint32_t *seqRead, int64_t nReads, bool resident = false)
+// resident: `bases` and `offsets` both lie in device memory and stay the caller's; the bases are read in place -- or, ownCopy
+// (kasa_parse_take: the pool's memory is reused by its next append), copied into the context's buffer like a host's.
+static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets, int64_t nSeq, const uint32_t *seqRead, int64_t nReads, bool resident = false,
+                       bool ownCopy = false)
 {
     if (!c) return fail(KASA_E_ARG, "ctx is NULL");
     if (nSeq < 0 || nReads < 0 || (nSeq > 0 && (!offsets || !bases))) return fail(KASA_E_ARG, "kasa_batch_upload: bad arguments");
@@ -918,11 +920,12 @@ static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets
     if (ends[1] < ends[0]) return fail(KASA_E_ARG, "kasa_batch_upload: offsets are not ascending");
     const uint64_t nBases = (uint64_t)(ends[1] - ends[0]);
     int rc;
-    if ((rc = resident ? KASA_OK : c->bases.reserve(nBases + 64)) || (rc = c->baseOff.reserve(((size_t)nSeq + 1) * 8)) ||
+    const bool inPlace = resident && !ownCopy;
+    if ((rc = inPlace ? KASA_OK : c->bases.reserve(nBases + 64)) || (rc = c->baseOff.reserve(((size_t)nSeq + 1) * 8)) ||
         (rc = c->kmerOff.reserve(((size_t)nReads + 1) * 8)) || (rc = c->seqOff.reserve(((size_t)nSeq + 1) * 8)) ||
         (rc = c->seqRead.reserve((size_t)nSeq * 4 + 64)) || (rc = c->rawOff.reserve(((size_t)nSeq + 1) * 8)))
         return rc;
-    if (resident) c->basesPtr = bases + ends[0];
+    if (inPlace) c->basesPtr = bases + ends[0];
     else {
         if (nBases) HIPCHK(hipMemcpyAsync(c->bases.p, bases + ends[0], nBases, hipMemcpyDefault, c->stream));   // `bases` may live in device memory (a host that keeps its reads in HBM)
         c->basesPtr = c->bases.as<uint8_t>();
@@ -8680,3 +8683,8 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
 // ------------------------------------------------------------------------------------------------
 #include "kasa_build.h"
 #include "kasa_edit.h"
+
+// ------------------------------------------------------------------------------------------------
+// parse: FASTA / FASTQ text -> the reads of a batch on the device (kasa_parse_*)
+// ------------------------------------------------------------------------------------------------
+#include "kasa_parse.h"

@@ -1,0 +1,562 @@
+// kasa_parse.h -- FASTA / FASTQ text -> the reads of a batch, on the device, behind kasa_parse_* of include/kasa_hip.h.
+//
+// Specification: parseRecords of kasa_amd/host/kasa_identify.cpp (what Read.hpp:699-760 hands on for reads that fit one chunk).
+// A chunk of whole records (it starts at a header line; only its last line may lack a line feed) becomes
+//   bases   : the sequence lines back to back, untouched ('\r' stays, no cleaning, no case folding)
+//   off     : running offsets into bases
+//   names   : header without its first character + one space, back to back, with nameOff
+//   lengths : letters + one per sequence line (FASTA: per non-empty sequence line)
+// behind the reads the pool already holds.  Kernels, all streaming (bound: HBM copy rate):
+//   line table : prs_count_kernel (16-byte loads, line feeds per tile of a wavefront), one running sum over the tiles
+//                (rocPRIM), prs_lines_kernel (the same loads again, every line feed writes the start of the next line)
+//   classify   : prs_classify_kernel, one lane per line: header / sequence line / neither, the FASTQ form checked line by
+//                line; two running sums (rocPRIM) over {headers, sequence lines} and {sequence bytes, name bytes} give every
+//                line its read, its place in `bases` and in `names`; prs_index_kernel lists the header lines and the
+//                non-empty sequence lines; prs_reads_kernel, one lane per read, writes off / nameOff / lengths
+//   gather     : prs_gather_kernel, work split by OUTPUT bytes: a wavefront owns 4 KiB of the output, finds the first and last
+//                source line of that tile in the list (wave-uniform binary searches), every lane finds the line of its 16
+//                output bytes between those two, reads them with unaligned dword loads + v_alignbyte (or byte by byte where
+//                the 16 bytes span lines) and stores one aligned 16-byte vector.  The same sweep checks the sequence bytes
+//                for ' ' and '\t'.  No atomics except the one that reports the first offence; no lane walks a record.
+// A chunk that is not in the form the device takes (KASA_PARSE_* codes) leaves the pool as it was: everything is written
+// behind the pool's end and the sizes move only when the status word is clean.
+#pragma once
+#include <memory>
+
+namespace kasa_parse_impl {
+
+static constexpr int STEP_BYTES = 1024;                 // 64 lanes x 16 bytes: one load instruction of a wavefront
+static constexpr int STEPS = 4;
+static constexpr int TILE_BYTES = STEP_BYTES * STEPS;   // what one wavefront owns (input tile of the line table, output tile of the gather)
+static constexpr int WAVES = 4;                         // per workgroup
+static constexpr uint64_t MAX_CHUNK = 0xFFFF0000ull;    // positions in a chunk are 32-bit
+
+// 0x80 in every byte of w that equals the pattern's byte (exact per byte: no borrow between bytes)
+__device__ __forceinline__ uint32_t eq_bytes(uint32_t w, uint32_t pattern)
+{
+    const uint32_t x = w ^ pattern;
+    const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+    return ~(t | x | 0x7F7F7F7Fu);
+}
+__device__ __forceinline__ unsigned long long status_key(uint32_t pos, int code) { return ((unsigned long long)pos << 8) | (unsigned)code; }
+
+// text is padded with zero bytes up to a whole tile: every load is a full one and a pad byte is no line feed
+__global__ __launch_bounds__(64 * WAVES) void prs_count_kernel(const uint4 *__restrict__ text, uint32_t nTiles, uint32_t *__restrict__ tileCnt)
+{
+    const uint32_t tile = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (tile >= nTiles) return;
+    const uint4 *p = text + (size_t)tile * (TILE_BYTES / 16) + lane;
+    uint32_t c = 0;
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        const uint4 v = p[s * 64];
+        c += __popc(eq_bytes(v.x, 0x0A0A0A0Au)) + __popc(eq_bytes(v.y, 0x0A0A0A0Au)) + __popc(eq_bytes(v.z, 0x0A0A0A0Au)) + __popc(eq_bytes(v.w, 0x0A0A0A0Au));
+    }
+    for (int o = 32; o; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
+    if (lane == 0) { tileCnt[tile] = c; if (tile == 0) tileCnt[nTiles] = 0; }
+}
+
+// lineStart[0] = 0, lineStart[k + 1] = position behind the k-th line feed; line i = text[lineStart[i], lineStart[i + 1] - 1).
+// A last line without a line feed ends at nBytes: lineStart[nLines] = nBytes + 1.
+__global__ __launch_bounds__(64 * WAVES) void prs_lines_kernel(const uint4 *__restrict__ text, uint32_t nTiles, const uint32_t *__restrict__ tileOff,
+                                                               uint32_t *__restrict__ lineStart, uint32_t nLines, uint32_t nBytes, int trailingFeed)
+{
+    const uint32_t tile = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (tile >= nTiles) return;
+    if (tile == 0 && lane == 0) { lineStart[0] = 0; if (!trailingFeed) lineStart[nLines] = nBytes + 1; }
+    const uint4 *p = text + (size_t)tile * (TILE_BYTES / 16) + lane;
+    uint32_t base = tileOff[tile];
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        const uint4 v = p[s * 64];
+        uint32_t m[4] = {eq_bytes(v.x, 0x0A0A0A0Au), eq_bytes(v.y, 0x0A0A0A0Au), eq_bytes(v.z, 0x0A0A0A0Au), eq_bytes(v.w, 0x0A0A0A0Au)};
+        const uint32_t c = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
+        uint32_t incl = c;
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, d); if ((int)lane >= d) incl += t; }
+        uint32_t k = base + incl - c;
+        const uint32_t pos0 = tile * TILE_BYTES + s * STEP_BYTES + lane * 16;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            for (uint32_t mm = m[w]; mm; mm &= mm - 1) lineStart[1 + k++] = pos0 + w * 4 + ((__ffs((int)mm) - 1) >> 3) + 1;
+        base += (uint32_t)__shfl((int)incl, 63);
+    }
+}
+
+// One lane per line.  k1 = headers << 32 | counted sequence lines, k2 = sequence bytes << 32 | name bytes (a chunk is below
+// 2^32 bytes, so neither half carries into the other under a running sum); entry nLines = 0: the sums' totals land there.
+__global__ void prs_classify_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ lineStart, uint32_t nLines, int fasta, uint64_t longSeq,
+                                    uint64_t *__restrict__ k1, uint64_t *__restrict__ k2, unsigned long long *__restrict__ status)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nLines) return;
+    if (i == nLines) {
+        k1[i] = 0; k2[i] = 0;
+        if (!fasta && (nLines & 3u)) atomicMin(status, status_key(lineStart[nLines & ~3u], KASA_PARSE_FASTQ_LINES));
+        return;
+    }
+    const uint32_t s = lineStart[i], len = lineStart[i + 1] - 1 - s;
+    const uint8_t c0 = len ? text[s] : 0;
+    bool hdr, seq;
+    if (fasta) {
+        hdr = len > 0 && c0 == '>';
+        seq = len > 0 && !hdr;                                   // empty lines are skipped and not counted
+    } else {
+        const uint32_t m = i & 3u;
+        hdr = m == 0; seq = m == 1;
+        int bad = 0;
+        if (len == 0) bad = KASA_PARSE_EMPTY_LINE;
+        else if (m == 0 && c0 != '@') bad = KASA_PARSE_FASTQ_HEADER;
+        else if (m == 1 && c0 == '+') bad = KASA_PARSE_FASTQ_SEQ_PLUS;     // the host parser would take it for the '+' line
+        else if (m == 1 && (uint64_t)len >= longSeq) bad = KASA_PARSE_LONG;
+        else if (m == 2 && c0 != '+') bad = KASA_PARSE_FASTQ_PLUS;
+        else if (m == 3 && len != lineStart[i - 1] - 1 - lineStart[i - 2]) bad = KASA_PARSE_FASTQ_QUALITY;
+        if (bad) atomicMin(status, status_key(s, bad));
+    }
+    k1[i] = ((uint64_t)(hdr ? 1 : 0) << 32) | (uint64_t)(seq ? 1 : 0);
+    k2[i] = ((uint64_t)(seq ? len : 0) << 32) | (uint64_t)(hdr ? len : 0);      // a name is the header less one character plus one space
+}
+
+// after the running sums: the header lines by read, the non-empty sequence lines in order with their place in the output
+__global__ void prs_index_kernel(const uint32_t *__restrict__ lineStart, const uint64_t *__restrict__ k1, const uint64_t *__restrict__ k2, uint32_t nLines,
+                                 uint32_t *__restrict__ hdrLine, uint32_t *__restrict__ seqSrc, uint32_t *__restrict__ seqDst)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nLines) return;
+    const uint64_t a = k1[i];
+    if (i == nLines) { hdrLine[(uint32_t)(a >> 32)] = nLines; seqDst[(uint32_t)a] = (uint32_t)(k2[i] >> 32); return; }
+    const uint64_t b = k1[i + 1], p = k2[i];
+    if ((b >> 32) != (a >> 32)) hdrLine[(uint32_t)(a >> 32)] = i;
+    if ((uint32_t)b != (uint32_t)a && (k2[i + 1] >> 32) != (p >> 32)) { seqSrc[(uint32_t)a] = lineStart[i]; seqDst[(uint32_t)a] = (uint32_t)(p >> 32); }
+}
+
+// One lane per read (and one for the end): off, nameOff, lengths at the pool's end; the names' places for the gather.
+__global__ void prs_reads_kernel(const uint32_t *__restrict__ lineStart, const uint32_t *__restrict__ hdrLine, const uint64_t *__restrict__ k1,
+                                 const uint64_t *__restrict__ k2, uint32_t nReads, uint64_t longSeq, int64_t baseBase, uint64_t nameBase,
+                                 int64_t *__restrict__ off, uint64_t *__restrict__ nameOff, uint32_t *__restrict__ lengths,
+                                 uint32_t *__restrict__ nameSrc, uint32_t *__restrict__ nameDst, unsigned long long *__restrict__ status)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > nReads) return;
+    const uint32_t h = hdrLine[r];
+    const uint64_t p = k2[h];
+    off[r] = baseBase + (int64_t)(p >> 32);
+    nameOff[r] = nameBase + (uint32_t)p;
+    nameDst[r] = (uint32_t)p;
+    if (r == nReads) return;
+    const uint32_t h2 = hdrLine[r + 1];
+    const uint64_t letters = (k2[h2] >> 32) - (p >> 32);
+    lengths[r] = (uint32_t)letters + ((uint32_t)k1[h2] - (uint32_t)k1[h]);
+    nameSrc[r] = lineStart[h] + 1;
+    if (letters >= longSeq) atomicMin(status, status_key(lineStart[h], KASA_PARSE_LONG));
+}
+
+// largest j in [lo, hi] with dst[j] <= o (dst ascends strictly, dst[lo] <= o)
+__device__ __forceinline__ uint32_t prs_find(const uint32_t *__restrict__ dst, uint32_t lo, uint32_t hi, uint32_t o)
+{
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo + 1) >> 1); if (dst[mid] <= o) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// Entry j = text[src[j] ...) goes to output bytes [dst[j], dst[j + 1]); NAMES: its last byte is a space instead.  n >= 1 entries
+// of at least one byte, dst[n] = total.  `out` is the 16-byte aligned address at or below the pool's end and `lead` what lies
+// between the two, so that every store of a whole vector is aligned whatever the pool holds.
+template <bool NAMES>
+__global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ src, const uint32_t *__restrict__ dst,
+                                                                uint32_t n, uint32_t total, uint8_t *__restrict__ out, uint32_t lead,
+                                                                unsigned long long *__restrict__ status)
+{
+    const uint32_t tile = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const uint64_t vEnd = (uint64_t)lead + total, v0 = (uint64_t)tile * TILE_BYTES;
+    if (v0 >= vEnd) return;
+    const uint64_t v1 = v0 + TILE_BYTES < vEnd ? v0 + TILE_BYTES : vEnd;
+    const uint32_t jLo = prs_find(dst, 0, n - 1, (uint32_t)((v0 > lead ? v0 : lead) - lead));
+    const uint32_t jHi = prs_find(dst, jLo, n - 1, (uint32_t)(v1 - 1 - lead));
+    for (int s = 0; s < STEPS; ++s) {
+        const uint64_t va = v0 + (uint64_t)s * STEP_BYTES + lane * 16;
+        const uint64_t vb = va + 16 < vEnd ? va + 16 : vEnd, vs = va > lead ? va : lead;
+        if (vs >= vb) continue;
+        const uint32_t oLo = (uint32_t)(vs - lead), oHi = (uint32_t)(vb - lead);
+        uint32_t j = prs_find(dst, jLo, jHi, oLo);
+        uint32_t d0 = dst[j], d1 = dst[j + 1], s0 = src[j];
+        uint32_t w[4] = {0, 0, 0, 0};
+        uint32_t blankAt = ~0u;                                                  // the chunk position of the first ' ' or '\t' this lane met
+        const bool whole = oHi - oLo == 16;
+        if (whole && (uint64_t)oLo + 16 + (NAMES ? 1 : 0) <= d1) {
+            // 16 bytes of one line: five dwords from the 4-byte aligned address below (the text is padded), shifted into place
+            const uint32_t a = s0 + (oLo - d0);
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(text + (a & ~3u));
+            const uint32_t sh = a & 3u, x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3], x4 = q[4];
+            w[0] = __builtin_amdgcn_alignbyte(x1, x0, sh); w[1] = __builtin_amdgcn_alignbyte(x2, x1, sh);
+            w[2] = __builtin_amdgcn_alignbyte(x3, x2, sh); w[3] = __builtin_amdgcn_alignbyte(x4, x3, sh);
+            if (!NAMES && (eq_bytes(w[0], 0x20202020u) | eq_bytes(w[1], 0x20202020u) | eq_bytes(w[2], 0x20202020u) | eq_bytes(w[3], 0x20202020u) |
+                           eq_bytes(w[0], 0x09090909u) | eq_bytes(w[1], 0x09090909u) | eq_bytes(w[2], 0x09090909u) | eq_bytes(w[3], 0x09090909u)) != 0)
+                for (int q = 15; q >= 0; --q) { const uint32_t c = (w[q >> 2] >> (8 * (q & 3))) & 0xFFu; if (c == ' ' || c == '\t') blankAt = a + q; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const uint64_t v = va + q;
+                if (v < vs || v >= vb) continue;
+                const uint32_t k = (uint32_t)(v - lead);
+                while (k >= d1) { ++j; d0 = d1; d1 = dst[j + 1]; s0 = src[j]; }       // (every entry has a byte: at most 16 steps per lane)
+                const uint32_t c = (NAMES && k == d1 - 1) ? (uint32_t)' ' : (uint32_t)text[s0 + (k - d0)];
+                if (!NAMES && (c == ' ' || c == '\t') && blankAt == ~0u) blankAt = s0 + (k - d0);
+                w[q >> 2] |= c << (8 * (q & 3));
+            }
+        }
+        if (blankAt != ~0u) atomicMin(status, status_key(blankAt, KASA_PARSE_BLANK));
+        if (whole) *reinterpret_cast<uint4 *>(out + va) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+            for (int q = 0; q < 16; ++q) { const uint64_t v = va + q; if (v >= vs && v < vb) out[v] = (uint8_t)(w[q >> 2] >> (8 * (q & 3))); }
+    }
+}
+
+// the reads a take left behind move to the front of the pool's other set of arrays
+template <class T> __global__ void prs_rebase_kernel(const T *__restrict__ src, T *__restrict__ dst, uint64_t n, T delta)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i] - delta;
+}
+
+// the ends of reads [r0, r0 + n) in letters and name bytes: four values for ONE read-back
+__global__ void prs_ends_kernel(const int64_t *__restrict__ off, const uint64_t *__restrict__ nameOff, uint64_t r0, uint64_t n, uint64_t *__restrict__ out)
+{
+    out[0] = (uint64_t)off[r0]; out[1] = (uint64_t)off[r0 + n]; out[2] = nameOff[r0]; out[3] = nameOff[r0 + n];
+}
+
+struct PoolArrays { DevBuf bases, off, names, nameOff, lengths; };
+
+}  // namespace kasa_parse_impl
+
+struct kasa_parser {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    uint64_t longSeq = 0;
+    // reads [head, nReads) of arrays[cur] are the pool: off / nameOff keep running values, a fetch or take rebases them
+    kasa_parse_impl::PoolArrays arrays[2];
+    int cur = 0;
+    uint64_t head = 0, nReads = 0, headBase = 0, endBase = 0, headName = 0, endName = 0;
+    DevBuf text, tileCnt, lineStart, k1, k2, hdrLine, seqSrc, seqDst, nameSrc, nameDst, scanTmp, status;
+    int lastCode = 0; uint64_t lastAt = 0;
+    double msUpload = 0, msParse = 0;
+};
+
+namespace kasa_parse_impl {
+
+static int grow_keep(DevBuf &b, size_t need, size_t keep, hipStream_t stream)
+{
+    if (need <= b.cap) return KASA_OK;
+    DevBuf nb;
+    int rc = nb.reserve(std::max(need, b.cap + b.cap / 2));
+    if (rc) return rc;
+    if (keep) HIPCHK(hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    b = std::move(nb);
+    return KASA_OK;
+}
+
+// room for `addReads` reads of `addBases` letters and `addNames` name bytes behind what set `a` holds (kept)
+static int pool_room(kasa_parser *p, PoolArrays &a, uint64_t reads, uint64_t bases, uint64_t names, uint64_t addReads, uint64_t addBases, uint64_t addNames, bool fresh)
+{
+    int rc;
+    if ((rc = grow_keep(a.bases, bases + addBases + 64, fresh ? 0 : bases, p->stream)) || (rc = grow_keep(a.names, names + addNames + 64, fresh ? 0 : names, p->stream)) ||
+        (rc = grow_keep(a.off, (reads + addReads + 1) * 8, fresh ? 0 : (reads + 1) * 8, p->stream)) ||
+        (rc = grow_keep(a.nameOff, (reads + addReads + 1) * 8, fresh ? 0 : (reads + 1) * 8, p->stream)) ||
+        (rc = grow_keep(a.lengths, (reads + addReads) * 4 + 64, fresh ? 0 : reads * 4, p->stream)))
+        return rc;
+    return KASA_OK;
+}
+
+// The reads already taken leave the arrays.  An empty pool starts over where it is (off[0] = nameOff[0] = 0 again, nothing
+// copied); a remainder moves to the front of the other set once the taken letters outweigh it, so that the copies stay
+// below the bytes appended and the arrays below twice the pool plus a chunk.
+static int pool_compact(kasa_parser *p)
+{
+    if (p->head == 0) return KASA_OK;
+    const uint64_t n = p->nReads - p->head, nb = p->endBase - p->headBase, nn = p->endName - p->headName;
+    if (n == 0) {
+        HIPCHK(hipMemsetAsync(p->arrays[p->cur].off.p, 0, 8, p->stream));
+        HIPCHK(hipMemsetAsync(p->arrays[p->cur].nameOff.p, 0, 8, p->stream));
+        p->head = p->nReads = 0; p->headBase = p->endBase = 0; p->headName = p->endName = 0;
+        return KASA_OK;
+    }
+    if (p->headBase <= nb) return KASA_OK;
+    PoolArrays &from = p->arrays[p->cur], &to = p->arrays[p->cur ^ 1];
+    int rc = pool_room(p, to, 0, 0, 0, n, nb, nn, true);
+    if (rc) return rc;
+    if (nb) HIPCHK(hipMemcpyAsync(to.bases.p, from.bases.as<uint8_t>() + p->headBase, nb, hipMemcpyDeviceToDevice, p->stream));
+    if (nn) HIPCHK(hipMemcpyAsync(to.names.p, from.names.as<char>() + p->headName, nn, hipMemcpyDeviceToDevice, p->stream));
+    if (n) HIPCHK(hipMemcpyAsync(to.lengths.p, from.lengths.as<uint32_t>() + p->head, n * 4, hipMemcpyDeviceToDevice, p->stream));
+    prs_rebase_kernel<int64_t><<<blocks_for(n + 1, 256), 256, 0, p->stream>>>(from.off.as<int64_t>() + p->head, to.off.as<int64_t>(), n + 1, (int64_t)p->headBase);
+    prs_rebase_kernel<uint64_t><<<blocks_for(n + 1, 256), 256, 0, p->stream>>>(from.nameOff.as<uint64_t>() + p->head, to.nameOff.as<uint64_t>(), n + 1, p->headName);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->cur ^= 1; p->head = 0; p->nReads = n; p->headBase = 0; p->endBase = nb; p->headName = 0; p->endName = nn;
+    return KASA_OK;
+}
+
+static int scan64(kasa_parser *p, uint64_t *a, size_t n)
+{
+    size_t tmpBytes = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, a, a, (uint64_t)0, n, rocprim::plus<uint64_t>(), p->stream));
+    int rc = p->scanTmp.reserve(tmpBytes);
+    if (rc) return rc;
+    HIPCHK(rocprim::exclusive_scan(p->scanTmp.p, tmpBytes, a, a, (uint64_t)0, n, rocprim::plus<uint64_t>(), p->stream));
+    return KASA_OK;
+}
+
+static int refuse(kasa_parser *p, int code, uint64_t at, int *parsable)
+{
+    p->lastCode = code; p->lastAt = at;
+    if (parsable) *parsable = 0;
+    return KASA_OK;
+}
+
+static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fasta, uint64_t *nReadsAdded, int *parsable)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (nBytes && !text) return fail(KASA_E_ARG, "kasa_parse_append: text is NULL");
+    if (nReadsAdded) *nReadsAdded = 0;
+    if (parsable) *parsable = 1;
+    p->lastCode = KASA_PARSE_OK; p->lastAt = 0;
+    if (nBytes == 0) return KASA_OK;
+    if (nBytes >= MAX_CHUNK) return refuse(p, KASA_PARSE_TOO_LARGE, 0, parsable);
+    if (fasta && text[0] != '>') return refuse(p, KASA_PARSE_FASTA_HEADER, 0, parsable);
+    HIPCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = pool_compact(p))) return rc;
+    const uint32_t nTiles = (uint32_t)((nBytes + TILE_BYTES - 1) / TILE_BYTES);
+    const size_t padded = (size_t)nTiles * TILE_BYTES + 64;
+    if ((rc = p->text.reserve(padded)) || (rc = p->tileCnt.reserve(((size_t)nTiles + 1) * 4)) || (rc = p->status.reserve(64))) return rc;
+    HIPCHK(hipEventRecord(p->ev[0], p->stream));
+    HIPCHK(hipMemcpyAsync(p->text.p, text, nBytes, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemsetAsync(p->text.as<uint8_t>() + nBytes, 0, padded - nBytes, p->stream));
+    HIPCHK(hipEventRecord(p->ev[1], p->stream));
+    HIPCHK(hipMemsetAsync(p->status.p, 0xFF, 8, p->stream));
+    // ---- line table
+    uint32_t *tileCnt = p->tileCnt.as<uint32_t>();
+    prs_count_kernel<<<blocks_for(nTiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint4>(), nTiles, tileCnt);
+    HIPCHK(hipGetLastError());
+    {
+        size_t tmpBytes = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>(), p->stream));
+        if ((rc = p->scanTmp.reserve(tmpBytes))) return rc;
+        HIPCHK(rocprim::exclusive_scan(p->scanTmp.p, tmpBytes, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>(), p->stream));
+    }
+    uint32_t nFeeds = 0;
+    HIPCHK(hipMemcpyAsync(&nFeeds, tileCnt + nTiles, 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    const int trailingFeed = text[nBytes - 1] == '\n';
+    const uint32_t nLines = nFeeds + (trailingFeed ? 0u : 1u);
+    const size_t nl = (size_t)nLines + 2;
+    if ((rc = p->lineStart.reserve(nl * 4)) || (rc = p->k1.reserve(nl * 8)) || (rc = p->k2.reserve(nl * 8)) || (rc = p->hdrLine.reserve(nl * 4)) ||
+        (rc = p->seqSrc.reserve(nl * 4)) || (rc = p->seqDst.reserve(nl * 4)))
+        return rc;
+    uint32_t *lineStart = p->lineStart.as<uint32_t>();
+    uint64_t *k1 = p->k1.as<uint64_t>(), *k2 = p->k2.as<uint64_t>();
+    unsigned long long *status = p->status.as<unsigned long long>();
+    prs_lines_kernel<<<blocks_for(nTiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint4>(), nTiles, tileCnt, lineStart, nLines, (uint32_t)nBytes, trailingFeed);
+    HIPCHK(hipGetLastError());
+    // ---- classify
+    prs_classify_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(p->text.as<uint8_t>(), lineStart, nLines, fasta, p->longSeq, k1, k2, status);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan64(p, k1, (size_t)nLines + 1)) || (rc = scan64(p, k2, (size_t)nLines + 1))) return rc;
+    prs_index_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(lineStart, k1, k2, nLines, p->hdrLine.as<uint32_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    uint64_t tot[2] = {0, 0};
+    unsigned long long st = ~0ull;
+    HIPCHK(hipMemcpyAsync(&tot[0], k1 + nLines, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(&tot[1], k2 + nLines, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(&st, status, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (st != ~0ull) {                                                             // (the text went up all the same: it counts)
+        float up = 0.0f;
+        if (hipEventElapsedTime(&up, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += up;
+        return refuse(p, (int)(st & 0xFF), st >> 8, parsable);
+    }
+    const uint64_t addReads = tot[0] >> 32, addBases = tot[1] >> 32, addNames = tot[1] & 0xFFFFFFFFull;
+    // FASTA sequence lines counted = the non-empty ones = the gather's entries; FASTQ: one per read, none empty
+    const uint32_t nSeqLines = (uint32_t)tot[0];
+    PoolArrays &a = p->arrays[p->cur];
+    if ((rc = pool_room(p, a, p->nReads, p->endBase, p->endName, addReads, addBases, addNames, false)) ||
+        (rc = p->nameSrc.reserve((addReads + 2) * 4)) || (rc = p->nameDst.reserve((addReads + 2) * 4)))
+        return rc;
+    // ---- per read, then the two gathers behind the pool's end
+    prs_reads_kernel<<<blocks_for(addReads + 1, 256), 256, 0, p->stream>>>(lineStart, p->hdrLine.as<uint32_t>(), k1, k2, (uint32_t)addReads, p->longSeq,
+        (int64_t)p->endBase, p->endName, a.off.as<int64_t>() + p->nReads, a.nameOff.as<uint64_t>() + p->nReads, a.lengths.as<uint32_t>() + p->nReads,
+        p->nameSrc.as<uint32_t>(), p->nameDst.as<uint32_t>(), status);
+    HIPCHK(hipGetLastError());
+    if (addBases && nSeqLines) {
+        const uint32_t lead = (uint32_t)(p->endBase & 15);
+        const uint64_t tiles = (lead + addBases + TILE_BYTES - 1) / TILE_BYTES;
+        prs_gather_kernel<false><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>(),
+            nSeqLines, (uint32_t)addBases, a.bases.as<uint8_t>() + (p->endBase - lead), lead, status);
+        HIPCHK(hipGetLastError());
+    }
+    if (addNames && addReads) {
+        const uint32_t lead = (uint32_t)(p->endName & 15);
+        const uint64_t tiles = (lead + addNames + TILE_BYTES - 1) / TILE_BYTES;
+        prs_gather_kernel<true><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->nameSrc.as<uint32_t>(), p->nameDst.as<uint32_t>(),
+            (uint32_t)addReads, (uint32_t)addNames, a.names.as<uint8_t>() + (p->endName - lead), lead, status);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(p->ev[2], p->stream));
+    HIPCHK(hipMemcpyAsync(&st, status, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += ms;
+    if (hipEventElapsedTime(&ms, p->ev[1], p->ev[2]) == hipSuccess) p->msParse += ms;
+    if (st != ~0ull) return refuse(p, (int)(st & 0xFF), st >> 8, parsable);         // (what was written lies behind the pool's end)
+    p->nReads += addReads; p->endBase += addBases; p->endName += addNames;
+    if (nReadsAdded) *nReadsAdded = addReads;
+    return KASA_OK;
+}
+
+static int pool_ends(kasa_parser *p, uint64_t r0, uint64_t n, uint64_t e[4])
+{
+    const PoolArrays &a = p->arrays[p->cur];
+    int rc = p->status.reserve(64);
+    if (rc) return rc;
+    uint64_t *d = p->status.as<uint64_t>() + 2;                                   // (behind the status word)
+    prs_ends_kernel<<<1, 1, 0, p->stream>>>(a.off.as<int64_t>(), a.nameOff.as<uint64_t>(), r0, n, d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e, d, 32, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return KASA_OK;
+}
+
+static int fetch_impl(kasa_parser *p, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    const uint64_t pooled = p->nReads - p->head;
+    if (first > pooled || n > pooled - first)
+        return fail(KASA_E_ARG, "kasa_parse_fetch: reads [%llu, +%llu) outside the %llu pooled", (unsigned long long)first, (unsigned long long)n, (unsigned long long)pooled);
+    HIPCHK(hipSetDevice(p->device));
+    const PoolArrays &a = p->arrays[p->cur];
+    const uint64_t r0 = p->head + first;
+    // the ends of the range, needed for the sizes of names and bases: one 32-byte read-back
+    uint64_t e[4] = {0, 0, 0, 0};
+    int rc = pool_ends(p, r0, n, e);
+    if (rc) return rc;
+    const int64_t ob[2] = {(int64_t)e[0], (int64_t)e[1]}; const uint64_t nb[2] = {e[2], e[3]};
+    if (lengths && n) HIPCHK(hipMemcpy(lengths, a.lengths.as<uint32_t>() + r0, n * 4, hipMemcpyDeviceToHost));
+    if (nameOff) { HIPCHK(hipMemcpy(nameOff, a.nameOff.as<uint64_t>() + r0, (n + 1) * 8, hipMemcpyDeviceToHost)); for (uint64_t i = 0; i <= n; ++i) nameOff[i] -= nb[0]; }
+    if (off) { HIPCHK(hipMemcpy(off, a.off.as<int64_t>() + r0, (n + 1) * 8, hipMemcpyDeviceToHost)); for (uint64_t i = 0; i <= n; ++i) off[i] -= ob[0]; }
+    if (names && nb[1] > nb[0]) HIPCHK(hipMemcpy(names, a.names.as<char>() + nb[0], nb[1] - nb[0], hipMemcpyDeviceToHost));
+    if (bases && ob[1] > ob[0]) HIPCHK(hipMemcpy(bases, a.bases.as<uint8_t>() + ob[0], (size_t)(ob[1] - ob[0]), hipMemcpyDeviceToHost));
+    return KASA_OK;
+}
+
+static int take_impl(kasa_parser *p, kasa_ctx *c, uint64_t n)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (!c) return fail(KASA_E_ARG, "ctx is NULL");
+    if (c->ix->device != p->device) return fail(KASA_E_ARG, "kasa_parse_take: the context is on device %d, the pool on device %d", c->ix->device, p->device);
+    if (n > p->nReads - p->head) return fail(KASA_E_ARG, "kasa_parse_take: %llu reads asked for, %llu pooled", (unsigned long long)n, (unsigned long long)(p->nReads - p->head));
+    HIPCHK(hipSetDevice(p->device));
+    const PoolArrays &a = p->arrays[p->cur];
+    uint64_t e[4] = {0, 0, 0, 0};                                                  // where the reads left behind start: one 32-byte read-back
+    int rc0 = pool_ends(p, p->head, n, e);
+    if (rc0) return rc0;
+    const uint64_t end = e[1], nameEnd = e[3];
+    // the context copies the bases (the pool's memory is reused by the next append) and returns with its stream idle
+    const int rc = upload_impl(c, a.bases.as<uint8_t>(), a.off.as<int64_t>() + p->head, (int64_t)n, nullptr, (int64_t)n, true, true);
+    if (rc) return rc;
+    p->head += n; p->headBase = end; p->headName = nameEnd;
+    return KASA_OK;
+}
+
+}  // namespace kasa_parse_impl
+
+extern "C" int kasa_parse_tile_bytes(void) { return kasa_parse_impl::TILE_BYTES; }
+
+static int parse_create_impl(int device, uint64_t longSequence, kasa_parser **out)
+{
+    if (!out) return fail(KASA_E_ARG, "kasa_parse_create: out is NULL");
+    *out = nullptr;
+    if (longSequence == 0) return fail(KASA_E_ARG, "kasa_parse_create: longSequence must be at least 1");
+    int ndev = 0;
+    kasa_device_count(&ndev);
+    if (device < 0 || device >= ndev) return fail(KASA_E_HIP, "kasa_parse_create: no HIP device %d (found %d)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<kasa_parser, void (*)(kasa_parser *)> p(new kasa_parser, kasa_parse_destroy);
+    p->device = device; p->longSeq = longSequence;
+    HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    for (hipEvent_t &e : p->ev) HIPCHK(hipEventCreate(&e));
+    for (kasa_parse_impl::PoolArrays &a : p->arrays) {                  // off[0] = nameOff[0] = 0
+        int rc;
+        if ((rc = a.off.reserve(8)) || (rc = a.nameOff.reserve(8))) return rc;
+        HIPCHK(hipMemsetAsync(a.off.p, 0, 8, p->stream));
+        HIPCHK(hipMemsetAsync(a.nameOff.p, 0, 8, p->stream));
+    }
+    HIPCHK(hipStreamSynchronize(p->stream));
+    *out = p.release();
+    return KASA_OK;
+}
+
+extern "C" int kasa_parse_create(int device, uint64_t longSequence, kasa_parser **out) { KASA_GUARDED(parse_create_impl(device, longSequence, out)) }
+
+extern "C" void kasa_parse_destroy(kasa_parser *p)
+{
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);
+    for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+
+extern "C" int kasa_parse_append(kasa_parser *p, const char *text, uint64_t nBytes, int fasta, uint64_t *nReadsAdded, int *parsable)
+{
+    KASA_GUARDED(kasa_parse_impl::append_impl(p, text, nBytes, fasta, nReadsAdded, parsable))
+}
+
+extern "C" int kasa_parse_status(kasa_parser *p, int *code, uint64_t *at)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (code) *code = p->lastCode;
+    if (at) *at = p->lastAt;
+    return KASA_OK;
+}
+
+extern "C" const char *kasa_parse_status_text(int code)
+{
+    switch (code) {
+    case KASA_PARSE_OK: return "parsable";
+    case KASA_PARSE_FASTQ_LINES: return "the line count of a FASTQ chunk is not a multiple of 4";
+    case KASA_PARSE_FASTQ_HEADER: return "a FASTQ record does not start with '@'";
+    case KASA_PARSE_FASTQ_PLUS: return "the third line of a FASTQ record does not start with '+'";
+    case KASA_PARSE_FASTQ_QUALITY: return "a quality line differs in length from its sequence line";
+    case KASA_PARSE_EMPTY_LINE: return "an empty line in a FASTQ chunk";
+    case KASA_PARSE_BLANK: return "a space or tab in a sequence line";
+    case KASA_PARSE_LONG: return "a sequence long enough to be read in pieces";
+    case KASA_PARSE_FASTA_HEADER: return "a FASTA chunk does not start with '>'";
+    case KASA_PARSE_FASTQ_SEQ_PLUS: return "a FASTQ sequence line starts with '+'";
+    case KASA_PARSE_TOO_LARGE: return "a chunk of 4 GiB or more";
+    default: return "unknown";
+    }
+}
+
+extern "C" int kasa_parse_sizes(kasa_parser *p, uint64_t *nReads, uint64_t *nBases, uint64_t *nNameBytes)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (nReads) *nReads = p->nReads - p->head;
+    if (nBases) *nBases = p->endBase - p->headBase;
+    if (nNameBytes) *nNameBytes = p->endName - p->headName;
+    return KASA_OK;
+}
+
+extern "C" int kasa_parse_fetch(kasa_parser *p, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases)
+{
+    KASA_GUARDED(kasa_parse_impl::fetch_impl(p, first, n, lengths, nameOff, names, off, bases))
+}
+
+extern "C" int kasa_parse_take(kasa_parser *p, kasa_ctx *ctx, uint64_t nReads) { KASA_GUARDED(kasa_parse_impl::take_impl(p, ctx, nReads)) }
+
+extern "C" int kasa_parse_stage_ms(kasa_parser *p, double *uploadMs, double *parseMs)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (uploadMs) *uploadMs = p->msUpload;
+    if (parseMs) *parseMs = p->msParse;
+    return KASA_OK;
+}

@@ -217,7 +217,7 @@ static vector<uint64_t> loadFreq(const string &prefix, size_t nTaxa, int kHigh, 
 }
 
 // KASA_HOST_TIMING=1: where the host spends the time of "Time fastq" (seconds, summed over the file)
-struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
+struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
 static HostTimers g_ht;
 static std::chrono::steady_clock::time_point g_t0 = std::chrono::steady_clock::now();
 static void mark(const char *what, uint64_t id = ~0ull)          // KASA_HOST_TIMING: a time line of the file's pipeline
@@ -292,6 +292,7 @@ struct ReadSet {
     HugeVec<char> nameBlob; HugeVec<uint64_t> nameOff;         // specifier of read r = nameBlob[nameOff[r] .. nameOff[r + 1])
     HugeVec<uint32_t> lengths;                                 // "Length" of read r
     bool protein = false, fasta = true;
+    bool devBases = false;                                     // --device-parse: the letters lie in the device's pool (kasa_parse_*): `off` is filled, `bases` is empty
     // A record of a million letters and more: how the reference's reader cuts its lines (Utilities::FileReader hands out text
     // up to the next line feed or the end of its 2048-byte buffer, Utilities.hpp:448-539) -- it reads such a record in
     // pieces that end with one of those calls (Read.hpp:371-600; Batcher::piecesOf).
@@ -308,11 +309,11 @@ struct ReadSet {
     ReadSet slice(size_t first, size_t last, size_t spr, unsigned threads) const
     {
         ReadSet o;
-        o.protein = protein; o.fasta = fasta;
+        o.protein = protein; o.fasta = fasta; o.devBases = devBases;
         for (const LongRec &lr : longRecs) if (lr.read >= first && lr.read < last) { o.longRecs.push_back(lr); o.longRecs.back().read -= first; }
         const size_t m = last - first;
         const int64_t s0 = off[first * spr], s1 = off[last * spr];
-        o.bases.resize((size_t)(s1 - s0)); parCopy(o.bases.data(), bases.data() + s0, (size_t)(s1 - s0), threads);
+        if (!devBases) { o.bases.resize((size_t)(s1 - s0)); parCopy(o.bases.data(), bases.data() + s0, (size_t)(s1 - s0), threads); }
         o.off.resize(m * spr + 1);
         for (size_t q = 0; q <= m * spr; ++q) o.off[q] = off[first * spr + q] - s0;
         const uint64_t n0 = nameOff[first], n1 = nameOff[last];
@@ -648,6 +649,7 @@ struct Params {
     bool verbose = false, coverage = false, unique = false, protein = false;
     bool gzipOut = false;                        // --gzip: the --filter files are written through zlib (Compare.hpp:2455,3713-3731)
     bool coherence = false; float coherenceThreshold = 11.0f;   // --coherence, --coherenceThreshold (MetaHeader.h:159)
+    bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
 };
 
 struct IndexFiles {                               // what Compare::ReadIndex loads (Compare.hpp:49-363), shared by every worker
@@ -997,10 +999,22 @@ template <class T> struct PcieBuf {
 };
 
 struct SplitCarry;
+
+// --device-parse: the reads of a file parsed on the device and not yet taken by a batch.  The batcher's thread appends, the
+// worker takes: the reads of formed batches lie first in the pool, in batch order (`outstanding` of them), those the
+// batcher still holds as `pending` behind them.
+struct DevicePool {
+    kasa_parser *ps = nullptr;
+    std::mutex mu;
+    uint64_t outstanding = 0;
+    PcieBuf<char> stage;                          // KASA_PARSE_STAGE=pinned: the chunk's text copied to page-locked memory first (default: straight from the reader's buffer, which measured faster)
+    ~DevicePool() { kasa_parse_destroy(ps); }
+};
 struct Batch {
     uint64_t id = 0, firstRead = 0;
     SplitCarry *carry = nullptr;
     ReadSet rs;                                   // the batch's reads (offsets start at 0)
+    DevicePool *pool = nullptr;                   // --device-parse: the letters of `rs` are the pool's first reads (kasa_parse_take)
     vector<uint32_t> segRead;                     // paired-end: read of every sequence
     vector<uint64_t> flagged;                     // --filter: read numbers of contaminants
     uint64_t kmers = 0;
@@ -1086,9 +1100,16 @@ struct Batcher {
     bool midRead = false; size_t midPiece = 0;
     int64_t carriedLen = 0;                       // strTransfer::lengthOfDNA (Read.hpp:1181)
 
-    Batcher(const Params &pp, const IndexFiles &f, bool rows, uint64_t maxKmers) : p(pp), ixf(f), wantRows(rows), paired(!pp.input2.empty()), maxKmersPerBatch(maxKmers)
+    std::unique_ptr<DevicePool> pool;             // --device-parse (poolDevice >= 0): chunks are parsed there until one is not device-parsable
+    bool devParse = false;
+    Batcher(const Params &pp, const IndexFiles &f, bool rows, uint64_t maxKmers, int poolDevice = -1) : p(pp), ixf(f), wantRows(rows), paired(!pp.input2.empty()), maxKmersPerBatch(maxKmers)
     {
         const auto t0 = std::chrono::steady_clock::now();
+        if (poolDevice >= 0 && !paired) {
+            pool.reset(new DevicePool());
+            if (kasa_parse_create(poolDevice, (uint64_t)kLongSequence, &pool->ps)) throwLast();
+            devParse = true;
+        }
         if (paired) {
             // paired-end (Read.hpp:834-1049): mate r of both files forms read r; the two sequences stay separate (no k-mer
             // spans the junction) but score into one row; specifier = both names, length = the sum
@@ -1140,8 +1161,56 @@ struct Batcher {
             pending.bases.reserve(left / 2 + left / 8 + 1024); pending.nameBlob.reserve(left / 8 + 1024);
             pending.nameOff.reserve(left / 160 + 17); pending.lengths.reserve(left / 160 + 16); pending.off.reserve(left / 160 + 17);
         }
+        if (devParse && refillDevice(chunk, chunkBytes)) return;
         parsePiece(chunk, chunkBytes, reader->fasta, p.threads, 1u << 20, pending, parts, reader->chunkStart);
     }
+    // --device-parse: the chunk's reads go behind those of the device's pool; what the batch cut and the text stage need of
+    // them (lengths, names, offsets: some 60 bytes a read) comes back, the letters stay.  false: the chunk is not in the form
+    // the device takes -- the pooled reads come to the host with their letters and the host parser has the rest of the file.
+    bool refillDevice(const char *chunk, size_t chunkBytes)
+    {
+        std::lock_guard<std::mutex> lk(pool->mu);
+        kasa_parser *ps = pool->ps;
+        static const bool staged = getenv("KASA_PARSE_STAGE") && string(getenv("KASA_PARSE_STAGE")) == "pinned";
+        const char *text = chunk;
+        if (staged) {
+            ScopedTimer tm(g_ht.uploadText);
+            pool->stage.resize(chunkBytes);
+            parCopy(pool->stage.data(), chunk, chunkBytes, p.threads);
+            text = pool->stage.data();
+        }
+        uint64_t before = 0, added = 0; int parsable = 0;
+        double up0 = 0, ps0 = 0, up1 = 0, ps1 = 0;
+        if (kasa_parse_sizes(ps, &before, nullptr, nullptr) || kasa_parse_stage_ms(ps, &up0, &ps0)) throwLast();
+        if (kasa_parse_append(ps, text, chunkBytes, reader->fasta ? 1 : 0, &added, &parsable)) throwLast();
+        if (kasa_parse_stage_ms(ps, &up1, &ps1)) throwLast();
+        g_ht.uploadText += (up1 - up0) * 1e-3; g_ht.deviceParse += (ps1 - ps0) * 1e-3;
+        const size_t r0 = pending.size();
+        if (before - pool->outstanding != r0 - pendPos) throw std::runtime_error("--device-parse: the pool and the pending reads disagree");
+        if (!parsable) {
+            int code = 0; uint64_t at = 0;
+            (void)kasa_parse_status(ps, &code, &at);
+            if (p.verbose) std::cout << "OUT: --device-parse: the host parser takes over from byte " << reader->chunkStart + at << " (" << kasa_parse_status_text(code) << ")" << std::endl;
+            if (pendPos > 0) { ReadSet rest = pending.slice(pendPos, pending.size(), 1, p.threads); pending = std::move(rest); pendPos = 0; }
+            const size_t n = pending.size();
+            pending.bases.resize((size_t)pending.off[n]);
+            if (n && kasa_parse_fetch(ps, pool->outstanding, n, nullptr, nullptr, nullptr, nullptr, pending.bases.data())) throwLast();
+            pending.devBases = false; devParse = false;
+            return false;
+        }
+        ScopedTimer tm(g_ht.deviceParse);
+        pending.devBases = true; pending.fasta = reader->fasta;
+        const size_t n0 = pending.nameBlob.size(); const int64_t b0 = pending.off[r0];
+        pending.lengths.resize(r0 + added); pending.nameOff.resize(r0 + added + 1); pending.off.resize(r0 + added + 1);
+        if (kasa_parse_fetch(ps, before, added, pending.lengths.data() + r0, pending.nameOff.data() + r0, nullptr, pending.off.data() + r0, nullptr)) throwLast();
+        const uint64_t nameBytes = pending.nameOff[r0 + added];
+        for (size_t i = 0; i <= added; ++i) { pending.nameOff[r0 + i] += n0; pending.off[r0 + i] += b0; }
+        pending.nameBlob.resize(n0 + nameBytes);
+        if (nameBytes && kasa_parse_fetch(ps, before, added, nullptr, nullptr, pending.nameBlob.data() + n0, nullptr, nullptr)) throwLast();
+        return true;
+    }
+    // a batch whose letters lie in the pool: its reads are the next ones there that no batch has claimed
+    void claim(Batch &b) { if (!b.rs.devBases || b.rs.size() == 0) return; std::lock_guard<std::mutex> lk(pool->mu); b.pool = pool.get(); pool->outstanding += b.rs.size(); }
     // What the first batch will need on the device, from the reads parsed so far and the size of the file: the device buffers
     // are allocated while the rest of the input is parsed (kasa_ctx_reserve).
     void estimateFirstBatch(uint64_t &nQueries, uint64_t &nBases) const
@@ -1339,6 +1408,7 @@ struct Batcher {
                 if (paired) { b.segRead.resize(2 * m); for (size_t x = 0; x < m; ++x) b.segRead[2 * x] = b.segRead[2 * x + 1] = (uint32_t)x; }
                 pendPos = r;
             }
+            if (pool) claim(b);
         }
         if (useRef && deviceFull && !p.allowDeviceSplit)
             // per-read scores are float sums whose order depends on the reads that share a batch (Compare.hpp:528-530): a batch cut
@@ -1519,7 +1589,8 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
     const uint64_t nr = b.rs.size();
     {
         ScopedTimerMt tm(g_ht.upload, g_ht.mu);
-        if (b.segRead.empty()) { if (kasa_batch_upload(ctx, b.rs.bases.data(), b.rs.off.data(), (int64_t)nr)) throwLast(); }
+        if (b.pool) { std::lock_guard<std::mutex> lk(b.pool->mu); if (kasa_parse_take(b.pool->ps, ctx, nr)) throwLast(); b.pool->outstanding -= nr; }
+        else if (b.segRead.empty()) { if (kasa_batch_upload(ctx, b.rs.bases.data(), b.rs.off.data(), (int64_t)nr)) throwLast(); }
         else if (kasa_batch_upload_segments(ctx, b.rs.bases.data(), b.rs.off.data(), (int64_t)b.segRead.size(), b.segRead.data(), (int64_t)nr)) throwLast();
     }
     uint64_t nk = 0;
@@ -1797,7 +1868,15 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     std::thread textPrep;
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joinTextPrep{textPrep};
     if (!p.rtt.empty() && !p.hostRank && !p.hostText) textPrep = std::thread([&wbs, &p] { try { for (size_t i = 0; i < wbs.size(); ++i) { (void)kasa_thread_device(p.devices[i]); wbs[i].prepareText(); } } catch (...) {} });   // (a fresh thread stands on device 0: the buffers are page-locked for the worker's device)   // (what is missing is made, or fails, when a worker needs it)
-    Batcher batcher(p, ixf, wantRows, maxKmersPerBatch);
+    // --device-parse: single-end input on one device slot; the other combinations keep the host parser and give the same bytes
+    int poolDevice = -1;
+    if (p.deviceParse) {
+        const char *why = !p.input2.empty() ? "paired-end input" : p.filter ? "--filter writes the reads back from host memory" : p.coherence ? "--coherence"
+                          : (nDev > 1 || !ixf.spread.empty()) ? "more than one device slot" : nullptr;
+        if (!why) poolDevice = p.devices[(size_t)devSlots[0]];
+        else if (p.verbose) std::cout << "OUT: --device-parse: the host parser is used (" << why << ")" << std::endl;
+    }
+    Batcher batcher(p, ixf, wantRows, maxKmersPerBatch, poolDevice);
     mark("first chunk parsed");
     p.protein = batcher.protein;
     for (auto *c : ctx) if (kasa_ctx_set_protein(c, p.protein ? 1 : 0)) throwLast();
@@ -1949,7 +2028,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     mark("profile written");
     if (p.verbose && g_ht.on)
         std::cout << "OUT: host timing: read " << g_ht.read << " s, cut " << g_ht.cut << " s, parse " << g_ht.parse << " s, merge " << g_ht.merge
-                  << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
+                  << " s, upload-text " << g_ht.uploadText << " s, device-parse " << g_ht.deviceParse << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
                   << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s" << std::endl;
     if (p.verbose && g_ht.on && p.coherence) {                   // (every call of the step returns with the device idle: host clock = device time + launches)
         std::cout << "OUT: coherence: " << g_ht.coherence << " s";
@@ -2063,6 +2142,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         }
         else if (key == "ErrorThreshold") opt("--errorThreshold", val);
         else if (key == "Gzip") flag("--gzip", val);
+        else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
     }
     vector<string> out = {exe, mode};
     if (!kH.empty() && !kL.empty()) { out.push_back("-k"); out.push_back(kH); out.push_back(kL); }
@@ -2760,6 +2840,39 @@ static int run(int argc, char **argv)
                        << " cut " << g_ht.cut << " parse " << g_ht.parse << " merge " << g_ht.merge << "\n";
         return 0;
     }
+    if (argc >= 4 && a[1] == "parse-dump-device") {              // test tap: parse-dump's streamed half with the reads coming out of the device's pool
+        const unsigned nt = (unsigned)std::stoul(a[3]);
+        ChunkReader cr(a[2]);
+        const char *chunk; size_t chunkBytes; ReadSet all; vector<ReadSet> parts;
+        kasa_parser *ps = nullptr;
+        if (kasa_parse_create(0, (uint64_t)kLongSequence, &ps)) throwLast();
+        struct Guard { kasa_parser *p; ~Guard() { kasa_parse_destroy(p); } } guard{ps};
+        bool onDevice = true;
+        auto drainPool = [&] {                                   // the pooled reads behind those dumped so far
+            uint64_t n = 0, nb = 0, nn = 0;
+            if (kasa_parse_sizes(ps, &n, &nb, &nn)) throwLast();
+            ReadSet q; q.lengths.resize(n); q.nameOff.resize(n + 1); q.off.resize(n + 1); q.nameBlob.resize(nn); q.bases.resize(nb);
+            if (kasa_parse_fetch(ps, 0, n, q.lengths.data(), q.nameOff.data(), q.nameBlob.data(), q.off.data(), q.bases.data())) throwLast();
+            all.appendSet(q, nt);
+        };
+        while (cr.next(chunk, chunkBytes, false)) {
+            uint64_t added = 0; int parsable = 0;
+            if (onDevice) {
+                if (kasa_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, &added, &parsable)) throwLast();
+                if (parsable) continue;
+                drainPool(); onDevice = false;                     // as the driver does: the host parser has the rest of the file
+            }
+            parsePiece(chunk, chunkBytes, cr.fasta, nt, 1u << 20, all, parts, cr.chunkStart);
+        }
+        if (onDevice) drainPool();
+        std::cout << "protein=" << cr.protein << " fasta=" << cr.fasta << "\n";
+        for (size_t r = 0; r < all.size(); ++r) {
+            std::cout << all.name(r) << "\t" << all.lengths[r] << "\t";
+            std::cout.write((const char *)all.bases.data() + all.off[r], all.off[r + 1] - all.off[r]);
+            std::cout << "\n";
+        }
+        return 0;
+    }
     if (argc >= 6 && a[1] == "pieces-dump") {                    // test tap: the pieces of every long record -- <file> <threads> <frames> <K> (no device involved)
         const unsigned nt = (unsigned)std::stoul(a[3]);
         ChunkReader cr(a[2]);
@@ -2836,6 +2949,7 @@ static int run(int argc, char **argv)
         else if (s == "-t" || s == "--temp" || s == "-x" || s == "--callidx") next();
         else if (s == "--host-rank") p.hostRank = true;
         else if (s == "--host-text") p.hostText = true;
+        else if (s == "--device-parse") p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());

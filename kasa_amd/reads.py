@@ -246,6 +246,47 @@ def parse_reads(path: str) -> ReadBatch:
     return ReadBatch(bases, off, names, np.asarray(lens, dtype=np.uint32), detect_protein(data), layout=layout, fasta=first == b">")
 
 
+def parse_reads_device(path: str, device: int = 0, chunk_bytes: int = 0) -> ReadBatch:
+    """`parse_reads` with the parsing done on the device (capi.Parser) and the reads fetched back: for tests and small hosts.
+    chunk_bytes > 0 hands the text over in chunks of about that size, cut at record starts.  Input the device parser does
+    not take (malformed records, sequences long enough to be read in pieces) raises RuntimeError: `parse_reads` handles it."""
+    from . import capi
+    with _open(path) as f:
+        data = f.read()
+    if not data:
+        return ReadBatch(np.zeros(0, np.uint8), np.zeros(1, np.int64), [], np.zeros(0, np.uint32))
+    first = data[:1]
+    if first not in (b">", b"@"):
+        raise RuntimeError("Input does not start with @ or >.")
+    fasta = first == b">"
+    cuts = [0]
+    if chunk_bytes > 0:
+        lines = data.split(b"\n")
+        pos, starts = 0, []
+        for i, ln in enumerate(lines):
+            # a record start: FASTA a '>' line; FASTQ every fourth line (the device parser's own strict form)
+            if (ln.startswith(b">") if fasta else i % 4 == 0) and pos < len(data):
+                starts.append(pos)
+            pos += len(ln) + 1
+        for s in starts:
+            if s - cuts[-1] >= chunk_bytes:
+                cuts.append(s)
+    cuts.append(len(data))
+    parser = capi.Parser(device, LONG_SEQUENCE)
+    try:
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            _, ok = parser.append(data[a:b], fasta)
+            if not ok:
+                code, text, at = parser.status()
+                raise RuntimeError(f"not device-parsable: {text} (line at byte {a + at})")
+        lengths, name_off, names, off, bases = parser.fetch()
+    finally:
+        parser.close()
+    blob = names.tobytes().decode("latin-1")
+    name_list = [blob[int(name_off[r]):int(name_off[r + 1])] for r in range(lengths.shape[0])]
+    return ReadBatch(bases, off, name_list, lengths, detect_protein(data), fasta=fasta)
+
+
 def parse_pairs(path1: str, path2: str) -> ReadBatch:
     """-1 <file> -2 <file>: mate i of both files forms read i (Read.hpp:834-1049).  Both sequences keep their own
     k-mers under one read id; the specifier is both names (each with its trailing space), the length the sum."""

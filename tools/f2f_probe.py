@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""File-to-file timing of the C++ driver with the host-side breakdown (KASA_HOST_TIMING=1): python tools/f2f_probe.py [reads] [-m GiB ...]"""
+"""File-to-file timing of the C++ driver with the host-side breakdown (KASA_HOST_TIMING=1): python tools/f2f_probe.py [reads] [-m GiB ...] [--device-parse]"""
 import os, subprocess, sys, tempfile, shutil, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -8,8 +8,10 @@ from kasa_amd import build, formats, synth
 import bench
 
 class A: pass
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-mems = [int(x) for x in sys.argv[2:]] or [1024, 12]
+extra = [x for x in sys.argv[1:] if x == "--device-parse"]         # handed on to the driver
+argv = [x for x in sys.argv[1:] if x not in extra]
+n = int(argv[0]) if argv else 10_000_000
+mems = [int(x) for x in argv[1:]] or [1024, 12]
 g = synth.genomes(1400, 300_000, seed=11)
 ix = synth.index_from_genomes(g)
 reads = synth.reads_from_genomes(g, n, 150, seed=1000)
@@ -37,13 +39,13 @@ for m in mems:
         nlist = os.environ.get("F2F_THREADS", "")
         for threads in ([["-n", x] for x in nlist.split(",")] if nlist else ([] if m != mems[0] else [["-n", "16"]]) + [[]]):
             cmd = [build.build_host(), "identify", "-c", os.path.join(d, "content.txt"), "-d", os.path.join(d, "idx"), "-i", os.path.join(d, "reads.fastq"),
-                   "-q", os.path.join(d, "out.jsonl"), "-p", os.path.join(d, "prof.csv"), "--jsonl", "-v", "-m", str(m)] + threads
+                   "-q", os.path.join(d, "out.jsonl"), "-p", os.path.join(d, "prof.csv"), "--jsonl", "-v", "-m", str(m)] + threads + extra
             for name in ("out.jsonl", "prof.csv"):
                 try: os.unlink(os.path.join(d, name))
                 except OSError: pass
             t0 = time.perf_counter()
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-            print("== -m", m, " ".join(threads), "wall %.2f s" % (time.perf_counter() - t0))
+            print("== -m", m, " ".join(threads + extra), "wall %.2f s" % (time.perf_counter() - t0))
             print("\n".join(l for l in r.stdout.splitlines() if l.startswith("OUT: Time") or "host timing" in l or "device stages" in l or l.startswith("ERROR") or (l.startswith("kasa:") and not os.environ.get("F2F_QUIET"))), flush=True)
     finally:
         shutil.rmtree(d, ignore_errors=True)
