@@ -6,7 +6,7 @@ INDEX  = kasa_amd/host/kasa_index
 
 all: $(LIB) $(HOST) $(INDEX) oracle
 
-$(LIB): kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp kasa_amd/csrc/stdsort_order.h kasa_amd/csrc/kasa_radix.h kasa_amd/csrc/kasa_text.h kasa_amd/csrc/kasa_replay.h kasa_amd/csrc/kasa_build.h kasa_amd/csrc/kasa_edit.h kasa_amd/csrc/kasa_parse.h kasa_amd/host/grisu_powers.inc include/kasa_hip.h
+$(LIB): kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp kasa_amd/csrc/stdsort_order.h kasa_amd/csrc/kasa_radix.h kasa_amd/csrc/kasa_text.h kasa_amd/csrc/kasa_replay.h kasa_amd/csrc/kasa_build.h kasa_amd/csrc/kasa_edit.h kasa_amd/csrc/kasa_parse.h kasa_amd/csrc/kasa_bgzf.h kasa_amd/host/grisu_powers.inc include/kasa_hip.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wall -Wno-unused-result -o $@ kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp -ldl -Wl,-rpath,/opt/rocm/lib
 
 $(HOST): kasa_amd/host/kasa_identify.cpp kasa_amd/host/grisu_powers.inc include/kasa_hip.h $(LIB)

@@ -325,6 +325,22 @@ int kasa_batch_text_fetch_range(kasa_ctx *ctx, char *text, uint64_t offset, uint
 /* Test tap: the reference's double -> text (dToStr.h) as the device writes it; out = 32 bytes per value, zero-terminated. */
 int kasa_text_dtoa(int device, const double *values, uint32_t n, char *out);
 
+/* The same text compressed on the device (ours: the reference's --gzip covers the --filter files only): a BGZF stream, the
+ * blocked gzip of htslib / bgzip that gzip -d, zcat and every gzip reader take.  Block i covers the text's bytes
+ * [i 65280, (i + 1) 65280) and is one complete gzip member: header 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, the subfield
+ * 'B' 'C' 02 00 BSIZE (member length - 1), one raw deflate stream with BFINAL = 1 in RFC 1951's fixed Huffman code -- or
+ * stored, when that is not smaller -- then CRC-32 and ISIZE.  A member has at most 65536 bytes; the same text gives the same
+ * bytes on every run.  The stream has NO end-of-file block (28 bytes, the same for every file): whoever closes the file
+ * appends it.  The text itself stays where it is: kasa_batch_text_fetch* deliver it afterwards as before.
+ *   kasa_batch_bgzf              after kasa_batch_text: the same text as a BGZF stream; *nBytes its length, *nBlocks its members
+ *                                (an empty text: 0 and 0).  KASA_E_STATE without a text of this batch.
+ *   kasa_batch_bgzf_fetch_range  dst[nBytes] = stream[offset .. offset + nBytes): any offset, any length inside the stream
+ *                                (pieces need not end with a member).  KASA_E_STATE without a stream of this batch's text. */
+int kasa_batch_bgzf(kasa_ctx *ctx, uint64_t *nBytes, uint64_t *nBlocks);
+int kasa_batch_bgzf_fetch_range(kasa_ctx *ctx, void *dst, uint64_t offset, uint64_t nBytes);
+/* Test tap (like kasa_text_dtoa): n host bytes through the same kernels; *nOut = stream length, KASA_E_LIMIT when dstCap is too small. */
+int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut);
+
 /* Page-locked host memory for buffers that cross PCIe (reads in, ranked hits or CSR out).  NULL when it cannot be had. */
 void *kasa_host_alloc(size_t bytes);
 void kasa_host_free(void *p);

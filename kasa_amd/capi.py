@@ -39,6 +39,7 @@ EXPORTS = [
     "kasa_encode_group_reads",
     "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
+    "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate",
 ]
 
 
@@ -339,6 +340,17 @@ def device_dtoa(values, device: int = 0):
     out = np.zeros(v.shape[0] * 32, dtype=np.uint8)
     _check(lib().kasa_text_dtoa(C.c_int(device), _p(v), C.c_uint32(v.shape[0]), _p(out)))
     return [bytes(out[i * 32:(i + 1) * 32]).split(b"\0", 1)[0].decode("ascii") for i in range(v.shape[0])]
+
+
+def bgzf_deflate(device: int, data) -> bytes:
+    """`data` as a BGZF stream made by the DEVICE (kasa_bgzf_deflate, the kernels of kasa_batch_bgzf); no EOF block."""
+    src = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = int(src.shape[0])
+    cap = n + 31 * ((n + 65279) // 65280)                        # every block stored: 18 + 5 + 8 bytes around it
+    out = np.empty(max(1, cap), dtype=np.uint8)
+    got = C.c_uint64(0)
+    _check(lib().kasa_bgzf_deflate(C.c_int(device), _p(src) if n else None, C.c_uint64(n), _p(out), C.c_uint64(cap), C.byref(got)))
+    return out[:got.value].tobytes()
 
 
 def pinned_empty(n: int, dtype) -> np.ndarray:
@@ -884,6 +896,18 @@ class Context:
                 k = min(step, n.value - a)
                 _check(lib().kasa_batch_text_fetch_range(self.h, C.c_void_p(buf.ctypes.data + a), C.c_uint64(a), C.c_uint64(k)))
         return buf[:n.value].tobytes(), offs, flags[:self.n_reads]
+
+    def batch_bgzf(self, piece: int = 0) -> bytes:
+        """kasa_batch_bgzf + fetch: the text of the last text() as a BGZF stream (no EOF block).  piece > 0: fetched in ranges
+        of that many bytes (kasa_batch_bgzf_fetch_range takes any offset and length)."""
+        n, nb = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_batch_bgzf(self.h, C.byref(n), C.byref(nb)))
+        buf = np.empty(max(1, n.value), dtype=np.uint8)
+        step = int(piece) if piece and piece > 0 else max(1, n.value)
+        for a in range(0, n.value, step):
+            k = min(step, n.value - a)
+            _check(lib().kasa_batch_bgzf_fetch_range(self.h, C.c_void_p(buf.ctypes.data + a), C.c_uint64(a), C.c_uint64(k)))
+        return buf[:n.value].tobytes()
 
     def coherence(self) -> np.ndarray:
         """--coherence scores of the batch (Compare::postProcess): float32[n_reads].  Raises where the reference throws."""

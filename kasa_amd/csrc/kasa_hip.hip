@@ -46,6 +46,7 @@
 #include "stdsort_order.h"
 #include "kasa_radix.h"
 #include "kasa_text.h"
+#include "kasa_bgzf.h"
 
 // ------------------------------------------------------------------------------------------------
 // constants
@@ -597,6 +598,8 @@ struct kasa_ctx {
     bool haveTaxText = false;
     DevBuf txtNames, txtNameOff, txtLen, txtBest, txtBytes, txtOff, txtOut, txtFlags;   // kasa_batch_text
     uint64_t txtTotal = 0; bool txtValid = false;
+    DevBuf bgzMembers, bgzSize, bgzOff, bgzOut;                // kasa_batch_bgzf: members at their stride (a chunk of blocks), u64 sizes and offsets, the stream
+    uint64_t bgzTotal = 0; bool bgzValid = false;              // ... of the text that is valid now (kasa_batch_text forgets it)
     const float *cohScores = nullptr;                          // device: the scores of the last kasa_batch_coherence of this batch
     const void *cohKey = nullptr; bool cohBegun = false;       // kasa_batch_coherence_begin handed this batch's k-mers (cohKey) and depth bytes out; _finish not yet
     bool grouped = false; uint32_t poolUsed = 1; // event records + pool of this batch are in place (group stage or import)
@@ -669,7 +672,7 @@ struct kasa_ctx {
                 &gwin, &touched, &fbList, &fastScratch, &profKeys, &profSorted, &profSorted2, &rowPos, &rowLen, &rowKey, &rowOff, &st, &cntAllMid, &outTax,
                 &outScore, &cntUnique, &cntTotal, &cntAllHi, &cntAllLo, &rawOff, &cohLen, &cohState, &sortBig, &rankDen, &rankClass, &rankMeta, &rankOut,
                 &rankList, &rankScratch, &scanTmp, &taxText, &taxTextOff, &taxTextIds, &txtNames, &txtNameOff, &txtLen, &txtBest, &txtBytes, &txtOff, &txtOut,
-                &txtFlags, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
+                &txtFlags, &bgzMembers, &bgzSize, &bgzOff, &bgzOut, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
                 &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn};
     }
 };
@@ -7601,7 +7604,7 @@ extern "C" int kasa_batch_text(kasa_ctx *c, const kasa_text_params *tp, uint64_t
     if (tp->coherence && !c->cohScores) return fail(KASA_E_STATE, "kasa_batch_text: no coherence scores of this batch (kasa_batch_coherence)");
     HIPCHK(hipSetDevice(c->ix->device));
     const uint32_t nReads = (uint32_t)c->nReads;
-    *nBytes = 0; c->txtTotal = 0; c->txtValid = false;
+    *nBytes = 0; c->txtTotal = 0; c->txtValid = false; c->bgzValid = false;
     if (nReads == 0) { c->txtValid = true; return KASA_OK; }
     if (tp->readNameOff[0] != 0) return fail(KASA_E_ARG, "kasa_batch_text: readNameOff does not start at 0");
     for (uint32_t r = 0; r < nReads; ++r)
@@ -7685,6 +7688,89 @@ extern "C" int kasa_text_dtoa(int device, const double *values, uint32_t n, char
     if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 32, hipMemcpyDeviceToHost);
     (void)hipFree(dv); (void)hipFree(dout);
     if (e != hipSuccess) return fail(KASA_E_HIP, hipGetErrorString(e));
+    return KASA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same text as a BGZF stream (kasa_bgzf.h)
+// ------------------------------------------------------------------------------------------------
+// n bytes at `text` (device, 16-byte aligned) -> *total bytes in `out`.  The members of a chunk of blocks are made at their
+// stride, their sizes are scanned behind the chunks before, and they are packed: the scratch is one chunk's whatever the
+// text's length, the stream's buffer is sized for the worst case (every block stored) before the first kernel runs.
+static constexpr uint64_t BGZF_CHUNK_BLOCKS = 4096;              // 256 MiB of members at a time
+static int bgzf_stream(const char *who, const uint8_t *text, uint64_t n, DevBuf &members, DevBuf &size, DevBuf &off, DevBuf &scanTmp, DevBuf &out, hipStream_t stream, uint64_t *total, uint64_t *nBlocks)
+{
+    using namespace kasa_bgzf;
+    *total = 0;
+    const uint64_t nBlk = (n + BLOCK_IN - 1) / BLOCK_IN;
+    *nBlocks = nBlk;
+    if (nBlk == 0) return KASA_OK;
+    if (nBlk > 0xFFFFFFFFull / 2) return fail(KASA_E_LIMIT, "%s: %llu bytes of text are more blocks than one stream takes", who, (unsigned long long)n);
+    const uint64_t chunk = std::min<uint64_t>(nBlk, BGZF_CHUNK_BLOCKS);
+    int rc;
+    if ((rc = members.reserve((size_t)chunk * STRIDE + 64)) || (rc = size.reserve((size_t)(chunk + 1) * 8)) || (rc = off.reserve((size_t)(chunk + 1) * 8)) ||
+        (rc = out.reserve((size_t)n + (size_t)nBlk * (HEADER + 5 + TRAILER) + 64)))
+        return rc;
+    size_t tmpBytes = 0;                                           // asked once, for the longest chunk: rocPRIM's need does not fall as the count grows, so it covers the shorter last one
+    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, size.as<uint64_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)chunk + 1, rocprim::plus<uint64_t>(), stream));
+    if ((rc = scanTmp.reserve(tmpBytes))) return rc;
+    uint64_t at = 0;                                               // bytes of the stream so far
+    for (uint64_t b0 = 0; b0 < nBlk; b0 += chunk) {
+        const uint64_t cnt = std::min<uint64_t>(chunk, nBlk - b0);
+        HIPCHK(hipMemsetAsync(size.p, 0, (size_t)(cnt + 1) * 8, stream));
+        deflate_kernel<<<(uint32_t)cnt, THREADS, 0, stream>>>(text + b0 * BLOCK_IN, n - b0 * BLOCK_IN, members.as<uint8_t>(), size.as<uint64_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(rocprim::exclusive_scan(scanTmp.p, tmpBytes, size.as<uint64_t>(), off.as<uint64_t>(), at, (size_t)cnt + 1, rocprim::plus<uint64_t>(), stream));
+        pack_kernel<<<(uint32_t)cnt, 256, 0, stream>>>(members.as<uint8_t>(), size.as<uint64_t>(), off.as<uint64_t>(), out.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&at, off.as<uint64_t>() + cnt, 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    *total = at;
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_bgzf(kasa_ctx *c, uint64_t *nBytes, uint64_t *nBlocks)
+{
+    if (!c || !nBytes || !nBlocks) return fail(KASA_E_ARG, "kasa_batch_bgzf: NULL argument");
+    if (!c->txtValid) return fail(KASA_E_STATE, "kasa_batch_bgzf: no text of this batch (kasa_batch_text)");
+    HIPCHK(hipSetDevice(c->ix->device));
+    *nBytes = 0; *nBlocks = 0; c->bgzValid = false; c->bgzTotal = 0;
+    int rc;
+    if ((rc = bgzf_stream("kasa_batch_bgzf", c->txtOut.as<uint8_t>(), c->txtTotal, c->bgzMembers, c->bgzSize, c->bgzOff, c->scanTmp, c->bgzOut, c->stream, &c->bgzTotal, nBlocks))) return rc;
+    c->bgzValid = true; *nBytes = c->bgzTotal;
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_bgzf_fetch_range(kasa_ctx *c, void *dst, uint64_t offset, uint64_t nBytes)
+{
+    if (!c) return fail(KASA_E_ARG, "kasa_batch_bgzf_fetch_range: NULL argument");
+    if (!c->txtValid || !c->bgzValid) return fail(KASA_E_STATE, "kasa_batch_bgzf_fetch_range: no stream of this batch's text (kasa_batch_bgzf)");
+    if (offset > c->bgzTotal || nBytes > c->bgzTotal - offset) return fail(KASA_E_ARG, "kasa_batch_bgzf_fetch_range: beyond the stream (%llu bytes)", (unsigned long long)c->bgzTotal);
+    if (nBytes && !dst) return fail(KASA_E_ARG, "kasa_batch_bgzf_fetch_range: NULL destination");
+    HIPCHK(hipSetDevice(c->ix->device));
+    if (nBytes) HIPCHK(hipMemcpyAsync(dst, c->bgzOut.as<char>() + offset, nBytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return KASA_OK;
+}
+
+// test tap: n host bytes through the same kernels
+extern "C" int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut)
+{
+    if (!nOut || (n && !src)) return fail(KASA_E_ARG, "kasa_bgzf_deflate: NULL argument");
+    *nOut = 0;
+    HIPCHK(hipSetDevice(device));
+    if (n == 0) return KASA_OK;
+    ScopedBuf text, members, size, off, scanTmp, out;
+    int rc;
+    if ((rc = text.reserve((size_t)n + 64))) return rc;
+    HIPCHK(hipMemcpy(text.p, src, n, hipMemcpyHostToDevice));
+    uint64_t total = 0, nBlocks = 0;
+    if ((rc = bgzf_stream("kasa_bgzf_deflate", text.as<uint8_t>(), n, members, size, off, scanTmp, out, nullptr, &total, &nBlocks))) return rc;
+    *nOut = total;
+    if (total > dstCap) return fail(KASA_E_LIMIT, "kasa_bgzf_deflate: the stream has %llu bytes, the destination takes %llu", (unsigned long long)total, (unsigned long long)dstCap);
+    if (!dst) return fail(KASA_E_ARG, "kasa_bgzf_deflate: NULL destination");
+    HIPCHK(hipMemcpy(dst, out.p, total, hipMemcpyDeviceToHost));
     return KASA_OK;
 }
 

@@ -287,3 +287,47 @@ def write_index_halved(ix: Index, prefix: str) -> None:
     with open(prefix + "_f.txt", "w") as f:                          # shrink copies the frequency file of the full index
         for r in range(ix.content.n_taxa):
             f.write(ix.content.names[r] + "\t" + "\t".join(str(int(v)) for v in ix.freq[r]) + "\n")
+
+
+# ---- BGZF: the per-read file of `identify --bgzf` -------------------------------------------------------------------------
+# The blocked gzip of htslib / bgzip: a multi-member .gz.  Every member holds at most BGZF_BLOCK bytes of the file, is at
+# most 65536 bytes long and says so itself in the extra subfield 'B' 'C' (BSIZE = member length - 1); the file ends with
+# the empty member BGZF_EOF.  The device makes the members (kasa_batch_bgzf); this is the host's form and the checker's.
+BGZF_BLOCK = 65280
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_members(stream: bytes):
+    """Walks a BGZF stream by BSIZE: yields (header fields, deflate payload, crc, isize) per member; header fields =
+    dict(offset, length, bsize, mtime, xfl, os, xlen, subfield).  ValueError where the stream is not BGZF."""
+    import struct
+    at = 0
+    while at < len(stream):
+        if len(stream) - at < 26:
+            raise ValueError("BGZF: %d stray bytes at %d" % (len(stream) - at, at))
+        magic, mtime, xfl, osb, xlen, sub, slen, bsize = struct.unpack_from("<4sIBBH2sHH", stream, at)
+        if magic != b"\x1f\x8b\x08\x04" or xlen != 6 or sub != b"BC" or slen != 2:
+            raise ValueError("BGZF: no member header with a BC subfield at %d" % at)
+        length = bsize + 1
+        if length < 26 or at + length > len(stream):
+            raise ValueError("BGZF: the member at %d says %d bytes, %d are there" % (at, length, len(stream) - at))
+        crc, isize = struct.unpack_from("<II", stream, at + length - 8)
+        yield (dict(offset=at, length=length, bsize=bsize, mtime=mtime, xfl=xfl, os=osb, xlen=xlen, subfield=sub),
+               stream[at + 18:at + length - 8], crc, isize)
+        at += length
+
+
+def bgzf_compress(data: bytes, level: int = 1) -> bytes:
+    """`data` as BGZF members (no EOF block) through zlib: blocks of at most BGZF_BLOCK bytes, raw deflate."""
+    import struct
+    import zlib
+    out = []
+    for a in range(0, len(data), BGZF_BLOCK):
+        block = data[a:a + BGZF_BLOCK]
+        for lv in (level, 0):                                    # level 0 = stored: always fits
+            z = zlib.compressobj(lv, zlib.DEFLATED, -15)
+            payload = z.compress(block) + z.flush()
+            if 18 + len(payload) + 8 <= 65536:
+                break
+        out.append(BGZF_EOF[:16] + struct.pack("<H", 18 + len(payload) + 8 - 1) + payload + struct.pack("<II", zlib.crc32(block), len(block)))
+    return b"".join(out)

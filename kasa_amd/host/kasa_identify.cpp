@@ -217,7 +217,7 @@ static vector<uint64_t> loadFreq(const string &prefix, size_t nTaxa, int kHigh, 
 }
 
 // KASA_HOST_TIMING=1: where the host spends the time of "Time fastq" (seconds, summed over the file)
-struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
+struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, deflate = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
 static HostTimers g_ht;
 static std::chrono::steady_clock::time_point g_t0 = std::chrono::steady_clock::now();
 static void mark(const char *what, uint64_t id = ~0ull)          // KASA_HOST_TIMING: a time line of the file's pipeline
@@ -649,6 +649,7 @@ struct Params {
     bool verbose = false, coverage = false, unique = false, protein = false;
     bool gzipOut = false;                        // --gzip: the --filter files are written through zlib (Compare.hpp:2455,3713-3731)
     bool coherence = false; float coherenceThreshold = 11.0f;   // --coherence, --coherenceThreshold (MetaHeader.h:159)
+    bool bgzf = false;                             // --bgzf: the per-read file is a BGZF stream (blocked gzip), compressed where its text is made
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
 };
 
@@ -1426,12 +1427,61 @@ struct Batcher {
     }
 };
 
+// BGZF (--bgzf): the blocked gzip of htslib / bgzip.  Every member is a complete gzip file of at most 65536 bytes that carries
+// its own length in the extra subfield 'B' 'C' (BSIZE = length - 1) and holds at most 65280 bytes of text; a file ends with
+// the empty member below.  The device makes such members of the text it writes (kasa_batch_bgzf); these are the host's:
+// zlib, raw deflate, level 1 -- for the frame, for batches whose text the host writes and for the bgzf-dump tap.
+static const size_t kBgzfBlock = 65280;
+static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static void bgzfAppend(string &out, const char *d, size_t n)    // the members of d[0 .. n) behind `out` (n = 0: none)
+{
+    unsigned char buf[65536];
+    for (size_t a = 0; a < n; a += kBgzfBlock) {
+        const size_t len = std::min(kBgzfBlock, n - a);
+        size_t payload = 0;
+        for (int level = 1;; level = 0) {                          // (level 0 = stored: 5 bytes per 65535 -- always fits)
+            z_stream zs; std::memset(&zs, 0, sizeof(zs));
+            if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("zlib could not be initialised");
+            zs.next_in = (Bytef *)(d + a); zs.avail_in = (uInt)len;
+            zs.next_out = buf + 18; zs.avail_out = (uInt)(sizeof(buf) - 18 - 8);
+            const int rc = deflate(&zs, Z_FINISH);
+            payload = (size_t)zs.total_out;
+            deflateEnd(&zs);
+            if (rc == Z_STREAM_END) break;
+            if (level == 0) throw std::runtime_error("a BGZF block could not be compressed");
+        }
+        const size_t total = 18 + payload + 8;
+        std::memcpy(buf, kBgzfEof, 16);
+        buf[16] = (unsigned char)((total - 1) & 0xff); buf[17] = (unsigned char)((total - 1) >> 8);
+        const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)(d + a), (uInt)len), isize = (uint32_t)len;
+        for (int i = 0; i < 4; ++i) { buf[18 + payload + i] = (unsigned char)(crc >> (8 * i)); buf[22 + payload + i] = (unsigned char)(isize >> (8 * i)); }
+        out.append((const char *)buf, total);
+    }
+}
+static string bgzfCompress(const string &t) { string z; z.reserve(t.size() / 3 + 64); bgzfAppend(z, t.data(), t.size()); return z; }
+// walks a stream by BSIZE: fn(member, its length, payload, payload length, crc, isize); false when a header is not BGZF's or a member is cut
+static bool bgzfMembers(const string &s, const std::function<void(const unsigned char *, size_t, const unsigned char *, size_t, uint32_t, uint32_t)> &fn)
+{
+    const unsigned char *b = (const unsigned char *)s.data();
+    for (size_t at = 0; at < s.size();) {
+        if (s.size() - at < 26 || std::memcmp(b + at, kBgzfEof, 4) != 0 || std::memcmp(b + at + 10, kBgzfEof + 10, 6) != 0) return false;
+        const size_t total = (size_t)(b[at + 16] | b[at + 17] << 8) + 1;
+        if (total < 26 || total > s.size() - at) return false;
+        uint32_t crc = 0, isize = 0;
+        for (int i = 0; i < 4; ++i) { crc |= (uint32_t)b[at + total - 8 + i] << (8 * i); isize |= (uint32_t)b[at + total - 4 + i] << (8 * i); }
+        fn(b + at, total, b + at + 18, total - 26, crc, isize);
+        at += total;
+    }
+    return true;
+}
+
 // The per-read file.  A slab of text (the reads [32768 s, 32768 (s + 1)) of a batch) gets its place in the file as soon as
 // the sizes of all slabs before it are known, and is written there by the thread that formatted it: formatting and writing
 // overlap, several threads fill the page cache at once (one thread does 2-3 GB/s; 10 M reads are 5.5 GB of JSON lines), and
 // no slab is copied into a batch-sized string first.  Slabs that arrive early wait (text of a later batch on another device).
 struct OrderedOut {
     int fd = -1; off_t pos = 0;
+    bool bgzf = false;                                          // --bgzf: what is put or parked is BGZF members (slabs arrive compressed)
     std::mutex mu;
     uint64_t curBatch = 0; size_t curSlab = 0;                  // the next slab to be placed
     // a slab: text the formatting thread made (owned), or the piece a device wrote (a view into the buffer it arrived in; `done`
@@ -1449,7 +1499,12 @@ struct OrderedOut {
     {
         while (n) { const ssize_t w = ::pwrite(fd, d, std::min<size_t>(n, (size_t)1 << 30), at); if (w <= 0) throw std::runtime_error("Readwise output file could not be written!"); d += w; n -= (size_t)w; at += w; }
     }
-    void put(const string &t) { writeAt(fd, t.data(), t.size(), pos); pos += (off_t)t.size(); }   // header / footer (nothing else in flight)
+    void put(const string &t)                                   // header / footer (nothing else in flight)
+    {
+        if (bgzf) { const string z = bgzfCompress(t); writeAt(fd, z.data(), z.size(), pos); pos += (off_t)z.size(); return; }
+        writeAt(fd, t.data(), t.size(), pos); pos += (off_t)t.size();
+    }
+    void putEof() { writeAt(fd, (const char *)kBgzfEof, sizeof(kBgzfEof), pos); pos += (off_t)sizeof(kBgzfEof); }   // BGZF's end-of-file block
     void place(vector<std::pair<off_t, Item>> &todo)               // mu held: everything that is next in line gets its offset
     {
         for (;;) {
@@ -1715,6 +1770,12 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
                 { ScopedTimerMt tm(g_ht.text, g_ht.mu); if (kasa_batch_text(ctx, &tp, &nBytes)) throwLast(); }
                 wb.flags.resize(nr);
                 if (p.filter && kasa_batch_text_fetch(ctx, nullptr, nullptr, wb.flags.data())) throwLast();
+                if (p.bgzf) {                                      // the pieces below are the stream's then: cut at any byte
+                    uint64_t zBytes = 0, zBlocks = 0;
+                    ScopedTimerMt tm(g_ht.deflate, g_ht.mu);
+                    if (kasa_batch_bgzf(ctx, &zBytes, &zBlocks)) throwLast();
+                    nBytes = zBytes;
+                }
                 const size_t nPieces = out.fd < 0 ? 0 : (size_t)((nBytes + wb.pieceBytes - 1) / wb.pieceBytes);   // (--filter without -q: only the flags)
                 out.begin(b.id, nPieces);
                 b.flaggedByDevice = 0;
@@ -1725,7 +1786,7 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
                     tText += secondsSince(tTxt);
                     const uint64_t at = (uint64_t)i * wb.pieceBytes, len = std::min<uint64_t>(wb.pieceBytes, nBytes - at);
                     if (wb.text[slot].capacity < wb.pieceBytes) wb.text[slot].resize(wb.pieceBytes);
-                    { ScopedTimerMt tm(g_ht.fetch, g_ht.mu); if (kasa_batch_text_fetch_range(ctx, wb.text[slot].data(), at, len)) throwLast(); }
+                    { ScopedTimerMt tm(g_ht.fetch, g_ht.mu); if (p.bgzf ? kasa_batch_bgzf_fetch_range(ctx, wb.text[slot].data(), at, len) : kasa_batch_text_fetch_range(ctx, wb.text[slot].data(), at, len)) throwLast(); }
                     wb.written[slot] = out.view(b.id, i, wb.text[slot].data(), (size_t)len);
                 }
                 if (p.filter) for (uint64_t r = 0; r < nr; ++r) if (wb.flags.data()[r]) b.flagged.push_back(b.firstRead + r);
@@ -1792,6 +1853,7 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
                         w.read(text, b.firstRead + r, b.rs.name(r), b.rs.lengths[r], tx.data() + ro[r], sc.data() + ro[r], ro[r + 1] - ro[r]);
                     if (p.filter && w.lastContaminated) flagged[sidx].push_back(b.firstRead + r);
                 }
+                if (p.bgzf) { ScopedTimerMt tm(g_ht.deflate, g_ht.mu); text = bgzfCompress(text); }   // by the thread that made it
                 out.submit(b.id, (size_t)sidx, std::move(text));
             }
         } catch (...) { err[t] = std::current_exception(); }
@@ -1840,6 +1902,13 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     {
         uint64_t freeB = 0, totalB = 0;
         if (kasa_device_memory(p.devices[(size_t)devSlots[0]], &freeB, &totalB)) throwLast();
+        // --bgzf: every owner slot of a device keeps kasa_batch_bgzf's member scratch there (a chunk of 4096 blocks at their
+        // stride of 64 KiB, and the allocator's sixteenth on top: a fixed amount, off the free memory first).  The stream
+        // itself is at most the text and 31 bytes a block; like the text it is not counted per query, the fifth kept free is
+        // its room, and a batch that outgrows it ends the run with the library's out-of-memory message in an ERROR: line.
+        const uint64_t bgzfScratch = p.bgzf ? (uint64_t)4096 * 65536 / 16 * 17 + (1u << 20) : 0;
+        auto lessScratch = [bgzfScratch](uint64_t freeBytes, uint64_t slots) { return freeBytes > slots * bgzfScratch ? freeBytes - slots * bgzfScratch : 0; };
+        freeB = lessScratch(freeB, (uint64_t)std::count(p.devices.begin(), p.devices.end(), p.devices[(size_t)devSlots[0]]));
         const uint64_t per = kasa_batch_bytes_per_query(ctx[0]);
         if (per) maxKmersPerBatch = std::max<uint64_t>(1u << 20, std::min<uint64_t>(maxKmersPerBatch, (uint64_t)(0.8 * (double)freeB) / per));
         if (per && !ixf.spread.empty()) {
@@ -1854,6 +1923,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
             uint64_t fit = 3000000000ull;
             for (const auto &kv : slotsOn) {
                 if (kasa_device_memory(kv.first, &freeB, &totalB)) throwLast();
+                freeB = lessScratch(freeB, kv.second);
                 const uint64_t bytesPerQuery = kv.second * (per + recBytes) + (uint64_t)p.devices.size() * per;
                 fit = std::min<uint64_t>(fit, (uint64_t)(0.8 * (double)freeB) / bytesPerQuery);
             }
@@ -1899,6 +1969,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     if (!p.rtt.empty()) {
         out.fd = ::open(p.rtt.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (out.fd < 0) throw std::runtime_error("Readwise output file could not be created!");
+        out.bgzf = p.bgzf;
         if (p.fmt == Params::Tsv) out.put(p.coherence ? "#Read number\tSpecifier from input file\tMatched taxa\tNames\tScores{relative,k-mer}\tError\tCoherence\n"
                                                       : "#Read number\tSpecifier from input file\tMatched taxa\tNames\tScores{relative,k-mer}\tError\n");
         else if (p.fmt == Params::Json) out.put("[\n");
@@ -2002,7 +2073,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     if (failure) std::rethrow_exception(failure);
     const uint64_t nReads = batcher.nextRead;
     mark("workers joined");
-    if (!p.rtt.empty()) { out.drainWriter(); out.stopWriter(); mark("writer drained"); if (p.fmt == Params::Json) out.put("\n]"); ::close(out.fd); out.fd = -1; }
+    if (!p.rtt.empty()) { out.drainWriter(); out.stopWriter(); mark("writer drained"); if (p.fmt == Params::Json) out.put("\n]"); if (p.bgzf) out.putEof(); ::close(out.fd); out.fd = -1; }
     if (p.filter) filterReads(p, contaminants);
     // profile: one RCCL all-reduce over the devices' tables, then device 0's copy
     if (!ixf.spread.empty()) {
@@ -2029,7 +2100,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     if (p.verbose && g_ht.on)
         std::cout << "OUT: host timing: read " << g_ht.read << " s, cut " << g_ht.cut << " s, parse " << g_ht.parse << " s, merge " << g_ht.merge
                   << " s, upload-text " << g_ht.uploadText << " s, device-parse " << g_ht.deviceParse << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
-                  << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s" << std::endl;
+                  << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s, deflate " << g_ht.deflate << " s" << std::endl;
     if (p.verbose && g_ht.on && p.coherence) {                   // (every call of the step returns with the device idle: host clock = device time + launches)
         std::cout << "OUT: coherence: " << g_ht.coherence << " s";
         if (ixf.nPartitions()) std::cout << " (begin " << g_ht.cohBegin << ", depth over the partitions " << g_ht.cohDepth << ", finish " << g_ht.cohFinish << ")";
@@ -2142,6 +2213,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         }
         else if (key == "ErrorThreshold") opt("--errorThreshold", val);
         else if (key == "Gzip") flag("--gzip", val);
+        else if (key == "Bgzf") flag("--bgzf", val);                                 // ours: the reference never compresses the per-read file
         else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
     }
     vector<string> out = {exe, mode};
@@ -2840,6 +2912,20 @@ static int run(int argc, char **argv)
                        << " cut " << g_ht.cut << " parse " << g_ht.parse << " merge " << g_ht.merge << "\n";
         return 0;
     }
+    if (argc >= 4 && a[1] == "bgzf-dump") {                      // test tap: the host's BGZF form of a file + the EOF block (no device involved)
+        std::ifstream in(a[2], std::ios::binary);
+        if (!in) throw std::runtime_error("Input file not found");
+        const string data((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+        string z = bgzfCompress(data);
+        z.append((const char *)kBgzfEof, sizeof(kBgzfEof));
+        size_t nMembers = 0; uint64_t covered = 0;
+        if (!bgzfMembers(z, [&](const unsigned char *, size_t, const unsigned char *, size_t, uint32_t, uint32_t isize) { ++nMembers; covered += isize; }) || covered != data.size())
+            throw std::runtime_error("the BGZF stream does not walk back to its input");
+        std::ofstream o(a[3], std::ios::binary);
+        if (!o.write(z.data(), (std::streamsize)z.size())) throw std::runtime_error("bgzf-dump: output file could not be written");
+        std::cout << data.size() << " bytes -> " << z.size() << " bytes in " << nMembers << " members" << std::endl;
+        return 0;
+    }
     if (argc >= 4 && a[1] == "parse-dump-device") {              // test tap: parse-dump's streamed half with the reads coming out of the device's pool
         const unsigned nt = (unsigned)std::stoul(a[3]);
         ChunkReader cr(a[2]);
@@ -2954,6 +3040,7 @@ static int run(int argc, char **argv)
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());
         else if (s == "--gzip") p.gzipOut = true;                                                  // main.cpp:570-572
+        else if (s == "--bgzf") p.bgzf = true;
         else if (s == "-a" || s == "--alphabet") { p.codonFile = next(); p.codonId = next(); }
         else if (s == "--coherence") p.coherence = true;                                        // main.cpp:576-581
         else if (s == "--coherenceThreshold") p.coherenceThreshold = std::stof(next());
@@ -2962,6 +3049,7 @@ static int run(int argc, char **argv)
         else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
     }
     if (p.partitionDevices && p.devicesGiven) throw std::runtime_error("--partition-devices cannot be combined with --device or --devices: its slots are the devices of the run");
+    if (p.bgzf && p.rtt.empty()) throw std::runtime_error("--bgzf compresses the per-read file: it needs -q <file>");
     if (frameFlags >= 2) throw std::runtime_error("You'll have to decide between using one, three, or six frames. Currently, more than one option was chosen. Please check your parameters!"); // main.cpp:618-620
     std::ifstream info(p.index + "_info.txt");
     if (!info) throw std::runtime_error("Info file for this index can not be found!");
