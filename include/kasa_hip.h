@@ -341,6 +341,36 @@ int kasa_batch_bgzf_fetch_range(kasa_ctx *ctx, void *dst, uint64_t offset, uint6
 /* Test tap (like kasa_text_dtoa): n host bytes through the same kernels; *nOut = stream length, KASA_E_LIMIT when dstCap is too small. */
 int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut);
 
+/* ---- BGZF in: members inflated on the device (ours: the reference reads .gz through zlib on one thread) -----------------
+ * A BGZF file is tens of thousands of deflate streams (RFC 1951: stored, fixed and dynamic blocks, any number per member)
+ * that state their own length (BSIZE) and content (ISIZE <= 65536): the host walks the headers, member i's text goes to the
+ * running sum of ISIZE before it, one wavefront inflates one member and checks its CRC-32 (kasa_amd/csrc/kasa_inflate.h).
+ * Gzip without the 'BC' subfield is one long stream and is not taken.  A malformed member is a STATUS, never a fault: every
+ * load stays inside the member's payload, every store inside its ISIZE bytes, no back-reference reaches below its first byte.
+ *   kasa_bgzf_inflate   test tap that mirrors kasa_bgzf_deflate: nBytes of host stream -> host text.  *nText = the ISIZE sum
+ *                       of the stream's whole members; KASA_E_LIMIT (nothing written) when cap is smaller.  A bad stream:
+ *                       KASA_OK with *status = the KASA_INFLATE_* code of the FIRST offending member and *member its index
+ *                       (for KASA_INFLATE_HEADER / _CUT: the number of whole members before the bytes that are none); the
+ *                       text is then not written.
+ *   kasa_inflate_status_text  names a code. */
+enum {
+    KASA_INFLATE_OK = 0,
+    KASA_INFLATE_HEADER = 1,        /* no BGZF member header (1f 8b 08 04 .. 06 00 'B' 'C' 02 00), BSIZE below 25 or ISIZE above 65536 */
+    KASA_INFLATE_CUT = 2,           /* the stream ends inside a member */
+    KASA_INFLATE_TRUNCATED = 3,     /* the deflate data end before the last block does */
+    KASA_INFLATE_BTYPE = 4,         /* block type 3 */
+    KASA_INFLATE_STORED_LEN = 5,    /* a stored block whose LEN is not the complement of NLEN */
+    KASA_INFLATE_CODE_LENGTHS = 6,  /* a code-length set that is over-subscribed, incomplete, too long or has no end-of-block code */
+    KASA_INFLATE_SYMBOL = 7,        /* a bit pattern that is no code, or a length / distance symbol outside the alphabet */
+    KASA_INFLATE_DISTANCE = 8,      /* a back-reference to before the member's first byte */
+    KASA_INFLATE_OVERRUN = 9,       /* more output than ISIZE states */
+    KASA_INFLATE_SHORT = 10,        /* less output than ISIZE states */
+    KASA_INFLATE_TRAILING = 11,     /* bytes between the last block and the trailer */
+    KASA_INFLATE_CRC = 12           /* the output's CRC-32 is not the trailer's */
+};
+int kasa_bgzf_inflate(int device, const void *stream, uint64_t nBytes, void *text, uint64_t cap, uint64_t *nText, int *status, uint64_t *member);
+const char *kasa_inflate_status_text(int code);
+
 /* Page-locked host memory for buffers that cross PCIe (reads in, ranked hits or CSR out).  NULL when it cannot be had. */
 void *kasa_host_alloc(size_t bytes);
 void kasa_host_free(void *p);
@@ -641,7 +671,8 @@ enum {
     KASA_PARSE_LONG = 7,            /* a record of longSequence letters or more */
     KASA_PARSE_FASTA_HEADER = 8,    /* a FASTA chunk that does not start with '>' */
     KASA_PARSE_FASTQ_SEQ_PLUS = 9,  /* a FASTQ sequence line that starts with '+' (the host parser takes it for the '+' line) */
-    KASA_PARSE_TOO_LARGE = 10       /* a chunk of 4 GiB or more (positions in a chunk are 32-bit) */
+    KASA_PARSE_TOO_LARGE = 10,      /* a chunk of 4 GiB or more (positions in a chunk are 32-bit) */
+    KASA_PARSE_INFLATE = 11         /* kasa_bgzf_parse_append: a member does not inflate; `at` is the member's index in the span */
 };
 typedef struct kasa_parser kasa_parser;
 int kasa_parse_create(int device, uint64_t longSequence, kasa_parser **out);
@@ -653,6 +684,25 @@ int kasa_parse_fetch(kasa_parser *p, uint64_t first, uint64_t n, uint32_t *lengt
 int kasa_parse_take(kasa_parser *p, kasa_ctx *ctx, uint64_t nReads);
 int kasa_parse_tile_bytes(void);
 int kasa_parse_stage_ms(kasa_parser *p, double *uploadMs, double *parseMs);
+/* The same pool fed with BGZF (kasa_bgzf_inflate above): a span of WHOLE members goes up compressed, is inflated into the
+ * parser's text buffer behind what the previous call carried, and the text is cut ON THE DEVICE at its last whole record --
+ * FASTQ: behind the last line feed that closes a fourth line (lines counted from the text's start: the carry begins a record),
+ * FASTA: before the last line that begins with '>' (its record may go on in the next span); final != 0: nothing is cut.  The
+ * cut text is parsed as kasa_parse_append parses a chunk, from the same line table and without a second upload; what lies
+ * behind the cut is carried: it moves to the front of the text buffer for the next call.
+ *   *nReadsAdded  reads pooled by this call; 0 with *parsable = 1 when the text holds no whole record yet (a contig that spans
+ *                 many members): everything is carried
+ *   *nTextBytes   bytes of text this call parsed (over a file they sum to its inflated size), *carryBytes what is carried now
+ *   *parsable = 0 the pool AND the carry are as before the call.  KASA_PARSE_INFLATE: a member of the span is malformed --
+ *                 kasa_bgzf_parse_status gives its KASA_INFLATE_* code and its index in the span (kasa_parse_status' `at`
+ *                 too); KASA_PARSE_TOO_LARGE: carry plus span reach 4 GiB; every other code as for kasa_parse_append, `at`
+ *                 counted in the cut text (carry included).
+ * kasa_parse_append returns KASA_E_STATE while bytes are carried.  kasa_bgzf_parse_ms: HIP-event milliseconds of the inflate
+ * kernels, summed like kasa_parse_stage_ms' two (the upload there is then the compressed bytes'). */
+int kasa_bgzf_parse_append(kasa_parser *p, const void *members, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                           uint64_t *nTextBytes, uint64_t *carryBytes);
+int kasa_bgzf_parse_status(kasa_parser *p, int *code, uint64_t *member);
+int kasa_bgzf_parse_ms(kasa_parser *p, double *inflateMs);
 void kasa_parse_destroy(kasa_parser *p);
 
 #ifdef __cplusplus

@@ -40,6 +40,7 @@ EXPORTS = [
     "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate",
+    "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
 ]
 
 
@@ -197,6 +198,12 @@ def lib():
         L.kasa_parse_tile_bytes.argtypes = []
         L.kasa_parse_stage_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_parse_destroy.argtypes = [C.c_void_p]
+        L.kasa_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_inflate_status_text.argtypes = [C.c_int]
+        L.kasa_inflate_status_text.restype = C.c_char_p
+        L.kasa_bgzf_parse_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.kasa_bgzf_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_bgzf_parse_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_parse_destroy.restype = None
         _check_runtime(L)
         _lib = L
@@ -351,6 +358,27 @@ def bgzf_deflate(device: int, data) -> bytes:
     got = C.c_uint64(0)
     _check(lib().kasa_bgzf_deflate(C.c_int(device), _p(src) if n else None, C.c_uint64(n), _p(out), C.c_uint64(cap), C.byref(got)))
     return out[:got.value].tobytes()
+
+
+def inflate_status_text(code: int) -> str:
+    return lib().kasa_inflate_status_text(C.c_int(code)).decode()
+
+
+def bgzf_inflate(device: int, stream, cap: int = None):
+    """A BGZF stream inflated by the DEVICE (kasa_bgzf_inflate): (text, status, member).  status 0: text is the bytes of all
+    members; else a KASA_INFLATE_* code, the index of the first offending member, and text is None.  cap: the destination's
+    size (default: what the members' ISIZE fields sum to); too small raises RuntimeError (KASA_E_LIMIT) and nothing is written."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = int(src.shape[0])
+    if cap is None:
+        from . import formats
+        cap = int(sum(m[5] for m in formats.bgzf_member_table(bytes(stream))[0]))
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    got, status, member = C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+    _check(lib().kasa_bgzf_inflate(C.c_int(device), _p(src) if n else None, C.c_uint64(n), _p(out), C.c_uint64(cap), C.byref(got), C.byref(status), C.byref(member)))
+    if status.value:
+        return None, int(status.value), int(member.value)
+    return out[:got.value].tobytes(), 0, 0
 
 
 def pinned_empty(n: int, dtype) -> np.ndarray:
@@ -614,6 +642,27 @@ class Parser:
         _check(lib().kasa_parse_append(self.h, _p(buf) if buf.shape[0] else None, C.c_uint64(buf.shape[0]), C.c_int(1 if fasta else 0),
                                        C.byref(n), C.byref(ok)))
         return int(n.value), bool(ok.value)
+
+    def append_bgzf(self, members: bytes, fasta: bool, final: bool = False):
+        """A span of whole BGZF members (kasa_bgzf_parse_append): inflated on the device behind the carry, cut at the last
+        whole record (final: not cut), parsed.  (reads added, parsable, text bytes parsed, bytes carried)."""
+        buf = np.frombuffer(members, dtype=np.uint8)
+        n, ok, nt, carry = C.c_uint64(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_bgzf_parse_append(self.h, _p(buf) if buf.shape[0] else None, C.c_uint64(buf.shape[0]), C.c_int(1 if fasta else 0), C.c_int(1 if final else 0),
+                                            C.byref(n), C.byref(ok), C.byref(nt), C.byref(carry)))
+        return int(n.value), bool(ok.value), int(nt.value), int(carry.value)
+
+    def inflate_status(self):
+        """(KASA_INFLATE_* code, its text, member index in the span) behind a KASA_PARSE_INFLATE refusal of append_bgzf."""
+        code, member = C.c_int(0), C.c_uint64(0)
+        _check(lib().kasa_bgzf_parse_status(self.h, C.byref(code), C.byref(member)))
+        return int(code.value), inflate_status_text(code.value), int(member.value)
+
+    def inflate_ms(self) -> float:
+        """HIP-event milliseconds of the inflate kernels, summed over append_bgzf calls."""
+        v = C.c_double(0)
+        _check(lib().kasa_bgzf_parse_ms(self.h, C.byref(v)))
+        return float(v.value)
 
     def status(self):
         """(KASA_PARSE_* code, its text, chunk position of the offending line) of the last append."""

@@ -47,6 +47,7 @@
 #include "kasa_radix.h"
 #include "kasa_text.h"
 #include "kasa_bgzf.h"
+#include "kasa_inflate.h"
 
 // ------------------------------------------------------------------------------------------------
 // constants
@@ -7772,6 +7773,65 @@ extern "C" int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *
     if (!dst) return fail(KASA_E_ARG, "kasa_bgzf_deflate: NULL destination");
     HIPCHK(hipMemcpy(dst, out.p, total, hipMemcpyDeviceToHost));
     return KASA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// BGZF in (kasa_inflate.h)
+// ------------------------------------------------------------------------------------------------
+// test tap: a host stream through walk_members and inflate_kernel
+static int bgzf_inflate_impl(int device, const uint8_t *stream, uint64_t nBytes, void *text, uint64_t cap, uint64_t *nText, int *status, uint64_t *member)
+{
+    if (!nText || !status || !member || (nBytes && !stream)) return fail(KASA_E_ARG, "kasa_bgzf_inflate: NULL argument");
+    *nText = 0; *status = KASA_INFLATE_OK; *member = 0;
+    std::vector<kasa_inflate::Member> tab;
+    uint64_t consumed = 0, total = 0;
+    int zs = kasa_inflate::walk_members(stream, nBytes, tab, &consumed, &total);
+    if (zs == KASA_INFLATE_OK && consumed != nBytes) zs = KASA_INFLATE_CUT;
+    *nText = total;
+    if (zs != KASA_INFLATE_OK) { *status = zs; *member = tab.size(); return KASA_OK; }
+    if (total > cap) return fail(KASA_E_LIMIT, "kasa_bgzf_inflate: the text has %llu bytes, the destination takes %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (tab.size() > 0x7FFFFFFFull) return fail(KASA_E_LIMIT, "kasa_bgzf_inflate: %zu members are more than one call takes", tab.size());
+    HIPCHK(hipSetDevice(device));
+    if (tab.empty()) return KASA_OK;
+    if (total && !text) return fail(KASA_E_ARG, "kasa_bgzf_inflate: NULL destination");
+    ScopedBuf dStream, dTab, dOut, dStatus;
+    int rc;
+    if ((rc = dStream.reserve((size_t)nBytes)) || (rc = dTab.reserve(tab.size() * sizeof(kasa_inflate::Member))) || (rc = dOut.reserve((size_t)total + 64)) || (rc = dStatus.reserve(8))) return rc;
+    HIPCHK(hipMemcpy(dStream.p, stream, nBytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dTab.p, tab.data(), tab.size() * sizeof(kasa_inflate::Member), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dStatus.p, 0xFF, 8));
+    kasa_inflate::inflate_kernel<<<(uint32_t)tab.size(), 64>>>(dStream.as<uint8_t>(), dTab.as<kasa_inflate::Member>(), (uint32_t)tab.size(), dOut.as<uint8_t>(), dStatus.as<unsigned long long>());
+    HIPCHK(hipGetLastError());
+    unsigned long long st = ~0ull;
+    HIPCHK(hipMemcpy(&st, dStatus.p, 8, hipMemcpyDeviceToHost));
+    if (st != ~0ull) { *status = (int)(st & 0xFF); *member = st >> 8; return KASA_OK; }
+    if (total) HIPCHK(hipMemcpy(text, dOut.p, total, hipMemcpyDeviceToHost));
+    return KASA_OK;
+}
+
+extern "C" int kasa_bgzf_inflate(int device, const void *stream, uint64_t nBytes, void *text, uint64_t cap, uint64_t *nText, int *status, uint64_t *member)
+{
+    KASA_GUARDED(bgzf_inflate_impl(device, static_cast<const uint8_t *>(stream), nBytes, text, cap, nText, status, member))
+}
+
+extern "C" const char *kasa_inflate_status_text(int code)
+{
+    switch (code) {
+    case KASA_INFLATE_OK: return "inflated";
+    case KASA_INFLATE_HEADER: return "no BGZF member header";
+    case KASA_INFLATE_CUT: return "the stream ends inside a member";
+    case KASA_INFLATE_TRUNCATED: return "the deflate data end before the last block does";
+    case KASA_INFLATE_BTYPE: return "a deflate block of type 3";
+    case KASA_INFLATE_STORED_LEN: return "a stored block whose LEN is not the complement of NLEN";
+    case KASA_INFLATE_CODE_LENGTHS: return "an invalid set of code lengths";
+    case KASA_INFLATE_SYMBOL: return "an invalid code, length symbol or distance symbol";
+    case KASA_INFLATE_DISTANCE: return "a back-reference to before the member's first byte";
+    case KASA_INFLATE_OVERRUN: return "more output than ISIZE states";
+    case KASA_INFLATE_SHORT: return "less output than ISIZE states";
+    case KASA_INFLATE_TRAILING: return "bytes between the last block and the trailer";
+    case KASA_INFLATE_CRC: return "a CRC-32 mismatch";
+    default: return "unknown";
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -210,6 +210,15 @@ __global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *_
     }
 }
 
+// the FASTA cut of kasa_bgzf_parse_append: the last line that begins with '>' as line << 32 | its start (the key grows with the line)
+__global__ void prs_last_header_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ lineStart, uint32_t nLines, uint32_t nBytes, unsigned long long *__restrict__ last)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nLines) return;
+    const uint32_t s = lineStart[i];
+    if (s < nBytes && text[s] == '>') atomicMax(last, ((unsigned long long)i << 32) | s);
+}
+
 // the reads a take left behind move to the front of the pool's other set of arrays
 template <class T> __global__ void prs_rebase_kernel(const T *__restrict__ src, T *__restrict__ dst, uint64_t n, T delta)
 {
@@ -239,6 +248,12 @@ struct kasa_parser {
     DevBuf text, tileCnt, lineStart, k1, k2, hdrLine, seqSrc, seqDst, nameSrc, nameDst, scanTmp, status;
     int lastCode = 0; uint64_t lastAt = 0;
     double msUpload = 0, msParse = 0;
+    // kasa_bgzf_parse_append: the text behind the last whole record stays at the front of `text` for the next span
+    uint64_t carry = 0;
+    DevBuf zStream, zTab, carryTmp;
+    hipEvent_t evz[2] = {nullptr, nullptr};
+    int inflateCode = 0; uint64_t inflateMember = 0;
+    double msInflate = 0;
 };
 
 namespace kasa_parse_impl {
@@ -312,10 +327,20 @@ static int refuse(kasa_parser *p, int code, uint64_t at, int *parsable)
     return KASA_OK;
 }
 
+// How the text that is on the device is cut before it is parsed (kasa_bgzf_parse_append; `cut` = nullptr: all of it, and its
+// first and last byte are known on the host).
+struct TextCut {
+    bool final = false;
+    uint64_t cutBytes = 0;                        // out: the text up to here was parsed (0 with *parsable = 0)
+};
+
+static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int lastByte, int fasta, TextCut *cut, uint64_t *nReadsAdded, int *parsable);
+
 static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fasta, uint64_t *nReadsAdded, int *parsable)
 {
     if (!p) return fail(KASA_E_ARG, "parser is NULL");
     if (nBytes && !text) return fail(KASA_E_ARG, "kasa_parse_append: text is NULL");
+    if (p->carry) return fail(KASA_E_STATE, "kasa_parse_append: %llu bytes of a BGZF span are carried (kasa_bgzf_parse_append with final set takes them)", (unsigned long long)p->carry);
     if (nReadsAdded) *nReadsAdded = 0;
     if (parsable) *parsable = 1;
     p->lastCode = KASA_PARSE_OK; p->lastAt = 0;
@@ -327,11 +352,20 @@ static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fa
     if ((rc = pool_compact(p))) return rc;
     const uint32_t nTiles = (uint32_t)((nBytes + TILE_BYTES - 1) / TILE_BYTES);
     const size_t padded = (size_t)nTiles * TILE_BYTES + 64;
-    if ((rc = p->text.reserve(padded)) || (rc = p->tileCnt.reserve(((size_t)nTiles + 1) * 4)) || (rc = p->status.reserve(64))) return rc;
+    if ((rc = p->text.reserve(padded))) return rc;
     HIPCHK(hipEventRecord(p->ev[0], p->stream));
     HIPCHK(hipMemcpyAsync(p->text.p, text, nBytes, hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemsetAsync(p->text.as<uint8_t>() + nBytes, 0, padded - nBytes, p->stream));
     HIPCHK(hipEventRecord(p->ev[1], p->stream));
+    return append_device(p, nBytes, (unsigned char)text[0], (unsigned char)text[nBytes - 1], fasta, nullptr, nReadsAdded, parsable);
+}
+
+// The text is in p->text (nBytes of it, zeros behind up to a whole tile + 64; ev[0] .. ev[1] spans how it got there).
+static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int lastByte, int fasta, TextCut *cut, uint64_t *nReadsAdded, int *parsable)
+{
+    int rc;
+    const uint32_t nTiles = (uint32_t)((nBytes + TILE_BYTES - 1) / TILE_BYTES);
+    if ((rc = p->tileCnt.reserve(((size_t)nTiles + 1) * 4)) || (rc = p->status.reserve(64))) return rc;
     HIPCHK(hipMemsetAsync(p->status.p, 0xFF, 8, p->stream));
     // ---- line table
     uint32_t *tileCnt = p->tileCnt.as<uint32_t>();
@@ -344,10 +378,15 @@ static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fa
         HIPCHK(rocprim::exclusive_scan(p->scanTmp.p, tmpBytes, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>(), p->stream));
     }
     uint32_t nFeeds = 0;
+    uint8_t ends[2] = {(uint8_t)firstByte, (uint8_t)lastByte};
     HIPCHK(hipMemcpyAsync(&nFeeds, tileCnt + nTiles, 4, hipMemcpyDeviceToHost, p->stream));
+    if (cut) {                                                                       // (nobody on the host has seen this text)
+        HIPCHK(hipMemcpyAsync(&ends[0], p->text.p, 1, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipMemcpyAsync(&ends[1], p->text.as<uint8_t>() + nBytes - 1, 1, hipMemcpyDeviceToHost, p->stream));
+    }
     HIPCHK(hipStreamSynchronize(p->stream));
-    const int trailingFeed = text[nBytes - 1] == '\n';
-    const uint32_t nLines = nFeeds + (trailingFeed ? 0u : 1u);
+    int trailingFeed = ends[1] == '\n';
+    uint32_t nLines = nFeeds + (trailingFeed ? 0u : 1u);                               // of the whole text: the line table covers all of it
     const size_t nl = (size_t)nLines + 2;
     if ((rc = p->lineStart.reserve(nl * 4)) || (rc = p->k1.reserve(nl * 8)) || (rc = p->k2.reserve(nl * 8)) || (rc = p->hdrLine.reserve(nl * 4)) ||
         (rc = p->seqSrc.reserve(nl * 4)) || (rc = p->seqDst.reserve(nl * 4)))
@@ -357,6 +396,27 @@ static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fa
     unsigned long long *status = p->status.as<unsigned long long>();
     prs_lines_kernel<<<blocks_for(nTiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint4>(), nTiles, tileCnt, lineStart, nLines, (uint32_t)nBytes, trailingFeed);
     HIPCHK(hipGetLastError());
+    if (cut && fasta && ends[0] != '>') return refuse(p, KASA_PARSE_FASTA_HEADER, 0, parsable);   // (before anything is carried: as kasa_parse_append refuses it)
+    if (cut && !cut->final) {
+        // ---- the cut, from the same line table: the parse sees lines [0, nLines) = text [0, cutBytes), which ends with a line feed
+        uint32_t useLines = 0, cutAt = 0;
+        if (!fasta) {                                                                // the last line feed that closes a fourth line
+            useLines = nFeeds & ~3u;
+            if (useLines) HIPCHK(hipMemcpyAsync(&cutAt, lineStart + useLines, 4, hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipStreamSynchronize(p->stream));
+        } else {                                                                     // the start of the last line that begins with '>'
+            unsigned long long *last = status + 1, key = 0;                          // (behind the status word)
+            HIPCHK(hipMemsetAsync(last, 0, 8, p->stream));
+            prs_last_header_kernel<<<blocks_for(nLines, 256), 256, 0, p->stream>>>(p->text.as<uint8_t>(), lineStart, nLines, (uint32_t)nBytes, last);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&key, last, 8, hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipStreamSynchronize(p->stream));
+            useLines = (uint32_t)(key >> 32); cutAt = (uint32_t)key;
+        }
+        if (useLines == 0 || cutAt == 0) return KASA_OK;                             // no whole record yet: everything is carried
+        nLines = useLines; nBytes = cutAt; trailingFeed = 1;
+    }
+    if (cut) cut->cutBytes = nBytes;
     // ---- classify
     prs_classify_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(p->text.as<uint8_t>(), lineStart, nLines, fasta, p->longSeq, k1, k2, status);
     HIPCHK(hipGetLastError());
@@ -371,7 +431,7 @@ static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fa
     HIPCHK(hipStreamSynchronize(p->stream));
     if (st != ~0ull) {                                                             // (the text went up all the same: it counts)
         float up = 0.0f;
-        if (hipEventElapsedTime(&up, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += up;
+        if (!cut && hipEventElapsedTime(&up, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += up;
         return refuse(p, (int)(st & 0xFF), st >> 8, parsable);
     }
     const uint64_t addReads = tot[0] >> 32, addBases = tot[1] >> 32, addNames = tot[1] & 0xFFFFFFFFull;
@@ -404,11 +464,84 @@ static int append_impl(kasa_parser *p, const char *text, uint64_t nBytes, int fa
     HIPCHK(hipMemcpyAsync(&st, status, 8, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += ms;
-    if (hipEventElapsedTime(&ms, p->ev[1], p->ev[2]) == hipSuccess) p->msParse += ms;
+    if (!cut && hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += ms;       // (a span's upload and inflate are counted where they happen)
+    if (hipEventElapsedTime(&ms, cut ? p->evz[1] : p->ev[1], p->ev[2]) == hipSuccess) p->msParse += ms;
     if (st != ~0ull) return refuse(p, (int)(st & 0xFF), st >> 8, parsable);         // (what was written lies behind the pool's end)
     p->nReads += addReads; p->endBase += addBases; p->endName += addNames;
     if (nReadsAdded) *nReadsAdded = addReads;
+    return KASA_OK;
+}
+
+// A span of whole BGZF members: inflated behind the carry, cut at the last whole record, parsed; what lies behind the cut is
+// the next carry.  Nothing changes -- pool, carry -- unless the span inflates cleanly and the cut text parses.
+static int append_bgzf_impl(kasa_parser *p, const uint8_t *span, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                            uint64_t *nTextBytes, uint64_t *carryBytes)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (nBytes && !span) return fail(KASA_E_ARG, "kasa_bgzf_parse_append: members is NULL");
+    if (nReadsAdded) *nReadsAdded = 0;
+    if (parsable) *parsable = 1;
+    if (nTextBytes) *nTextBytes = 0;
+    if (carryBytes) *carryBytes = p->carry;
+    p->lastCode = KASA_PARSE_OK; p->lastAt = 0; p->inflateCode = KASA_INFLATE_OK; p->inflateMember = 0;
+    std::vector<kasa_inflate::Member> tab;
+    uint64_t consumed = 0, nText = 0;
+    int zs = kasa_inflate::walk_members(span, nBytes, tab, &consumed, &nText);
+    if (zs == KASA_INFLATE_OK && consumed != nBytes) zs = KASA_INFLATE_CUT;
+    if (zs != KASA_INFLATE_OK) { p->inflateCode = zs; p->inflateMember = tab.size(); return refuse(p, KASA_PARSE_INFLATE, tab.size(), parsable); }
+    if (tab.size() > 0x7FFFFFFFull) return fail(KASA_E_LIMIT, "kasa_bgzf_parse_append: %zu members are more than one call takes", tab.size());
+    const uint64_t total = p->carry + nText;
+    if (total >= MAX_CHUNK) return refuse(p, KASA_PARSE_TOO_LARGE, 0, parsable);
+    if (total == 0) return KASA_OK;
+    HIPCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = pool_compact(p))) return rc;
+    const uint32_t nTiles = (uint32_t)((total + TILE_BYTES - 1) / TILE_BYTES);
+    const size_t padded = (size_t)nTiles * TILE_BYTES + 64;
+    if ((rc = grow_keep(p->text, padded, p->carry, p->stream)) || (rc = p->status.reserve(64))) return rc;
+    uint8_t *text = p->text.as<uint8_t>();
+    HIPCHK(hipEventRecord(p->ev[0], p->stream));
+    HIPCHK(hipEventRecord(p->evz[0], p->stream));
+    if (!tab.empty() && nText) {
+        if ((rc = p->zStream.reserve(nBytes)) || (rc = p->zTab.reserve(tab.size() * sizeof(kasa_inflate::Member)))) return rc;
+        HIPCHK(hipMemcpyAsync(p->zStream.p, span, nBytes, hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipMemcpyAsync(p->zTab.p, tab.data(), tab.size() * sizeof(kasa_inflate::Member), hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipMemsetAsync(p->status.p, 0xFF, 8, p->stream));
+        HIPCHK(hipEventRecord(p->evz[0], p->stream));
+        kasa_inflate::inflate_kernel<<<(uint32_t)tab.size(), 64, 0, p->stream>>>(p->zStream.as<uint8_t>(), p->zTab.as<kasa_inflate::Member>(), (uint32_t)tab.size(),
+                                                                                text + p->carry, p->status.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemsetAsync(text + total, 0, padded - total, p->stream));
+    HIPCHK(hipEventRecord(p->evz[1], p->stream));
+    unsigned long long st = ~0ull;
+    if (!tab.empty() && nText) HIPCHK(hipMemcpyAsync(&st, p->status.p, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, p->ev[0], p->evz[0]) == hipSuccess) p->msUpload += ms;
+    if (hipEventElapsedTime(&ms, p->evz[0], p->evz[1]) == hipSuccess) p->msInflate += ms;
+    if (st != ~0ull) { p->inflateCode = (int)(st & 0xFF); p->inflateMember = st >> 8; return refuse(p, KASA_PARSE_INFLATE, st >> 8, parsable); }
+    TextCut cut;
+    cut.final = final != 0;
+    int ok = 1;
+    uint64_t added = 0;
+    if ((rc = append_device(p, total, 0, 0, fasta, &cut, &added, &ok))) return rc;
+    if (!ok) { if (parsable) *parsable = 0; return KASA_OK; }                      // (the carry is where it was; the text behind it is given up)
+    // ---- what lies behind the cut moves to the front
+    const uint64_t rest = total - cut.cutBytes;
+    if (rest && cut.cutBytes) {
+        if (rest <= cut.cutBytes) HIPCHK(hipMemcpyAsync(text, text + cut.cutBytes, rest, hipMemcpyDeviceToDevice, p->stream));
+        else {                                                                      // (the two ranges overlap: by way of a buffer)
+            if ((rc = p->carryTmp.reserve(rest))) return rc;
+            HIPCHK(hipMemcpyAsync(p->carryTmp.p, text + cut.cutBytes, rest, hipMemcpyDeviceToDevice, p->stream));
+            HIPCHK(hipMemcpyAsync(text, p->carryTmp.p, rest, hipMemcpyDeviceToDevice, p->stream));
+        }
+        HIPCHK(hipStreamSynchronize(p->stream));
+    }
+    p->carry = rest;
+    if (nReadsAdded) *nReadsAdded = added;
+    if (nTextBytes) *nTextBytes = cut.cutBytes;
+    if (carryBytes) *carryBytes = rest;
     return KASA_OK;
 }
 
@@ -483,6 +616,7 @@ static int parse_create_impl(int device, uint64_t longSequence, kasa_parser **ou
     p->device = device; p->longSeq = longSequence;
     HIPCHK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     for (hipEvent_t &e : p->ev) HIPCHK(hipEventCreate(&e));
+    for (hipEvent_t &e : p->evz) HIPCHK(hipEventCreate(&e));
     for (kasa_parse_impl::PoolArrays &a : p->arrays) {                  // off[0] = nameOff[0] = 0
         int rc;
         if ((rc = a.off.reserve(8)) || (rc = a.nameOff.reserve(8))) return rc;
@@ -502,6 +636,7 @@ extern "C" void kasa_parse_destroy(kasa_parser *p)
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->evz) if (e) (void)hipEventDestroy(e);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -509,6 +644,27 @@ extern "C" void kasa_parse_destroy(kasa_parser *p)
 extern "C" int kasa_parse_append(kasa_parser *p, const char *text, uint64_t nBytes, int fasta, uint64_t *nReadsAdded, int *parsable)
 {
     KASA_GUARDED(kasa_parse_impl::append_impl(p, text, nBytes, fasta, nReadsAdded, parsable))
+}
+
+extern "C" int kasa_bgzf_parse_append(kasa_parser *p, const void *members, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                                      uint64_t *nTextBytes, uint64_t *carryBytes)
+{
+    KASA_GUARDED(kasa_parse_impl::append_bgzf_impl(p, static_cast<const uint8_t *>(members), nBytes, fasta, final, nReadsAdded, parsable, nTextBytes, carryBytes))
+}
+
+extern "C" int kasa_bgzf_parse_status(kasa_parser *p, int *code, uint64_t *member)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (code) *code = p->inflateCode;
+    if (member) *member = p->inflateMember;
+    return KASA_OK;
+}
+
+extern "C" int kasa_bgzf_parse_ms(kasa_parser *p, double *inflateMs)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (inflateMs) *inflateMs = p->msInflate;
+    return KASA_OK;
 }
 
 extern "C" int kasa_parse_status(kasa_parser *p, int *code, uint64_t *at)
@@ -533,6 +689,7 @@ extern "C" const char *kasa_parse_status_text(int code)
     case KASA_PARSE_FASTA_HEADER: return "a FASTA chunk does not start with '>'";
     case KASA_PARSE_FASTQ_SEQ_PLUS: return "a FASTQ sequence line starts with '+'";
     case KASA_PARSE_TOO_LARGE: return "a chunk of 4 GiB or more";
+    case KASA_PARSE_INFLATE: return "a BGZF member that does not inflate";
     default: return "unknown";
     }
 }

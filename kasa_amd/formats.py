@@ -317,6 +317,50 @@ def bgzf_members(stream: bytes):
         at += length
 
 
+def bgzf_member_table(stream: bytes):
+    """The member walk of the device inflater (walk_members in csrc/kasa_inflate.h), stated in Python: (rows, consumed, status).
+    One row per WHOLE member: (offset, length, payload offset, payload length, crc, isize, text offset) -- text offset = the
+    ISIZE sum of the members before it, which is where the device writes the member's text.  The walk stops at a cut member
+    (consumed < len(stream), status 0) and at bytes that are no BGZF member header, a BSIZE below 25 or an ISIZE above 65536
+    (status 1 = KASA_INFLATE_HEADER); a cut header is judged by the bytes that are there."""
+    import struct
+    magic, extra = b"\x1f\x8b\x08\x04", b"\x06\x00BC\x02\x00"
+    rows, at, text = [], 0, 0
+    while at < len(stream):
+        left = len(stream) - at
+        if stream[at:at + 4] != magic[:min(4, left)] or (left > 10 and stream[at + 10:at + 16] != extra[:min(6, left - 10)]):
+            return rows, at, 1
+        if left < 18:
+            break
+        length = struct.unpack_from("<H", stream, at + 16)[0] + 1
+        if length < 26:
+            return rows, at, 1
+        if length > left:
+            break
+        crc, isize = struct.unpack_from("<II", stream, at + length - 8)
+        if isize > 65536:
+            return rows, at, 1
+        rows.append((at, length, at + 18, length - 26, crc, isize, text))
+        text += isize
+        at += length
+    return rows, at, 0
+
+
+def record_cut(text: bytes, fasta: bool, final: bool = False) -> int:
+    """Where kasa_bgzf_parse_append cuts a text that starts at a record: everything before the cut is whole records, the
+    rest is carried into the next span.  FASTQ: behind the last line feed that closes a fourth line (lines are counted from
+    the text's start, so a quality line that begins with '@' cuts nothing); FASTA: before the last line that begins with '>'
+    (0 when that is the first line: its record may go on); final: nothing is cut."""
+    if final:
+        return len(text)
+    if not fasta:
+        feeds = [i for i, c in enumerate(text) if c == 10]
+        whole = len(feeds) & ~3
+        return feeds[whole - 1] + 1 if whole else 0
+    at = text.rfind(b"\n>")
+    return at + 1 if at >= 0 else 0
+
+
 def bgzf_compress(data: bytes, level: int = 1) -> bytes:
     """`data` as BGZF members (no EOF block) through zlib: blocks of at most BGZF_BLOCK bytes, raw deflate."""
     import struct

@@ -217,7 +217,7 @@ static vector<uint64_t> loadFreq(const string &prefix, size_t nTaxa, int kHigh, 
 }
 
 // KASA_HOST_TIMING=1: where the host spends the time of "Time fastq" (seconds, summed over the file)
-struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, deflate = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
+struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, inflate = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, deflate = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
 static HostTimers g_ht;
 static std::chrono::steady_clock::time_point g_t0 = std::chrono::steady_clock::now();
 static void mark(const char *what, uint64_t id = ~0ull)          // KASA_HOST_TIMING: a time line of the file's pipeline
@@ -514,6 +514,8 @@ static ReadSet readInput(const string &path, bool verbose, unsigned threads)
 // ---------------------------------------------------------------------------------------------------
 // input: streamed in chunks of whole records (N1) -- never the whole file in memory
 // ---------------------------------------------------------------------------------------------------
+// (the empty BGZF member that ends a file; its bytes 0..3 and 10..15 are every member's: see BGZF below)
+static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 // Reads a FASTA/FASTQ(.gz) file block by block (gz members inflate as they come) and hands out chunks that end at a record
 // boundary; a chunk is parsed by all host threads (parseRecords over runs cut at safe record starts).
 struct ChunkReader {
@@ -525,13 +527,24 @@ struct ChunkReader {
     HugeVec<char> buf[2]; int cur = 0; size_t have = 0;
     bool fasta = false, protein = false, eof = false, first = true;
     size_t blockBytes = 256u << 20;
-    explicit ChunkReader(const string &path)
+    // --device-inflate: a BGZF file is handed out as spans of whole members (nextSpan), its bytes read with the pread path;
+    // spanStarts lists where every span begins in the file and in the inflated text, for the way back to gzread (toGzread)
+    bool bgzf = false; const char *bgzfWhy = nullptr;
+    uint64_t membersOut = 0, textOut = 0, spanFileStart = 0;
+    vector<std::pair<uint64_t, uint64_t>> spanStarts;
+    explicit ChunkReader(const string &path, bool wantBgzf = false)
     {
         fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) throw std::runtime_error("Input file not found");
-        unsigned char magic[2] = {0, 0};
-        const ssize_t m = ::pread(fd, magic, 2, 0);
-        if (m == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+        unsigned char magic[18] = {0};
+        const ssize_t m = ::pread(fd, magic, 18, 0);
+        if (wantBgzf) {
+            if (m < 2 || magic[0] != 0x1f || magic[1] != 0x8b) bgzfWhy = "the input is not gzip";
+            else if (m < 18 || std::memcmp(magic, kBgzfEof, 4) != 0 || std::memcmp(magic + 10, kBgzfEof + 10, 6) != 0) bgzfWhy = "gzip without a BC subfield in its first member: one long stream";
+            else bgzf = true;
+        }
+        if (bgzf) { /* the descriptor stays: pread */ }
+        else if (m >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
             g = gzdopen(fd, "rb");                 // takes the descriptor over
             if (!g) { ::close(fd); fd = -1; throw std::runtime_error("Input file not found"); }
             fd = -1;
@@ -563,6 +576,83 @@ struct ChunkReader {
         for (size_t t = 0; t < nt; ++t) { total += got[t]; if ((size_t)got[t] < std::min(want, (t + 1) * slice) - t * slice) break; }   // (a short slice ends the data)
         filePos += total;
         return total;
+    }
+    // BGZF: the next span of whole members whose ISIZE sum is about blockBytes (false at the end of the file); `final`: the
+    // file ends with it.  Before the first span goes out the first member with text is inflated here, with zlib, for what
+    // next() reads off the text's start.  What is no member header, and a file that ends inside a member, end the run.
+    bool nextSpan(const char *&span, size_t &size, bool &final, bool verbose)
+    {
+        span = nullptr; size = 0; final = false;
+        auto bad = [&](int code, uint64_t member) { throw std::runtime_error(string(kasa_inflate_status_text(code)) + " in BGZF member " + std::to_string(member)); };
+        const size_t wantText = first ? std::max<size_t>(1, blockBytes / 4) : blockBytes;
+        for (;;) {
+            HugeVec<char> &D = buf[cur];
+            const unsigned char *b = (const unsigned char *)D.data();
+            size_t at = 0, text = 0; uint64_t nMem = 0;
+            while (have - at >= 18 && text < wantText) {
+                if (std::memcmp(b + at, kBgzfEof, 4) != 0 || std::memcmp(b + at + 10, kBgzfEof + 10, 6) != 0) bad(KASA_INFLATE_HEADER, membersOut + nMem);
+                const size_t total = (size_t)(b[at + 16] | b[at + 17] << 8) + 1;
+                if (total < 26) bad(KASA_INFLATE_HEADER, membersOut + nMem);
+                if (total > have - at) break;
+                uint32_t isize = 0;
+                for (int i = 0; i < 4; ++i) isize |= (uint32_t)b[at + total - 4 + i] << (8 * i);
+                if (first && isize > 0) {
+                    ScopedTimer tmCut(g_ht.cut);
+                    string head((size_t)std::min<uint32_t>(isize, 65536u), '\0');
+                    z_stream z; std::memset(&z, 0, sizeof z);
+                    if (inflateInit2(&z, -15) != Z_OK) throw std::runtime_error("zlib could not be initialised");
+                    z.next_in = const_cast<Bytef *>(b + at + 18); z.avail_in = (uInt)(total - 26);
+                    z.next_out = (Bytef *)&head[0]; z.avail_out = (uInt)head.size();
+                    const int zr = inflate(&z, Z_FINISH);
+                    const size_t got = head.size() - z.avail_out;
+                    inflateEnd(&z);
+                    if (zr != Z_STREAM_END || got == 0) bad(KASA_INFLATE_TRUNCATED, membersOut + nMem);
+                    if (head[0] != '>' && head[0] != '@') throw std::runtime_error("Input does not start with @ or >.");
+                    fasta = head[0] == '>';
+                    protein = detectProtein(head.data(), got, verbose);
+                    first = false;
+                }
+                at += total; text += isize; ++nMem;
+            }
+            if ((text >= wantText && at < have) || eof) {
+                if (eof && at < have) bad(have - at >= 4 && std::memcmp(b + at, kBgzfEof, 4) != 0 ? KASA_INFLATE_HEADER : KASA_INFLATE_CUT, membersOut + nMem);
+                if (at == 0) return false;
+                final = eof;                                            // (at == have: nothing follows)
+                HugeVec<char> &T = buf[cur ^ 1];
+                T.reserve(have - at + blockBytes + (1u << 17));
+                std::memcpy(T.data(), D.data() + at, have - at);
+                span = D.data(); size = at;
+                have -= at; cur ^= 1;
+                spanStarts.emplace_back(spanFileStart, textOut);
+                spanFileStart += at; textOut += text; membersOut += nMem;
+                return true;
+            }
+            ScopedTimer tm(g_ht.read);
+            const size_t want = std::max<size_t>(blockBytes, 1u << 17);
+            D.reserve(have + want);
+            const long n = readSome(D.data() + have, want);
+            if (n <= 0) eof = true; else have += (size_t)n;
+        }
+    }
+    // The way back: the host reads the rest of the file, which starts at inflated byte `textAt`, through gzread -- from the
+    // start of the span that holds that byte, the bytes before it dropped.
+    void toGzread(uint64_t textAt)
+    {
+        size_t k = spanStarts.size();
+        while (k > 0 && spanStarts[k - 1].second > textAt) --k;
+        const uint64_t fileAt = k ? spanStarts[k - 1].first : 0, from = k ? spanStarts[k - 1].second : 0;
+        if (::lseek(fd, (off_t)fileAt, SEEK_SET) < 0) throw std::runtime_error("the input cannot be read again from where the device stopped");
+        g = gzdopen(fd, "rb");
+        if (!g) throw std::runtime_error("the input cannot be read again from where the device stopped");
+        fd = -1; bgzf = false;
+        gzbuffer(g, 1u << 20);
+        vector<char> drop(1u << 16);
+        for (uint64_t left = textAt - from; left > 0;) {
+            const int n = gzread(g, drop.data(), (unsigned)std::min<uint64_t>(left, drop.size()));
+            if (n <= 0) throw std::runtime_error("the input cannot be read again from where the device stopped");
+            left -= (uint64_t)n;
+        }
+        have = 0; eof = false; handedOut = (size_t)textAt; chunkStart = handedOut;
     }
     // next chunk of whole records (false at the end of the file); it stays valid until the call after the next one
     bool next(const char *&chunk, size_t &size, bool verbose)
@@ -651,6 +741,7 @@ struct Params {
     bool coherence = false; float coherenceThreshold = 11.0f;   // --coherence, --coherenceThreshold (MetaHeader.h:159)
     bool bgzf = false;                             // --bgzf: the per-read file is a BGZF stream (blocked gzip), compressed where its text is made
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
+    bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
 };
 
 struct IndexFiles {                               // what Compare::ReadIndex loads (Compare.hpp:49-363), shared by every worker
@@ -1129,7 +1220,8 @@ struct Batcher {
             }
             protein = pending.protein;
         } else {
-            reader.reset(new ChunkReader(p.input));
+            reader.reset(new ChunkReader(p.input, devParse && p.deviceInflate));
+            if (reader->bgzfWhy && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << reader->bgzfWhy << ")" << std::endl;
             refill();
             protein = reader->protein;
         }
@@ -1150,6 +1242,20 @@ struct Batcher {
         ++pendingGen;
         if (pendPos > 0 && pendPos == pending.size()) { pending.clear(); pendPos = 0; }
         const char *chunk = nullptr; size_t chunkBytes = 0;
+        if (devParse && reader->bgzf) {             // --device-inflate: spans of members until one adds reads, the file ends or the host takes over
+            for (;;) {
+                bool final = false;
+                if (!reader->nextSpan(chunk, chunkBytes, final, p.verbose)) return;
+                if (pendPos > 0) { ReadSet rest = pending.slice(pendPos, pending.size(), 1, p.threads); pending = std::move(rest); pendPos = 0; }   // drop what was handed out, keep the rest
+                const size_t before = pending.size();
+                if (!refillDeviceBgzf(chunk, chunkBytes, final)) break;
+                if (pending.size() != before || final) return;
+            }
+            // (the reader is a gzread reader now and stands at the first byte the device has not parsed)
+            if (!reader->next(chunk, chunkBytes, p.verbose)) return;
+            parsePiece(chunk, chunkBytes, reader->fasta, p.threads, 1u << 20, pending, parts, reader->chunkStart);
+            return;
+        }
         if (!reader->next(chunk, chunkBytes, p.verbose)) return;
         if (pendPos > 0) {                          // drop what was handed out, keep the rest
             ReadSet rest = pending.slice(pendPos, pending.size(), 1, p.threads);
@@ -1186,12 +1292,49 @@ struct Batcher {
         if (kasa_parse_append(ps, text, chunkBytes, reader->fasta ? 1 : 0, &added, &parsable)) throwLast();
         if (kasa_parse_stage_ms(ps, &up1, &ps1)) throwLast();
         g_ht.uploadText += (up1 - up0) * 1e-3; g_ht.deviceParse += (ps1 - ps0) * 1e-3;
+        return pooled(ps, before, added, parsable, reader->chunkStart);
+    }
+    // --device-inflate: the same with a span of BGZF members (kasa_bgzf_parse_append).  A member that does not inflate ends the run.
+    uint64_t textParsed = 0;                      // inflated bytes the device has parsed: where the host would go on
+    bool refillDeviceBgzf(const char *span, size_t spanBytes, bool final)
+    {
+        std::lock_guard<std::mutex> lk(pool->mu);
+        kasa_parser *ps = pool->ps;
+        uint64_t before = 0, added = 0, nText = 0, carry = 0; int parsable = 0;
+        double up0 = 0, ps0 = 0, z0 = 0, up1 = 0, ps1 = 0, z1 = 0;
+        if (kasa_parse_sizes(ps, &before, nullptr, nullptr) || kasa_parse_stage_ms(ps, &up0, &ps0) || kasa_bgzf_parse_ms(ps, &z0)) throwLast();
+        if (kasa_bgzf_parse_append(ps, span, spanBytes, reader->fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &carry)) throwLast();
+        if (kasa_parse_stage_ms(ps, &up1, &ps1) || kasa_bgzf_parse_ms(ps, &z1)) throwLast();
+        g_ht.uploadText += (up1 - up0) * 1e-3; g_ht.deviceParse += (ps1 - ps0) * 1e-3; g_ht.inflate += (z1 - z0) * 1e-3;
+        if (!parsable) {
+            int code = 0; uint64_t at = 0;
+            (void)kasa_parse_status(ps, &code, &at);
+            if (code == KASA_PARSE_INFLATE) {
+                int zc = 0; uint64_t member = 0;
+                (void)kasa_bgzf_parse_status(ps, &zc, &member);
+                throw std::runtime_error(string(kasa_inflate_status_text(zc)) + " in BGZF member " + std::to_string(reader->membersOut - membersIn(span, spanBytes) + member));
+            }
+        }
+        const bool ok = pooled(ps, before, added, parsable, textParsed);
+        if (ok) textParsed += nText;
+        else reader->toGzread(textParsed);
+        return ok;
+    }
+    static uint64_t membersIn(const char *span, size_t n)
+    {
+        uint64_t k = 0;
+        for (size_t at = 0; at + 18 <= n; ++k) at += (size_t)((unsigned char)span[at + 16] | (unsigned char)span[at + 17] << 8) + 1;
+        return k;
+    }
+    // what both appends do with the outcome (pool->mu is held)
+    bool pooled(kasa_parser *ps, uint64_t before, uint64_t added, int parsable, uint64_t textStart)
+    {
         const size_t r0 = pending.size();
         if (before - pool->outstanding != r0 - pendPos) throw std::runtime_error("--device-parse: the pool and the pending reads disagree");
         if (!parsable) {
             int code = 0; uint64_t at = 0;
             (void)kasa_parse_status(ps, &code, &at);
-            if (p.verbose) std::cout << "OUT: --device-parse: the host parser takes over from byte " << reader->chunkStart + at << " (" << kasa_parse_status_text(code) << ")" << std::endl;
+            if (p.verbose) std::cout << "OUT: --device-parse: the host parser takes over from byte " << textStart + at << " (" << kasa_parse_status_text(code) << ")" << std::endl;
             if (pendPos > 0) { ReadSet rest = pending.slice(pendPos, pending.size(), 1, p.threads); pending = std::move(rest); pendPos = 0; }
             const size_t n = pending.size();
             pending.bases.resize((size_t)pending.off[n]);
@@ -1199,6 +1342,7 @@ struct Batcher {
             pending.devBases = false; devParse = false;
             return false;
         }
+        if (added == 0) return true;
         ScopedTimer tm(g_ht.deviceParse);
         pending.devBases = true; pending.fasta = reader->fasta;
         const size_t n0 = pending.nameBlob.size(); const int64_t b0 = pending.off[r0];
@@ -1432,7 +1576,6 @@ struct Batcher {
 // the empty member below.  The device makes such members of the text it writes (kasa_batch_bgzf); these are the host's:
 // zlib, raw deflate, level 1 -- for the frame, for batches whose text the host writes and for the bgzf-dump tap.
 static const size_t kBgzfBlock = 65280;
-static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static void bgzfAppend(string &out, const char *d, size_t n)    // the members of d[0 .. n) behind `out` (n = 0: none)
 {
     unsigned char buf[65536];
@@ -1945,6 +2088,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                           : (nDev > 1 || !ixf.spread.empty()) ? "more than one device slot" : nullptr;
         if (!why) poolDevice = p.devices[(size_t)devSlots[0]];
         else if (p.verbose) std::cout << "OUT: --device-parse: the host parser is used (" << why << ")" << std::endl;
+        if (why && p.deviceInflate && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << why << ")" << std::endl;
     }
     Batcher batcher(p, ixf, wantRows, maxKmersPerBatch, poolDevice);
     mark("first chunk parsed");
@@ -2099,7 +2243,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     mark("profile written");
     if (p.verbose && g_ht.on)
         std::cout << "OUT: host timing: read " << g_ht.read << " s, cut " << g_ht.cut << " s, parse " << g_ht.parse << " s, merge " << g_ht.merge
-                  << " s, upload-text " << g_ht.uploadText << " s, device-parse " << g_ht.deviceParse << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
+                  << " s, upload-text " << g_ht.uploadText << " s, inflate " << g_ht.inflate << " s, device-parse " << g_ht.deviceParse << " s, batch forming " << g_ht.form << " s, output write " << g_ht.write << " s; upload " << g_ht.upload << " s, device " << g_ht.compute
                   << " s (encode " << g_ht.encode << ", sort " << g_ht.sort << ", lookup + score " << g_ht.score << "), ranking " << g_ht.rank << " s, text " << g_ht.text << " s, text fetch " << g_ht.fetch << " s, deflate " << g_ht.deflate << " s" << std::endl;
     if (p.verbose && g_ht.on && p.coherence) {                   // (every call of the step returns with the device idle: host clock = device time + launches)
         std::cout << "OUT: coherence: " << g_ht.coherence << " s";
@@ -2215,6 +2359,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "Gzip") flag("--gzip", val);
         else if (key == "Bgzf") flag("--bgzf", val);                                 // ours: the reference never compresses the per-read file
         else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
+        else if (key == "DeviceInflate") flag("--device-inflate", val);
     }
     vector<string> out = {exe, mode};
     if (!kH.empty() && !kL.empty()) { out.push_back("-k"); out.push_back(kH); out.push_back(kL); }
@@ -3036,6 +3181,7 @@ static int run(int argc, char **argv)
         else if (s == "--host-rank") p.hostRank = true;
         else if (s == "--host-text") p.hostText = true;
         else if (s == "--device-parse") p.deviceParse = true;
+        else if (s == "--device-inflate") p.deviceInflate = p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());
