@@ -360,7 +360,9 @@ enum {
     KASA_INFLATE_TRUNCATED = 3,     /* the deflate data end before the last block does */
     KASA_INFLATE_BTYPE = 4,         /* block type 3 */
     KASA_INFLATE_STORED_LEN = 5,    /* a stored block whose LEN is not the complement of NLEN */
-    KASA_INFLATE_CODE_LENGTHS = 6,  /* a code-length set that is over-subscribed, incomplete, too long or has no end-of-block code */
+    KASA_INFLATE_CODE_LENGTHS = 6,  /* a dynamic block's header: more than 286 / 30 codes stated, a repeat with no length before it or
+                                       past the last one, a set that is over-subscribed or incomplete (but for a single one-bit
+                                       code; the code-length code has to be complete), no end-of-block code */
     KASA_INFLATE_SYMBOL = 7,        /* a bit pattern that is no code, or a length / distance symbol outside the alphabet */
     KASA_INFLATE_DISTANCE = 8,      /* a back-reference to before the member's first byte */
     KASA_INFLATE_OVERRUN = 9,       /* more output than ISIZE states */

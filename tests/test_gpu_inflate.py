@@ -1,7 +1,9 @@
 """BGZF inflated on the device (kasa_bgzf_inflate, kasa_bgzf_parse_append; csrc/kasa_inflate.h) against Python's zlib and
 against the parser fed with plain text: the corpus of tests/inflate_corpus.py gives zlib's bytes or its status and member,
 what the device's own deflater wrote comes back, members land at the running sum of ISIZE, and a file cut into members of
-997 bytes -- they end inside headers, sequences and quality lines -- pools the reads one append of the whole text pools."""
+997 bytes -- they end inside headers, sequences and quality lines -- pools the reads one append of the whole text pools.
+The second half takes corpus.built_cases(), the members tests/deflate_writer.py makes by construction (what zlib's compressor
+never writes), as spans of many members: the kernel's own sequencing, copies, token queue and CRC slices have no CPU build."""
 import ctypes as C
 import os
 
@@ -229,5 +231,72 @@ def test_fasta_text_without_a_header_is_refused_at_the_first_span():
         assert ps.append_bgzf(b"".join(ms[:2]), True) == (0, False, 0, 0)
         assert ps.status()[0] == KASA_PARSE_FASTA_HEADER and ps.sizes() == (0, 0, 0)
         assert ps.append_bgzf(b"".join(_members_of(b">a\nACGT\n")), True, final=True) == (1, True, 8, 0)
+    finally:
+        ps.close()
+
+
+# ---- members zlib's compressor never writes (corpus.built_cases; tests/test_inflate_cpu.py has run them on the CPU) -----------
+BUILT = {c[0]: c for c in corpus.built_cases()}
+BUILT_SPANS = {g: [c[0] for c in corpus.built_cases() if c[0][0] == g and c[2] is not None] for g in "ABCDEF"}
+_G = [c[0] for c in corpus.built_cases() if c[0][0] == "G"]
+BUILT_SPANS.update({"G%d" % k: _G[100 * k:100 * k + 100] + (_G[300:] if k == 2 else []) for k in range(3)})
+assert sum(len(v) for v in BUILT_SPANS.values()) == sum(1 for c in BUILT.values() if c[2] is not None)
+
+
+def _member_names(names):
+    """the case name of every member of the cases' spans put together"""
+    return [name for name in names for _ in formats.bgzf_member_table(BUILT[name][1])[0]]
+
+
+@pytest.mark.parametrize("group", list(BUILT_SPANS))
+def test_built_group(group):
+    """a whole group as ONE span of many members: zlib's text of every member, each at the running sum of ISIZE"""
+    assert capi.device_count() > 0, "no HIP device visible: the inflater needs a real MI355X"
+    names = BUILT_SPANS[group]
+    span, want = b"".join(BUILT[n][1] for n in names), b"".join(BUILT[n][2] for n in names)
+    rows, consumed, walk = formats.bgzf_member_table(span)
+    of = _member_names(names)
+    assert walk == 0 and consumed == len(span) and len(of) == len(rows)
+    text, st, member = capi.bgzf_inflate(0, span)
+    assert (st, member) == (0, 0), "member %d (%s): %s" % (member, of[member], capi.inflate_status_text(st))
+    if text != want:
+        for k, r in enumerate(rows):
+            a, b = r[6], r[6] + r[5]
+            if text[a:b] != want[a:b]:
+                at = next(i for i in range(a, b) if text[i] != want[i])
+                pytest.fail("member %d (%s) differs first at its byte %d of %d: %d for %d" % (k, of[k], at - a, r[5], text[at], want[at]))
+    assert text == want
+
+
+@pytest.mark.parametrize("name", [c[0] for c in corpus.built_cases() if c[2] is None])
+def test_built_malformed(name):
+    _, span, _, status = BUILT[name]
+    text, st, member = capi.bgzf_inflate(0, span)
+    assert text is None and (st, member) == status, (capi.inflate_status_text(st), member)
+
+
+@pytest.mark.parametrize("group", list(BUILT_SPANS))
+def test_built_texts_round_trip(group):
+    """the texts of the built members -- long overlapping runs, far matches, random bytes -- through the device's own
+    deflater and back, a text per call"""
+    for name in BUILT_SPANS[group]:
+        data = BUILT[name][2]
+        text, st, _ = capi.bgzf_inflate(0, capi.bgzf_deflate(0, data))
+        assert st == 0 and text == data, name
+
+
+def test_built_members_feed_the_parser():
+    """group G's member maker over the FASTQ file (literals and random back-references into itself), one append: the pool of
+    the plain text"""
+    _, span, text, _ = BUILT["G_over_fastq"]
+    assert text == _plain("reads.fastq")[0] and len(formats.bgzf_member_table(span)[0]) > 5
+    _, n, sizes, pool = _plain("reads.fastq")
+    ps = capi.Parser(0)
+    try:
+        got = ps.append_bgzf(span, False, final=True)
+        assert got == (n, True, len(text), 0), (got, ps.status(), ps.inflate_status())
+        assert ps.sizes() == sizes
+        for x, y in zip(ps.fetch(), pool):
+            assert np.array_equal(x, y)
     finally:
         ps.close()
