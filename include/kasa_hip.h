@@ -516,6 +516,21 @@ int kasa_ctx_counters(kasa_ctx *ctx, uint32_t *generalReads, uint32_t *secondPas
  * window in device memory (narrow records; 64-byte records return KASA_E_LIMIT there).  Ours: the reference's flush is a
  * hash map per thread and has no such window (Compare.hpp:917-955). */
 int kasa_ctx_third_pass_reads(kasa_ctx *ctx, uint32_t *thirdPassReads);
+/* The row merge takes the staging rows of the fast score kernels in classes by length (256 / 512 / 1024 records up to 2048
+ * taxa, 256 / 1024 up to 16 384 taxa where the second class stays empty, and a streaming class for the longer rows of long
+ * reads): the first class's launch sweeps all reads, the others walk the rows score_main_kernel listed for them and are not
+ * launched without any.  out[0..3]: rows of the last batch in the first, second, third and long class (the first counts
+ * every read the fast kernels kept that is not listed above it, rows without records included; zeros when the sorting merge
+ * or the general kernel took the batch -- the first then holds the reads the fast kernels kept).  Diagnostics, host side only. */
+int kasa_ctx_row_classes(kasa_ctx *ctx, uint64_t out[4]);
+/* Test tap: at most n workgroups per row-merge launch (0: as many as are resident), so that a small batch makes one
+ * wavefront walk many rows. */
+int kasa_ctx_row_merge_blocks(kasa_ctx *ctx, uint32_t n);
+/* Test tap: on != 0 makes every later kasa_batch_score / kasa_batch_lookup_score copy the rows' lengths to the host before
+ * the merge replaces them by the number of distinct taxa (one more copy and wait per batch); kasa_batch_staged_lengths
+ * returns them, out[nReads]: records of a row the fast kernels staged, pairs of a row the general kernel wrote. */
+int kasa_ctx_keep_staged_lengths(kasa_ctx *ctx, int on);
+int kasa_batch_staged_lengths(kasa_ctx *ctx, uint32_t *out);
 /* ... and the reads of that list that were long enough (16384 k-mers and more: a contig, a chromosome read in pieces under one
  * read id) to be replayed from SORTED EVENTS instead -- every query of theirs turned into events {read, taxon, flush position,
  * level} by all wavefronts, one radix sort, one float32 chain per (read, taxon) -- and the events that took.  The reference

@@ -41,6 +41,7 @@ EXPORTS = [
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate",
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
+    "kasa_ctx_row_classes", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
 ]
 
 
@@ -1063,6 +1064,25 @@ class Context:
         n = C.c_uint32(0)
         _check(lib().kasa_ctx_third_pass_reads(self.h, C.byref(n)))
         return int(n.value)
+
+    def row_classes(self):
+        """Rows of the last batch per row-merge class: (first, second, third, long) -- kasa_ctx_row_classes."""
+        out = np.zeros(4, dtype=np.uint64)
+        _check(lib().kasa_ctx_row_classes(self.h, _p(out)))
+        return tuple(int(v) for v in out)
+
+    def row_merge_blocks(self, n: int):
+        """Cap the grid of every row-merge launch at n workgroups (0: the default) -- kasa_ctx_row_merge_blocks."""
+        _check(lib().kasa_ctx_row_merge_blocks(self.h, C.c_uint32(int(n))))
+
+    def keep_staged_lengths(self, on: bool = True):
+        _check(lib().kasa_ctx_keep_staged_lengths(self.h, C.c_int(int(bool(on)))))
+
+    def staged_lengths(self) -> np.ndarray:
+        """Length of every read's staging row before the row merge (after keep_staged_lengths) -- kasa_batch_staged_lengths."""
+        out = np.zeros(self.n_reads, dtype=np.uint32)
+        _check(lib().kasa_batch_staged_lengths(self.h, _p(out)))
+        return out
 
     def batch_stats(self):
         st = np.zeros(8, dtype=np.uint64)

@@ -650,6 +650,10 @@ struct kasa_ctx {
     uint64_t profLeftHint = 0;                  // per-level keys the last batch's table pass left over, when the list was too short for them
     bool forceSlowScore = false; uint32_t lastSlowReads = 0; int debugFlags = 0;
     DevBuf rowPos, rowLen, rowKey, rowOff, st, outTax, outScore;
+    DevBuf clsList;                            // rows of the upper row-merge classes (second, third, long), nReads entries each: score_main_kernel lists them
+    uint64_t rowClasses[4] = {0, 0, 0, 0};     // rows of the last batch per row-merge class (kasa_ctx_row_classes)
+    uint32_t rowMergeBlocks = 0;               // cap on the grid of every row-merge launch (0: as many as are resident)
+    bool keepStagedLengths = false; std::vector<uint32_t> stagedLengths;   // kasa_batch_staged_lengths: rowLen before the merge
     DevBuf cntUnique, cntTotal, cntAllHi, cntAllMid, cntAllLo; // u64[nK*nTaxa] each
     uint64_t poolCap = 0, stCap = 0, keyCap = 0, keyCapScore = 0, nnz = 0;   // keyCap: group keys (narrow records); keyCapScore: the per-read side's keys (wide records)
     void *qKmer = nullptr; uint32_t *qRead = nullptr; // current (valid) query arrays; keys are u64 or key128 as the index
@@ -674,7 +678,7 @@ struct kasa_ctx {
                 &outScore, &cntUnique, &cntTotal, &cntAllHi, &cntAllLo, &rawOff, &cohLen, &cohState, &sortBig, &rankDen, &rankClass, &rankMeta, &rankOut,
                 &rankList, &rankScratch, &scanTmp, &taxText, &taxTextOff, &taxTextIds, &txtNames, &txtNameOff, &txtLen, &txtBest, &txtBytes, &txtOff, &txtOut,
                 &txtFlags, &bgzMembers, &bgzSize, &bgzOff, &bgzOut, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
-                &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn};
+                &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn, &clsList};
     }
 };
 
@@ -3791,6 +3795,8 @@ struct ScoreArgs {
     const uint32_t *list; uint32_t nList;        // general kernel: reads to process (NULL = all)
     const uint32_t *flushPos; const uint64_t *flushOff;   // general kernel: F per level of the listed reads' queries; first query of list entry wi
     uint32_t *fbList, *fbCount;                  // fast kernel: reads it hands to the general kernel
+    uint32_t clsLo[3];                           // fast kernel: a row of more than clsLo[k] records belongs to row-merge class k + 1 or above (second, third, long)
+    uint32_t *clsList[3], *clsCount;             // fast kernel: the rows of each of those classes, and how many (clsCount NULL: no lists)
     uint32_t *ovList, *ovCount;                  // general kernel, first pass: reads it hands to the second pass (NULL = last pass)
     uint32_t *mainOut;                           // fast kernels: {taxon 0, taxon 1, position, count} per read, main -> other
     uint32_t *otherOff64;                        // fast kernels: records of the other taxa a read has yielded before slot 64 i
@@ -4778,6 +4784,21 @@ __global__ __launch_bounds__(64, (RW == 8 && NLV <= 6 && FB == 8) ? 7 : (RW == 1
             fbBase = lane_value<0>(fbBase);
             if (active && fb) A.fbList[fbBase + __popcll(fbMask & ((1ull << lane) - 1ull))] = r;
         }
+        // rows beyond the first row-merge class, listed per class: those launches walk their list, not all reads
+        if (A.clsCount) {
+            const uint32_t cls = (active && !fb && fits && m > A.clsLo[0]) ? (m > A.clsLo[2] ? 3u : (m > A.clsLo[1] ? 2u : 1u)) : 0u;
+            if (__ballot(cls != 0u)) {
+#pragma unroll
+                for (uint32_t k = 1; k <= 3; ++k) {
+                    const unsigned long long clsMask = __ballot(cls == k);
+                    if (!clsMask) continue;
+                    uint32_t clsBase = 0;
+                    if (lane == 0) clsBase = atomicAdd(&A.clsCount[k - 1], (uint32_t)__popcll(clsMask));
+                    clsBase = lane_value<0>(clsBase);
+                    if (cls == k) A.clsList[k - 1][clsBase + __popcll(clsMask & ((1ull << lane) - 1ull))] = r;
+                }
+            }
+        }
     }
 }
 
@@ -5444,8 +5465,8 @@ static constexpr int BM_WORDS = 512;
 // three lanes busy).
 template <int RCAP, int BMW, bool LONG = false>
 __global__ __launch_bounds__(64) void row_merge_bitmap_kernel(const uint32_t *__restrict__ rowPos, uint32_t *__restrict__ rowLen,
-                                                              const uint32_t *__restrict__ rowKey,
-                                                              uint32_t nReads, uint2 *__restrict__ st, uint64_t *__restrict__ profKeys,
+                                                              const uint32_t *__restrict__ rowKey, const uint32_t *__restrict__ list,
+                                                              uint32_t nRows, uint2 *__restrict__ st, uint64_t *__restrict__ profKeys,
                                                               int kHigh, uint32_t nTaxa, uint32_t mLo, ProfLayout PL)
 {
     __shared__ uint32_t bm[BMW], pre[BMW];
@@ -5456,21 +5477,47 @@ __global__ __launch_bounds__(64) void row_merge_bitmap_kernel(const uint32_t *__
     const int lane = threadIdx.x;
     const uint32_t W = (nTaxa + 31u) >> 5;
     constexpr int HELD = 4;                                            // chunks of a row kept in registers between the passes
-    // the row's whereabouts are fetched one row ahead: the kernel is a chain of dependent round trips per row
-    uint32_t r = blockIdx.x;
-    uint32_t nRaw = r < nReads ? rowLen[r] : 0u, nPos = r < nReads ? rowPos[r] : 0u, nKey = r < nReads ? rowKey[r] : 0u;
-    for (; r < nReads; r += gridDim.x) {
-        const uint32_t raw = nRaw, s0 = nPos, key0 = nKey;
-        const uint32_t rNext = r + gridDim.x;
-        if (rNext < nReads) { nRaw = rowLen[rNext]; nPos = rowPos[rNext]; nKey = rowKey[rNext]; }
-        if (!(raw & ROW_MERGE)) continue;                              // uniform per block
+    // The kernel is a chain of dependent round trips per row, so the walk runs ahead of the merge: the row number three
+    // steps ahead (list: the rows of this launch's class, NULL: all reads), the row's whereabouts two steps ahead, and the
+    // first chunks of the next row -- when it is one this launch takes -- one step ahead, in flight during the passes below.
+    const uint32_t G = gridDim.x;
+    auto rowOf = [&](uint32_t step) -> uint32_t {
+        const unsigned long long i = (unsigned long long)blockIdx.x + (unsigned long long)step * G;
+        return i < nRows ? (list ? list[i] : (uint32_t)i) : 0xFFFFFFFFu;
+    };
+    struct Where { uint32_t r, raw, pos, key; };
+    auto whereOf = [&](uint32_t row) -> Where {
+        Where w{row, 0u, 0u, 0u};
+        if (row != 0xFFFFFFFFu) { w.raw = rowLen[row]; w.pos = rowPos[row]; w.key = rowKey[row]; }
+        return w;
+    };
+    auto taken = [&](uint32_t raw) -> bool {                           // uniform per block; a row is taken by exactly one launch
         const uint32_t m = raw & ~ROW_MERGE;
-        if (m <= mLo || (!LONG && m > (uint32_t)RCAP)) continue;
-        uint2 held[HELD];                                              // all loads of the first chunks go out together
+        return (raw & ROW_MERGE) && m > mLo && (LONG || m <= (uint32_t)RCAP);
+    };
+    auto fetch = [&](const Where &w, uint2 (&h)[HELD]) {               // all loads of the first chunks go out together
+        const uint32_t m = w.raw & ~ROW_MERGE;
 #pragma unroll
         for (int c = 0; c < HELD; ++c) {
             const uint32_t i = (uint32_t)c * 64u + lane;
-            held[c] = i < m ? st[s0 + i] : make_uint2(RK_FINAL, 0u);
+            h[c] = i < m ? st[w.pos + i] : make_uint2(RK_FINAL, 0u);
+        }
+    };
+    Where cur = whereOf(rowOf(0)), a1 = whereOf(rowOf(1));
+    uint32_t r2 = rowOf(2);
+    uint2 held[HELD] = {}, ahead[HELD] = {};
+    if (taken(cur.raw)) fetch(cur, held);
+    for (uint32_t step = 0; cur.r != 0xFFFFFFFFu; ++step) {
+        const Where a2 = whereOf(r2);
+        const uint32_t r3 = rowOf(step + 3u);
+        if (taken(a1.raw)) fetch(a1, ahead);
+        const uint32_t r = cur.r, s0 = cur.pos, key0 = cur.key, m = cur.raw & ~ROW_MERGE;
+        const bool mine = taken(cur.raw);
+        cur = a1; a1 = a2; r2 = r3;
+        if (!mine) {
+#pragma unroll
+            for (int c = 0; c < HELD; ++c) held[c] = ahead[c];
+            continue;
         }
         for (uint32_t w = lane; w < W; w += 64) bm[w] = 0u;
         for (uint32_t i = lane; i < (LONG ? min(m, (uint32_t)RCAP) : m); i += 64) { val[i] = 0.0f; claim[i] = 0xFFFFFFFFu; }
@@ -5559,6 +5606,8 @@ __global__ __launch_bounds__(64) void row_merge_bitmap_kernel(const uint32_t *__
         for (uint32_t sl = lane; sl < nSlots; sl += 64) st[s0 + sl] = make_uint2(slotTax[sl], __float_as_uint(val[sl]));
         if (lane == 0) rowLen[r] = nSlots;                             // flag cleared: the other instantiation skips it
         LDS_WAVE_SYNC();
+#pragma unroll
+        for (int c = 0; c < HELD; ++c) held[c] = ahead[c];
     }
 }
 
@@ -6316,6 +6365,8 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
     const int RW = c->recWords();
     int rc;
     c->haveScores = false; c->nnz = 0;
+    for (int k = 0; k < 4; ++k) c->rowClasses[k] = 0;
+    if (c->keepStagedLengths) c->stagedLengths.assign(nReads, 0u); else c->stagedLengths.clear();
     if (nQ == 0 || nReads == 0) {
         if (wantPerRead) {
             if ((rc = c->rowOff.reserve(((size_t)nReads + 1) * 8))) return rc;
@@ -6326,14 +6377,21 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         c->state = 4;
         return KASA_OK;
     }
-    uint32_t *counters = c->misc.as<uint32_t>(); // [2] error flags, [3] fallback count, [5] second-pass count, [8..15] reasons; u64 [16] pool cursor, [17] staging cursor
+    uint32_t *counters = c->misc.as<uint32_t>(); // [2] error flags, [3] fallback count, [5] second-pass count, [8..15] reasons, [84..86] rows per upper row-merge class; u64 [16] pool cursor, [17] staging cursor
     const bool gp = RW == 8;                     // narrow records: the profile is group_stage's, the kernels here leave no keys (they still add their zero)
     unsigned long long *stCursor = c->misc.as<unsigned long long>() + 17, *keyCursor = c->misc.as<unsigned long long>() + (gp ? 30 : 18);
     hipEvent_t a, b;
 
     if ((rc = c->rowPos.reserve((size_t)nReads * 4 + 64)) || (rc = c->rowLen.reserve((size_t)nReads * 4 + 64)) || (rc = c->rowKey.reserve((size_t)nReads * 4 + 64)) ||
-        (rc = c->rowOff.reserve(((size_t)nReads + 1) * 8 + 64)) || (rc = c->fbList.reserve((size_t)nReads * 4 + 64)))
+        (rc = c->rowOff.reserve(((size_t)nReads + 1) * 8 + 64)) || (rc = c->fbList.reserve((size_t)nReads * 4 + 64)) ||
+        (rc = c->clsList.reserve((size_t)nReads * 12 + 64)))
         return rc;
+    // row-merge classes by row length (the LDS a row needs is what limits the resident wavefronts of that latency-bound kernel):
+    // up to 2048 taxa 256 / 512 / RMAX, up to BM_WORDS * 32 taxa 256 / RMAX over the wide bitmap (no second class), LONG beyond RMAX
+    const bool bitmapMerge = nTaxa <= (uint32_t)BM_WORDS * 32u && !(c->debugFlags & 4);
+    const uint32_t clsLo[3] = {256u, nTaxa <= 2048u ? 512u : 256u, (uint32_t)RMAX};
+    uint32_t *clsCount = counters + 84;          // [84..86] rows listed for the second, third and long class
+    uint32_t nCls[3] = {0, 0, 0}, nHanded = 0;
     if (c->stCap == 0) c->stCap = std::max<uint64_t>(1u << 16, (uint64_t)nReads * 8);
     const bool fast = nK <= 25 && nTaxa <= (1u << 20) && !c->forceSlowScore;   // staging records keep the taxon in 20 bits
     bool slowProfileDone = false;   // score_kernel adds to the profile tables itself: only once, whatever is rerun
@@ -6351,6 +6409,8 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         HIPCHK(hipMemsetAsync(counters + 8, 0, 32, c->stream));
         HIPCHK(hipMemsetAsync(stCursor, 0, 8, c->stream));             // staging cursor
         HIPCHK(hipMemsetAsync(keyCursor, 0, 8, c->stream));
+        HIPCHK(hipMemsetAsync(clsCount, 0, 12, c->stream));            // a rerun lists the rows anew
+        nCls[0] = nCls[1] = nCls[2] = 0; nHanded = 0;
         HIPCHK(hipMemsetAsync(c->rowLen.p, 0, (size_t)nReads * 4, c->stream));
         A.rec = c->rec.as<uint32_t>(); A.recCW = c->recCW; A.recQS = c->recCW == 8u ? 1u : 2u; A.kmerOff = c->kmerOff.as<uint64_t>();
         // long rows for long reads: the streaming row merge keeps a slot per taxon in LDS (up to 4096 taxa), the bitmap merge must be the one in use (test tap 4: the sorting merge)
@@ -6366,6 +6426,8 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         A.addProfile = gp ? 0 : (slowProfileDone ? 0 : 1);
         A.list = nullptr; A.nList = 0; A.flushPos = nullptr; A.flushOff = nullptr;
         A.fbList = c->fbList.as<uint32_t>(); A.fbCount = counters + 3; A.why = counters + 8;
+        for (int k = 0; k < 3; ++k) { A.clsLo[k] = clsLo[k]; A.clsList[k] = c->clsList.as<uint32_t>() + (size_t)k * nReads; }
+        A.clsCount = bitmapMerge ? clsCount : nullptr;                  // (the sorting merge takes every row in one launch)
         A.ovList = nullptr; A.ovCount = nullptr; A.workCursor = nullptr; A.forceHandOn = (c->debugFlags & 16384) ? 1 : 0;
         if ((rc = timer_begin(c, c->timers[KASA_STAGE_SCORE], &a, &b))) return rc;
         uint32_t nSlow = nReads;
@@ -6416,8 +6478,9 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
             uint32_t h3 = 0; unsigned long long want[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(&h3, counters + 3, 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipMemcpyAsync(want, stCursor, gp ? 8 : 16, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipMemcpyAsync(nCls, clsCount, 12, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
-            nSlow = h3;
+            nSlow = h3; nHanded = h3;
             if (want[0] > c->stCap || (!gp && want[1] > c->keyCapScore)) {   // the fast kernels have no side effects: grow and rerun
                 if ((rc = timer_end(c, c->timers[KASA_STAGE_SCORE], a, b))) return rc;
                 if (want[0] > c->stCap) c->stCap = want[0] + want[0] / 8 + (uint64_t)nSlow * 64 + 1024;
@@ -6592,7 +6655,17 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         if (want <= c->stCap) { staged = want; break; }
         c->stCap = want + want / 8 + 1024;
     }
+    if (c->keepStagedLengths) {                  // (tests: the rows' lengths as the score kernels left them)
+        c->stagedLengths.resize(nReads);
+        HIPCHK(hipMemcpyAsync(c->stagedLengths.data(), c->rowLen.p, (size_t)nReads * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (uint32_t &v : c->stagedLengths) v &= ~ROW_MERGE;
+    } else c->stagedLengths.clear();
     // ---- resolve the fast kernels' records: per-read merge
+    if (fast) {                                  // (the first class: the reads the fast kernels kept, rows without records among them)
+        c->rowClasses[0] = (uint64_t)nReads - nHanded - nCls[0] - nCls[1] - nCls[2];
+        for (int k = 0; k < 3; ++k) c->rowClasses[k + 1] = nCls[k];
+    }
     bool mergePending = false;
     if (fast && staged > 0) {
         const ProfLayout PL = prof_layout(nTaxa, nK);
@@ -6600,32 +6673,32 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         hipEvent_t ka, kb;
         if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_ROW_MERGE], &ka, &kb))) return rc;
         uint64_t *noKeys = gp ? nullptr : c->profKeys.as<uint64_t>();   // (narrow records: the rows' events leave no profile keys -- group_stage)
-        if (nTaxa <= (uint32_t)BM_WORDS * 32u && !(c->debugFlags & 4)) {
-            uint32_t mLo = 0;
-            if (nTaxa <= 2048u) {
-                // (three sizes: the LDS a row needs is what limits the resident wavefronts of this latency-bound kernel)
-                row_merge_bitmap_kernel<256, 64><<<std::min<uint32_t>(nReads, 256u * 32u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                    c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, 0u, PL);
-                row_merge_bitmap_kernel<512, 64><<<std::min<uint32_t>(nReads, 256u * 32u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                    c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, 256u, PL);
-                mLo = 512;
-            } else {                                                 // up to 16384 taxa: the same two sizes over the wide bitmap
-                row_merge_bitmap_kernel<256, BM_WORDS><<<std::min<uint32_t>(nReads, 256u * 32u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                    c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, 0u, PL);
-                mLo = 256;
-            }
-            row_merge_bitmap_kernel<RMAX, BM_WORDS><<<std::min<uint32_t>(nReads, 256u * 16u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, mLo, PL);
-            if (A.rowPerQuery && (uint64_t)c->maxCnt * A.rowPerQuery >= 2ull * RMAX) {   // long reads' rows (beyond RMAX records): streamed, slots in LDS
-                if (nTaxa <= 2048u)
-                    row_merge_bitmap_kernel<2048, 64, true><<<std::min<uint32_t>(nReads, 256u * 16u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                        c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, (uint32_t)RMAX, PL);
-                else
-                    row_merge_bitmap_kernel<4096, 128, true><<<std::min<uint32_t>(nReads, 256u * 16u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(),
-                        c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, (uint32_t)RMAX, PL);
-            }
+        if (bitmapMerge) {
+            // The first class sweeps all reads (nearly every row is its own); the upper classes and LONG walk the rows
+            // score_main_kernel listed for them and are not launched when there are none.  As many workgroups as are resident.
+            typedef void (*MergeKernel)(const uint32_t *, uint32_t *, const uint32_t *, const uint32_t *, uint32_t, uint2 *, uint64_t *, int, uint32_t, uint32_t, ProfLayout);
+            int nCu = 0;
+            HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
+            auto merge = [&](MergeKernel kern, const uint32_t *list, uint32_t rows, uint32_t mLo) -> int {
+                if (rows == 0) return KASA_OK;
+                int perCu = 0;
+                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *)kern, 64, 0));
+                uint32_t grid = (uint32_t)std::max(1, perCu) * (uint32_t)std::max(1, nCu);
+                if (c->rowMergeBlocks) grid = std::min(grid, c->rowMergeBlocks);
+                kern<<<std::min(rows, grid), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), list, rows,
+                                                               c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, mLo, PL);
+                HIPCHK(hipGetLastError());
+                return KASA_OK;
+            };
+            const bool narrow = nTaxa <= 2048u;                      // (the wide bitmap beyond: the same sizes, no second class)
+            if ((rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<256, 64> : (MergeKernel)row_merge_bitmap_kernel<256, BM_WORDS>, nullptr, nReads, 0u)) ||
+                (rc = merge(row_merge_bitmap_kernel<512, 64>, A.clsList[0], narrow ? nCls[0] : 0u, clsLo[0])) ||
+                (rc = merge(row_merge_bitmap_kernel<RMAX, BM_WORDS>, A.clsList[1], nCls[1], clsLo[1])) ||
+                // long reads' rows (beyond RMAX records): streamed, slots in LDS
+                (rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<2048, 64, true> : (MergeKernel)row_merge_bitmap_kernel<4096, 128, true>, A.clsList[2], nCls[2], clsLo[2])))
+                return rc;
         } else
-            row_merge_kernel<<<std::min<uint32_t>(nReads, 256u * 24u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(),
+            row_merge_kernel<<<std::min<uint32_t>(nReads, c->rowMergeBlocks ? c->rowMergeBlocks : 256u * 24u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(),
                 c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, PL);
         HIPCHK(hipGetLastError());
         if ((rc = timer_end(c, c->kernels[KASA_KERNEL_ROW_MERGE], ka, kb))) return rc;
@@ -8805,6 +8878,37 @@ extern "C" int kasa_ctx_third_pass_reads(kasa_ctx *c, uint32_t *thirdPassReads)
 {
     if (!c || !thirdPassReads) return fail(KASA_E_ARG, "kasa_ctx_third_pass_reads: NULL argument");
     *thirdPassReads = c->lastThirdPassReads;
+    return KASA_OK;
+}
+
+extern "C" int kasa_ctx_row_classes(kasa_ctx *c, uint64_t out[4])
+{
+    if (!c || !out) return fail(KASA_E_ARG, "kasa_ctx_row_classes: NULL argument");
+    for (int k = 0; k < 4; ++k) out[k] = c->rowClasses[k];
+    return KASA_OK;
+}
+
+extern "C" int kasa_ctx_row_merge_blocks(kasa_ctx *c, uint32_t n)
+{
+    if (!c) return fail(KASA_E_ARG, "ctx is NULL");
+    c->rowMergeBlocks = n;
+    return KASA_OK;
+}
+
+extern "C" int kasa_ctx_keep_staged_lengths(kasa_ctx *c, int on)
+{
+    if (!c) return fail(KASA_E_ARG, "ctx is NULL");
+    c->keepStagedLengths = on != 0;
+    if (!on) c->stagedLengths.clear();
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_staged_lengths(kasa_ctx *c, uint32_t *out)
+{
+    if (!c || !out) return fail(KASA_E_ARG, "kasa_batch_staged_lengths: NULL argument");
+    if (c->state < 4 || !c->keepStagedLengths || c->stagedLengths.size() != (size_t)c->nReads)
+        return fail(KASA_E_STATE, "kasa_batch_staged_lengths: no lengths kept (kasa_ctx_keep_staged_lengths before the batch is scored)");
+    if (c->nReads) memcpy(out, c->stagedLengths.data(), (size_t)c->nReads * 4);
     return KASA_OK;
 }
 
