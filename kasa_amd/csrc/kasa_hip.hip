@@ -5709,7 +5709,30 @@ static ProfTableLayout prof_table_layout(int nK, int lvLo, int lvHi, uint32_t nT
     for (int lv = 0; lv < MAX_LEVELS; ++lv) L.first[lv + 1] = (uint16_t)(L.first[lv] + L.nn[lv]);
     return L;
 }
-__global__ __launch_bounds__(PT_THREADS) void profile_table_kernel(const uint64_t *__restrict__ keys, uint32_t nKeys, uint32_t nTaxa, int nK, ProfTableLayout TL,
+// The layout as the kernels take it: a window has at most eight levels (narrow records: nK <= 8; wide ones: windows of four
+// and of eight) and at most 24 + 7 * 8 rows, so nn and first of its levels are a byte each in two 64-bit kernel arguments --
+// scalar registers, read with a shift by the level.  (As arrays in the argument segment a lane-varying level made every
+// lookup two global loads: 12 vector-memory reads per key load.)  Levels outside the window have nn = 0: no cell.
+struct ProfTablePacked {
+    uint64_t nnPk, firstPk;                                            // byte j: level lvLo + j
+    int lvLo, lvHi;
+    uint32_t rows;                                                     // all levels' rows together (first[MAX_LEVELS])
+    __device__ __forceinline__ uint32_t nn(uint32_t j) const { return (uint32_t)(nnPk >> (8u * j)) & 255u; }
+    __device__ __forceinline__ uint32_t first(uint32_t j) const { return (uint32_t)(firstPk >> (8u * j)) & 255u; }
+    // the window level of a table row, row < rows
+    __device__ __forceinline__ uint32_t level_of_row(uint32_t row) const { uint32_t j = 0; while (j < 7u && row >= first(j) + nn(j)) ++j; return j; }
+};
+static bool prof_table_pack(const ProfTableLayout &L, ProfTablePacked &P)
+{
+    P.nnPk = 0; P.firstPk = 0; P.lvLo = L.lvLo; P.lvHi = L.lvHi; P.rows = L.first[MAX_LEVELS];
+    if (L.lvHi - L.lvLo > 8 || L.first[MAX_LEVELS] > 255u) return false;
+    for (int j = 0; j < 8 && L.lvLo + j < MAX_LEVELS; ++j) {
+        P.nnPk |= (uint64_t)L.nn[L.lvLo + j] << (8 * j);
+        P.firstPk |= (uint64_t)L.first[L.lvLo + j] << (8 * j);
+    }
+    return true;
+}
+__global__ __launch_bounds__(PT_THREADS) void profile_table_kernel(const uint64_t *__restrict__ keys, uint32_t nKeys, uint32_t nTaxa, int nK, ProfTablePacked TL,
                                                                    uint64_t *__restrict__ cntUnique, uint64_t *__restrict__ hiTab,
                                                                    uint64_t *__restrict__ midTab, uint64_t *__restrict__ loTab, ProfLayout PL,
                                                                    uint64_t *__restrict__ leftOut, unsigned long long *__restrict__ leftCursor)
@@ -5718,7 +5741,8 @@ __global__ __launch_bounds__(PT_THREADS) void profile_table_kernel(const uint64_
     __shared__ uint64_t sLeft[PT_LEFT];
     __shared__ uint32_t sLeftN;
     __shared__ unsigned long long sLeftBase;
-    const uint32_t cells = (uint32_t)TL.first[MAX_LEVELS] * nTaxa;
+    const uint32_t cells = TL.rows * nTaxa;
+    const uint32_t nW = (uint32_t)(TL.lvHi - TL.lvLo);                  // levels of this pass's window
     for (uint32_t i = threadIdx.x; i < cells; i += PT_THREADS) tab[i] = 0u;
     if (threadIdx.x == 0) sLeftN = 0;
     __syncthreads();
@@ -5756,8 +5780,9 @@ __global__ __launch_bounds__(PT_THREADS) void profile_table_kernel(const uint64_
             if (hits != 0u && tax != (1u << PL.tb) - 1u) {               // (else: unused slot)
                 const uint32_t n = (uint32_t)((f >> PL.tb) & ((1ull << PL.nb) - 1ull));
                 const uint32_t lv = (uint32_t)(f >> (PL.tb + PL.nb));
-                if ((int)lv < TL.lvLo || (int)lv >= TL.lvHi) {}                // another pass counts this level
-                else if (n >= 1u && n <= (uint32_t)TL.nn[lv] && hits <= maxHits) atomicAdd(&tab[((uint32_t)TL.first[lv] + (n - 1u)) * nTaxa + tax], hits);
+                const uint32_t j = lv - (uint32_t)TL.lvLo;                     // (below the window: wraps beyond nW)
+                if (j >= nW) {}                                                // another pass counts this level
+                else if (n >= 1u && n <= TL.nn(j) && hits <= maxHits) atomicAdd(&tab[(TL.first(j) + (n - 1u)) * nTaxa + tax], hits);
                 else {
                     const uint32_t at = atomicAdd(&sLeftN, 1u);
                     if (at < (uint32_t)PT_LEFT) sLeft[at] = key;
@@ -5773,9 +5798,8 @@ __global__ __launch_bounds__(PT_THREADS) void profile_table_kernel(const uint64_
         const uint32_t c = tab[i];
         if (!c) continue;
         const uint32_t tax = i % nTaxa, row = i / nTaxa;
-        uint32_t lv = 0;
-        while (row >= (uint32_t)TL.first[lv + 1]) ++lv;
-        const uint32_t n = row - (uint32_t)TL.first[lv] + 1u;
+        const uint32_t j = TL.level_of_row(row), lv = (uint32_t)TL.lvLo + j;
+        const uint32_t n = row - TL.first(j) + 1u;
         const size_t cell = (size_t)lv * nTaxa + tax;
         if (n == 1u) atomicAdd((unsigned long long *)&cntUnique[cell], (unsigned long long)c);
         fixed_add(hiTab, midTab, loTab, cell, c, n);
@@ -5904,14 +5928,14 @@ static int launch_group2(kasa_ctx *c, const uint32_t *slotOf, uint32_t nTiles, u
 // a crowded index that is most of them, so they leave without any per-key atomic: a round's keys are looked at twice -- first
 // the cells are served and the leftovers counted, then (one running sum over the workgroup, ONE add to the list's cursor) every
 // thread writes its leftovers to its own place.  Should the list be full: straight to the tables.
-__global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const uint64_t *__restrict__ keys, uint32_t nKeys, uint32_t nTaxa, int nK, ProfTableLayout TL,
+__global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const uint64_t *__restrict__ keys, uint32_t nKeys, uint32_t nTaxa, int nK, ProfTablePacked TL,
                                                                          uint64_t *__restrict__ cntUnique, uint64_t *__restrict__ hiTab,
                                                                          uint64_t *__restrict__ midTab, uint64_t *__restrict__ loTab, ProfLayout PL,
                                                                          uint64_t *__restrict__ leftOut, unsigned long long *__restrict__ leftCursor, unsigned long long leftCap,
                                                                          int rangeCells)
 {
-    extern __shared__ uint32_t tab[];                                  // [level][|T| - 1][nTaxa], TL.nn[level] values of |T| per level
-    const uint32_t cells = (uint32_t)TL.first[MAX_LEVELS] * nTaxa;
+    extern __shared__ uint32_t tab[];                                  // [level][|T| - 1][nTaxa], TL.nn(level) values of |T| per level
+    const uint32_t cells = TL.rows * nTaxa;
     uint32_t *tabR = tab + cells;                                      // ... followed, when there is room (rangeCells), by [first level][nTaxa]
     const uint32_t rangeN = rangeCells ? (uint32_t)nK * nTaxa : 0u;
     __shared__ uint32_t sWave[PT_THREADS / 64];
@@ -5929,28 +5953,59 @@ __global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const u
     const uint64_t rounds = ((uint64_t)nKeys + step - 1) / step;
     // a workgroup sees at most `rounds * PT_THREADS * PT_KEYS` keys: with hits <= maxHits no 32-bit counter can wrap
     const uint32_t maxHits = (uint32_t)std::min<uint64_t>(65535ull, 0xFFFFFFFFull / std::max<uint64_t>(1, rounds * PT_THREADS * PT_KEYS));
+    // A round's keys: two neighbours per 16-byte load, four loads a thread, without a branch -- a pair past the end reads the first
+    // pair instead, and the odd last key's neighbour is there to be read (the key buffer is 64 bytes longer than its keys); what
+    // lies past the end becomes 0 (hits = 0: skipped) where the round takes its keys over.  The next round's keys are asked for
+    // before this round's are worked on: with one workgroup per CU nothing else hides the way to memory.
+    auto firstOf = [&](uint64_t rd, int q) { return rd * step + (uint64_t)blockIdx.x * PT_THREADS * PT_KEYS + (uint64_t)q * PT_THREADS + 2u * threadIdx.x; };
+    auto load = [&](uint64_t (&k)[PT_KEYS], uint64_t rd) {
+#pragma unroll
+        for (int q = 0; q < PT_KEYS; q += 2) {
+            const uint64_t i = firstOf(rd, q);
+            const ulonglong2 w = *reinterpret_cast<const ulonglong2 *>(keys + (i < nKeys ? i : 0ull));
+            k[q] = w.x; k[q + 1] = w.y;
+        }
+    };
+    uint64_t nx[PT_KEYS];
+    load(nx, 0);
     for (uint64_t rd = 0; rd < rounds; ++rd) {
-        const uint64_t i0 = rd * step + (uint64_t)blockIdx.x * PT_THREADS * PT_KEYS + threadIdx.x;
         uint64_t kk[PT_KEYS];
 #pragma unroll
-        for (int q = 0; q < PT_KEYS; ++q) { const uint64_t i = i0 + (uint64_t)q * PT_THREADS; kk[q] = i < nKeys ? keys[i] : 0ull; }   // (hits = 0: skipped)
-        // what a key's level does: 0 nothing, 1 a cell, 2 left over
-        auto levelsOf = [&](uint64_t key, auto cell, auto left) {
+        for (int q = 0; q < PT_KEYS; q += 2) {
+            const uint64_t i = firstOf(rd, q);
+            kk[q] = i < nKeys ? nx[q] : 0ull; kk[q + 1] = i + 1 < nKeys ? nx[q + 1] : 0ull;
+        }
+        load(nx, rd + 1);
+        // The levels a key spans and has not served yet: bit 8 q + level of `which` (narrow records: up to 8 levels).  |T| = 1 down to
+        // the shallowest level is ONE add to a range cell and spans nothing.  Then level by level, the level uniform and its nn / first
+        // row in scalar registers: the keys' LDS adds depend on nothing but the keys and issue back to back.  What is still set after
+        // the last level has no cell (|T| > nn, hits > maxHits, no table at all: nn = 0): the leftovers' marks.
+        uint32_t hitsOf[PT_KEYS], nm1[PT_KEYS], cellOf[PT_KEYS];
+        unsigned long long which = 0;
+#pragma unroll
+        for (int q = 0; q < PT_KEYS; ++q) {
+            const uint64_t key = kk[q];
             const uint32_t hits = (uint32_t)(key & 0xFFFFull);
-            if (hits == 0u) return;
             const uint32_t tax = (uint32_t)(key >> 16) & SEG_TAX_MASK, n = (uint32_t)(key >> 38) & 0x1FFFu;
             const uint32_t lvLo = (uint32_t)(key >> 51) & 31u, lvHi = lvLo + ((uint32_t)(key >> 56) & 31u);
-            if (rangeN && n == 1u && lvHi + 1u == (uint32_t)nK && hits <= maxHits) { cell(&tabR[lvLo * nTaxa + tax], hits); return; }
-            for (uint32_t lv = lvLo; lv <= lvHi; ++lv) {                     // (one pass over all levels: no level windows here)
-                if ((int)lv >= TL.lvLo && (int)lv < TL.lvHi && n >= 1u && n <= (uint32_t)TL.nn[lv] && hits <= maxHits) cell(&tab[((uint32_t)TL.first[lv] + (n - 1u)) * nTaxa + tax], hits);
-                else left(lv, n, tax, hits);
-            }
-        };
-        uint32_t nLeft = 0;
-        unsigned long long which = 0;                                        // the leftovers of this thread's keys: bit 8 q + level (up to 8 levels)
+            hitsOf[q] = hits;
+            nm1[q] = hits <= maxHits ? n - 1u : ~0u;                         // (n = 0 wraps: no cell either)
+            cellOf[q] = (n - 1u) * nTaxa + tax;                              // (used with n <= nn only)
+            if (hits == 0u) continue;
+            if (rangeN && n == 1u && lvHi + 1u == (uint32_t)nK && hits <= maxHits) { atomicAdd(&tabR[lvLo * nTaxa + tax], hits); continue; }
+            which |= (unsigned long long)(((2u << (lvHi & 7u)) - (1u << (lvLo & 7u))) & 255u) << (8 * q);
+        }
 #pragma unroll
-        for (int q = 0; q < PT_KEYS; ++q)
-            levelsOf(kk[q], [&](uint32_t *c, uint32_t hits) { atomicAdd(c, hits); }, [&](uint32_t lv, uint32_t, uint32_t, uint32_t) { ++nLeft; which |= 1ull << (8 * q + (int)(lv & 7u)); });
+        for (int lv = 0; lv < 8; ++lv) {
+            if (lv >= nK) break;                                             // (uniform)
+            const uint32_t nnL = TL.nn((uint32_t)lv), rowL = TL.first((uint32_t)lv) * nTaxa;
+#pragma unroll
+            for (int q = 0; q < PT_KEYS; ++q) {
+                const unsigned long long bit = 1ull << (8 * q + lv);
+                if ((which & bit) && nm1[q] < nnL) { atomicAdd(&tab[rowL + cellOf[q]], hitsOf[q]); which &= ~bit; }
+            }
+        }
+        const uint32_t nLeft = (uint32_t)__popcll(which);
         // the leftovers' places: running sum over the workgroup, one add to the list's cursor
         const uint32_t incl = wave_incl_sum(nLeft);
         if (lane == 63) sWave[wv] = incl;
@@ -5961,7 +6016,7 @@ __global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const u
         if (threadIdx.x == 0) sBase = atomicAdd(leftCursor, (unsigned long long)total);
         __syncthreads();
         unsigned long long at = sBase + before + incl - nLeft;
-        if (nLeft && nK <= 8) {                                              // straight from the marks
+        if (nLeft) {                                                          // straight from the marks
 #pragma unroll
             for (int q = 0; q < PT_KEYS; ++q) {
                 uint32_t m = (uint32_t)(which >> (8 * q)) & 255u;
@@ -5974,13 +6029,6 @@ __global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const u
                     ++at;
                 }
             }
-        } else if (nLeft) {
-#pragma unroll
-            for (int q = 0; q < PT_KEYS; ++q)
-                levelsOf(kk[q], [&](uint32_t *, uint32_t) {}, [&](uint32_t lv, uint32_t n, uint32_t tax, uint32_t hits) {
-                    if (at < leftCap) leftOut[at] = profile_key_of(lv, n, tax, hits, PL); else direct(lv, n, tax, hits);
-                    ++at;
-                });
         }
         __syncthreads();                                                     // (sWave, sBase are written again in the next round)
     }
@@ -6000,9 +6048,8 @@ __global__ __launch_bounds__(PT_THREADS) void profile_group_table_kernel(const u
         const uint32_t c = tab[i];
         if (!c) continue;
         const uint32_t tax = i % nTaxa, row = i / nTaxa;
-        uint32_t lv = 0;
-        while (row >= (uint32_t)TL.first[lv + 1]) ++lv;
-        const uint32_t n = row - (uint32_t)TL.first[lv] + 1u;
+        const uint32_t lv = TL.level_of_row(row);                       // (group keys: the window starts at level 0)
+        const uint32_t n = row - TL.first(lv) + 1u;
         const size_t cell = (size_t)lv * nTaxa + tax;
         if (n == 1u) atomicAdd((unsigned long long *)&cntUnique[cell], (unsigned long long)c);
         fixed_add(hiTab, midTab, loTab, cell, c, n);
@@ -6153,8 +6200,10 @@ static int profile_from_keys(kasa_ctx *c, uint64_t nKeys, bool grouped)
         unsigned long long *leftCursor = c->misc.as<unsigned long long>() + 19;
         unsigned long long left = 0;
         HIPCHK(hipMemsetAsync(leftCursor, 0, 8, ps));
-        for (const auto &TL : passes) {
-            const size_t shBytes = ((size_t)TL.first[MAX_LEVELS] * nTaxa + (rangeCells ? (size_t)nK * nTaxa : 0)) * 4;
+        for (const auto &L : passes) {
+            ProfTablePacked TL;
+            if (!prof_table_pack(L, TL) || (grouped && nK > 8)) return fail(KASA_E_LIMIT, "profile tables: a window of more than eight levels");
+            const size_t shBytes = ((size_t)TL.rows * nTaxa + (rangeCells ? (size_t)nK * nTaxa : 0)) * 4;
             HIPCHK(hipFuncSetAttribute((const void *)profile_table_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shBytes));
             if (grouped) {
                 HIPCHK(hipFuncSetAttribute((const void *)profile_group_table_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shBytes));
