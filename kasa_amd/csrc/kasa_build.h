@@ -262,14 +262,10 @@ static int unique_into(kasa_builder *b, Key *k, uint32_t *v, uint64_t n, int dro
     bld_flag_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, v, n, dropIllegal, f);
     HIPCHK(hipGetLastError());
     uint32_t last = 0;
-    HIPCHK(hipMemcpyAsync(&last, f + n - 1, 4, hipMemcpyDeviceToHost, b->stream));
-    size_t tmp = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmp, f, f, 0u, (size_t)n, rocprim::plus<uint32_t>(), b->stream));
-    if ((rc = b->scanTmp.reserve(tmp))) return rc;
-    HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, tmp, f, f, 0u, (size_t)n, rocprim::plus<uint32_t>(), b->stream));
+    if ((rc = fetch_async(b->stream, last, f + n - 1))) return rc;           // (the last flag, before the scan overwrites it)
+    if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, f, f, 0u, (size_t)n, rocprim::plus<uint32_t>()))) return rc;
     uint32_t lastPos = 0;
-    HIPCHK(hipMemcpyAsync(&lastPos, f + n - 1, 4, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    if ((rc = fetch(b->stream, lastPos, f + n - 1))) return rc;
     const uint64_t nu = (uint64_t)lastPos + last;
     if ((rc = out.k.reserve(nu * sizeof(Key) + 64)) || (rc = out.v.reserve(nu * 4 + 64))) return rc;
     bld_scatter_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, v, n, dropIllegal, f, out.k.as<Key>(), out.v.as<uint32_t>());
@@ -391,13 +387,9 @@ static int merge_two(kasa_builder *b, kasa_builder::Run &A, kasa_builder::Run &B
     bld_merge_kernel<Key, false><<<g, 256, 0, b->stream>>>(A.k.as<Key>(), A.v.as<uint32_t>(), A.n, B.k.as<Key>(), B.v.as<uint32_t>(), B.n, c, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(c + nT, 0, 8, b->stream));
-    size_t tmp = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmp, c, c, (uint64_t)0, (size_t)nT + 1, rocprim::plus<uint64_t>(), b->stream));
-    if ((rc = b->scanTmp.reserve(tmp))) return rc;
-    HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, tmp, c, c, (uint64_t)0, (size_t)nT + 1, rocprim::plus<uint64_t>(), b->stream));
+    if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, c, c, (uint64_t)0, (size_t)nT + 1, rocprim::plus<uint64_t>()))) return rc;
     uint64_t nu = 0;
-    HIPCHK(hipMemcpyAsync(&nu, c + nT, 8, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    if ((rc = fetch(b->stream, nu, c + nT))) return rc;
     if ((rc = out.k.reserve(nu * sizeof(Key) + 64)) || (rc = out.v.reserve(nu * 4 + 64))) return rc;
     bld_merge_kernel<Key, true><<<g, 256, 0, b->stream>>>(A.k.as<Key>(), A.v.as<uint32_t>(), A.n, B.k.as<Key>(), B.v.as<uint32_t>(), B.n, c, out.k.as<Key>(), out.v.as<uint32_t>());
     HIPCHK(hipGetLastError());
@@ -476,15 +468,10 @@ static int finish_impl(kasa_builder *b)
         bld_trie_flag_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, n, shift, f);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(p + n, 0, 8, b->stream));
-        size_t tmp = 0;
         rocprim::transform_iterator<const uint32_t *, rocprim::identity<uint64_t>, uint64_t> fin(f, rocprim::identity<uint64_t>());
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmp, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), b->stream));
-        if ((rc = b->scanTmp.reserve(tmp))) return rc;
-        HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, tmp, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), b->stream));
+        if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>()))) return rc;
         uint64_t lastPos = 0; uint32_t lastF = 0;
-        HIPCHK(hipMemcpyAsync(&lastPos, p + n - 1, 8, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipMemcpyAsync(&lastF, f + n - 1, 4, hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
+        if ((rc = fetch_async(b->stream, lastPos, p + n - 1)) || (rc = fetch(b->stream, lastF, f + n - 1))) return rc;
         b->nTrie = lastPos + lastF;
         if ((rc = b->trieFirst.reserve(b->nTrie * 8 + 64)) || (rc = b->triePrefix.reserve(b->nTrie * 4 + 64)) || (rc = b->trieCount.reserve(b->nTrie * 8 + 64))) return rc;
         bld_trie_scatter_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, n, shift, p, b->trieFirst.as<uint64_t>(), b->triePrefix.as<uint32_t>());

@@ -223,13 +223,10 @@ static int taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint6
     HIPCHK(hipMemcpyAsync(err, &bad, 8, hipMemcpyHostToDevice, b->stream));
     HIPCHK(hipMemsetAsync(d, 0, nBins * 8, b->stream));
     rocprim::transform_iterator<rocprim::counting_iterator<uint64_t>, EditHeadPos<Key>, uint64_t> in(rocprim::counting_iterator<uint64_t>(0), EditHeadPos<Key>{rec});
-    size_t tmp = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, tmp, in, head.as<uint64_t>(), (size_t)n, rocprim::maximum<uint64_t>(), b->stream));
-    if ((rc = b->scanTmp.reserve(tmp))) return rc;
-    HIPCHK(rocprim::inclusive_scan(b->scanTmp.p, tmp, in, head.as<uint64_t>(), (size_t)n, rocprim::maximum<uint64_t>(), b->stream));
+    if ((rc = dev_inclusive_scan(b->scanTmp, b->stream, in, head.as<uint64_t>(), (size_t)n, rocprim::maximum<uint64_t>()))) return rc;
     edit_taxa_hist_kernel<Key><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(rec, head.as<uint64_t>(), n, nBins, d, err);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, b->stream));
+    if ((rc = fetch_async(b->stream, bad, err))) return rc;
     HIPCHK(hipMemcpyAsync(hist, d, nBins * 8, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));                          // (head and bins go out of scope here)
     if (bad != ~0ull) {
@@ -250,15 +247,10 @@ static int compact_result(kasa_builder *b, const uint32_t *f)
     DevBuf pos;
     if ((rc = pos.reserve(n * 8 + 64))) return rc;
     uint64_t *p = pos.as<uint64_t>();
-    size_t tmp = 0;
     rocprim::transform_iterator<const uint32_t *, rocprim::identity<uint64_t>, uint64_t> fin(f, rocprim::identity<uint64_t>());
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmp, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), b->stream));
-    if ((rc = b->scanTmp.reserve(tmp))) return rc;
-    HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, tmp, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), b->stream));
+    if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>()))) return rc;
     uint64_t lastPos = 0; uint32_t lastF = 0;
-    HIPCHK(hipMemcpyAsync(&lastPos, p + n - 1, 8, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipMemcpyAsync(&lastF, f + n - 1, 4, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
+    if ((rc = fetch_async(b->stream, lastPos, p + n - 1)) || (rc = fetch(b->stream, lastF, f + n - 1))) return rc;
     const uint64_t nu = lastPos + lastF;
     if (nu == n) return KASA_OK;
     kasa_builder::Run out;
@@ -327,9 +319,9 @@ static int nth_flags(kasa_builder *b, uint32_t *f)
     if ((rc = kA.reserve(cm * 4 + 64)) || (rc = vA.reserve(cm * 4 + 64)) || (rc = kB.reserve(cm * 4 + 64)) || (rc = vB.reserve(cm * 4 + 64)) ||
         (rc = tmpSort.reserve(kasa_radix::scratch_bytes<uint32_t>(cm))))
         return rc;
-    size_t scanBytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, scanBytes, ch, start.as<uint64_t>(), (uint64_t)0, (size_t)nRank, rocprim::plus<uint64_t>(), b->stream));
-    if ((rc = b->scanTmp.reserve(scanBytes))) return rc;
+    auto starts = [&]() -> int {                                       // (every chunk scans nRank counts: the first call reserves)
+        return dev_exclusive_scan(b->scanTmp, b->stream, ch, start.as<uint64_t>(), (uint64_t)0, (size_t)nRank, rocprim::plus<uint64_t>());
+    };
     for (uint64_t c0 = 0; c0 < n; c0 += chunk) {
         const uint64_t m = std::min(chunk, n - c0);
         HIPCHK(hipMemcpyAsync(kA.p, v + c0, m * 4, hipMemcpyDeviceToDevice, b->stream));
@@ -338,7 +330,7 @@ static int nth_flags(kasa_builder *b, uint32_t *f)
         HIPCHK(kasa_radix::sort_pairs<uint32_t>(kA.as<uint32_t>(), vA.as<uint32_t>(), kB.as<uint32_t>(), vB.as<uint32_t>(), (uint32_t)m, 0, 24, tmpSort.p, b->stream, &sr, &si));
         HIPCHK(hipMemsetAsync(ch, 0, (size_t)nRank * 8, b->stream));
         hist(sr, m, ch);
-        HIPCHK(rocprim::exclusive_scan(b->scanTmp.p, scanBytes, ch, start.as<uint64_t>(), (uint64_t)0, (size_t)nRank, rocprim::plus<uint64_t>(), b->stream));
+        if ((rc = starts())) return rc;
         edit_nth_flag_kernel<<<grid_for(m), 256, 0, b->stream>>>(sr, si, m, start.as<uint64_t>(), car, dBits.as<uint32_t>(), (uint64_t)bits.size() * 32, f + c0);
         edit_carry_kernel<<<blocks_for(nRank, 256), 256, 0, b->stream>>>(car, ch, nRank);
         HIPCHK(hipGetLastError());
@@ -452,8 +444,7 @@ static int build_add_index_impl(kasa_builder *b, uint64_t first, uint64_t count,
             if (b->wide) edit_load_kernel<key128><<<grid_for(count), 256, 0, b->stream>>>(src, first, count, b->idOfRank.as<uint32_t>(), (uint32_t)b->ids.size(), run.k.as<key128>(), run.v.as<uint32_t>(), err);
             else edit_load_kernel<uint64_t><<<grid_for(count), 256, 0, b->stream>>>(src, first, count, b->idOfRank.as<uint32_t>(), (uint32_t)b->ids.size(), run.k.as<uint64_t>(), run.v.as<uint32_t>(), err);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&bad, err, 8, hipMemcpyDeviceToHost, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));
+            if ((rc = fetch(b->stream, bad, err))) return rc;
             clk.stop();
         }
         if (bad != ~0ull) {

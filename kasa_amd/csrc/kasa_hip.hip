@@ -138,6 +138,114 @@ struct DevBuf {
 };
 typedef DevBuf ScopedBuf;                                     // a function's own scratch
 
+// ---- the library's primitives --------------------------------------------------------------------------------------------
+// rocPRIM is called twice: without temporary storage for its size, then with it.  `tmp` is the buffer the SITE chooses (a
+// context's sortTmp or scanTmp, a builder's or a parser's own): work queued behind one may not share it with the other.
+template <class Call> static int dev_with_tmp(DevBuf &tmp, Call call)
+{
+    size_t bytes = 0;
+    HIPCHK(call(nullptr, bytes));
+    if (int rc = tmp.reserve(bytes)) return rc;
+    HIPCHK(call(tmp.p, bytes));
+    return KASA_OK;
+}
+// Templates over the iterator and value types: a site passes what it would pass to rocPRIM (pointers, counting and transform
+// iterators alike), so the instantiation is the site's own.
+template <class In, class Out, class Init, class Op>
+static int dev_exclusive_scan(DevBuf &tmp, hipStream_t stream, In in, Out out, Init init, size_t n, Op op)
+{
+    return dev_with_tmp(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, in, out, init, n, op, stream); });
+}
+template <class In, class Out, class Op>
+static int dev_inclusive_scan(DevBuf &tmp, hipStream_t stream, In in, Out out, size_t n, Op op)
+{
+    return dev_with_tmp(tmp, [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, in, out, n, op, stream); });
+}
+template <class KeyIn, class KeyOut, class ValIn, class ValOut>
+static int dev_sort_pairs(DevBuf &tmp, hipStream_t stream, KeyIn keysIn, KeyOut keysOut, ValIn valsIn, ValOut valsOut, size_t n, unsigned beginBit, unsigned endBit)
+{
+    return dev_with_tmp(tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, keysIn, keysOut, valsIn, valsOut, n, beginBit, endBit, stream); });
+}
+template <class KeyIn, class KeyOut, class ValIn, class ValOut, class Off>
+static int dev_segmented_sort_pairs(DevBuf &tmp, hipStream_t stream, KeyIn keysIn, KeyOut keysOut, ValIn valsIn, ValOut valsOut, unsigned n, unsigned segments,
+                                    Off segBegin, Off segEnd, unsigned beginBit, unsigned endBit)
+{
+    return dev_with_tmp(tmp, [&](void *t, size_t &b) { return rocprim::segmented_radix_sort_pairs(t, b, keysIn, keysOut, valsIn, valsOut, n, segments, segBegin, segEnd, beginBit, endBit, stream); });
+}
+
+// ---- small values back to the host: the byte count is the host object's -----------------------------------------------------
+// One value, a sub-struct of CtxCounters (below), or an array: as many elements as the host array has.
+template <class H, class D> static int fetch_async(hipStream_t stream, H &host, const D *dev)
+{
+    static_assert(std::is_same<typename std::remove_extent<H>::type, D>::value && std::is_trivially_copyable<D>::value, "fetch: host object and device pointer differ in type");
+    HIPCHK(hipMemcpyAsync(&host, dev, sizeof(H), hipMemcpyDeviceToHost, stream));
+    return KASA_OK;
+}
+template <class H, class D> static int fetch(hipStream_t stream, H &host, const D *dev)   // ... and the stream has finished
+{
+    if (int rc = fetch_async(stream, host, dev)) return rc;
+    HIPCHK(hipStreamSynchronize(stream));
+    return KASA_OK;
+}
+
+// ---- the context's counter block ------------------------------------------------------------------------------------------
+// 512 bytes of device memory (kasa_ctx::misc) that the kernels are handed addresses into; THIS struct is its map, and a new
+// counter is a new field here (with its static_assert), never a number at the site.  The host only ever takes addresses of
+// the fields (kasa_ctx::ctr()), it does not read through them.  Fields that are cleared or fetched in one call stand in one
+// sub-struct or array.  The offsets are the ones the block has always had -- 32-bit and 64-bit indices of one array.
+struct ScoreFlags { uint32_t err, fallbacks; };               // score kernels: error bits (2: more than PCAP groups pending); reads handed to the slower kernels
+// cursor[0..3] by name; the halves of cursor[3] while group_stage runs: "a list too long for the lean kernel", tiles group2_kernel listed
+struct GroupCursors { unsigned long long pool, staging, profKeys; uint32_t needCoop, listedTiles; };
+struct UploadFlags { uint32_t errBits, maxKmers; };           // upload_geometry_kernel: 1 offsets descend, 2 a bad read id; most k-mers of a read
+struct LongBuckets { uint32_t count, longest; };              // bucket_rank*: buckets too long to rank by counting; bucket_bounds_kernel: the longest of them
+struct CohExits { uint32_t walked[2], anyFail; };             // coh_chunk_kernel: chunks that left elsewhere than a round before, at the same place; coh_any_kernel
+// esr_stage (kasa_replay.h): reads esr_split_kernel listed as long, as short; first staging record of a round's chains; its big chains
+struct ReplayCounters { uint32_t split[2]; unsigned long long rowBase; uint32_t bigChains; };
+struct CtxCounters {
+    uint32_t unused0[2];
+    ScoreFlags score;                                         // u32 [2], [3]
+    uint32_t longestListed, secondPass;                       // [4] most k-mers of a read a later general pass is given, [5] reads the first pass hands on
+    uint32_t workCursor, thirdPass;                           // [6] score_main_kernel: next 64 reads, [7] reads the second general pass hands on (narrow records)
+    uint32_t why[8];                                          // [8..15] hand-over reasons of the fast kernels (kasa_ctx_debug)
+    uint32_t unused1[16];
+    union {                                                   // u64 [16..19]: ONE array to group_kernel and group2_kernel
+        unsigned long long cursor[4];                         // pool (starts at 1), staging records, profile keys, and [3]: two tenants, one
+        GroupCursors group;                                   // after the other -- group_stage's flag word (GroupCursors), then the cursor of the
+    };                                                        // keys profile_from_keys' table pass leaves over (CUR_LEFT_OVER)
+    unsigned long long rankCursor;                            // u64 [20]
+    uint32_t rankFlagged;                                     // u32 [42]
+    LongBuckets sortBig;                                      // [43], [44]
+    uint32_t rankListLen;                                     // [45]
+    UploadFlags upload;                                       // [46], [47]
+    unsigned long long uploadErrAt[2];                        // u64 [24], [25] first offending sequence per error bit
+    unsigned long long cohFirstMatch;                         // u64 [26]
+    CohExits coh;                                             // u32 [54..56]
+    uint32_t unused2[3];
+    unsigned long long scoreKeyCursor;                        // u64 [30] where the score kernels of NARROW records count the keys they do not write (wide ones: cursor[CUR_PROF_KEYS])
+    uint32_t unused3[2];
+    uint32_t rankClass[4];                                    // u32 [64..67] flagged reads per class of hit count
+    uint32_t unused4[2];
+    uint32_t denseHanded;                                     // [70] reads score_dense_kernel hands to the general kernel
+    uint32_t unused5;
+    ReplayCounters replay;                                    // [72..77]
+    uint32_t group2Second;                                   // [78] tiles group2_kernel's second chance lists again
+    uint32_t unused7[5];
+    uint32_t rowClass[3];                                     // [84..86] rows score_main_kernel lists for the second, third and long row-merge class
+};
+enum { CUR_POOL = 0, CUR_STAGING = 1, CUR_PROF_KEYS = 2, CUR_GROUP_FLAG = 3, CUR_LEFT_OVER = 3 };   // CtxCounters::cursor
+static constexpr size_t CTX_COUNTER_BYTES = 512;
+#define KASA_CTR_AT(field, bytes) static_assert(offsetof(CtxCounters, field) == (bytes), "CtxCounters::" #field " moved: the kernels address it by this offset")
+KASA_CTR_AT(score, 2 * 4); KASA_CTR_AT(score.err, 2 * 4); KASA_CTR_AT(score.fallbacks, 3 * 4);
+KASA_CTR_AT(longestListed, 4 * 4); KASA_CTR_AT(secondPass, 5 * 4); KASA_CTR_AT(workCursor, 6 * 4); KASA_CTR_AT(thirdPass, 7 * 4); KASA_CTR_AT(why, 8 * 4);
+KASA_CTR_AT(cursor, 16 * 8); KASA_CTR_AT(group.pool, 16 * 8); KASA_CTR_AT(group.staging, 17 * 8); KASA_CTR_AT(group.profKeys, 18 * 8);
+KASA_CTR_AT(group.needCoop, 19 * 8); KASA_CTR_AT(group.listedTiles, 19 * 8 + 4);
+KASA_CTR_AT(rankCursor, 20 * 8); KASA_CTR_AT(rankFlagged, 42 * 4); KASA_CTR_AT(sortBig.count, 43 * 4); KASA_CTR_AT(sortBig.longest, 44 * 4); KASA_CTR_AT(rankListLen, 45 * 4);
+KASA_CTR_AT(upload.errBits, 46 * 4); KASA_CTR_AT(upload.maxKmers, 47 * 4); KASA_CTR_AT(uploadErrAt, 24 * 8); KASA_CTR_AT(cohFirstMatch, 26 * 8); KASA_CTR_AT(coh.walked, 54 * 4); KASA_CTR_AT(coh.anyFail, 56 * 4);
+KASA_CTR_AT(scoreKeyCursor, 30 * 8); KASA_CTR_AT(rankClass, 64 * 4); KASA_CTR_AT(denseHanded, 70 * 4);
+KASA_CTR_AT(replay.split, 72 * 4); KASA_CTR_AT(replay.rowBase, 74 * 4); KASA_CTR_AT(replay.bigChains, 76 * 4); KASA_CTR_AT(group2Second, 78 * 4); KASA_CTR_AT(rowClass, 84 * 4);
+#undef KASA_CTR_AT
+static_assert(sizeof(CtxCounters) <= CTX_COUNTER_BYTES, "the counter block is allocated once, with the context");
+
 // ---- a buffer that takes random 32-byte stores is CHOSEN ---------------------------------------------------------------
 // The rate at which this chip takes random 32-byte stores is a property of the PHYSICAL memory a buffer got: 21.2, 25.8, 27.2
 // or 28.4 G records/s for 34 GB pieces of one device, the same piece always the same and whatever virtual address it is
@@ -494,7 +602,7 @@ static int index_create_impl(int device, const void *records, uint64_t nRecords,
         dense_tax_kernel<<<blocks_for(n, 256), 256>>>(ix->tax.as<uint32_t>(), n, ids.as<uint32_t>(), dense.as<uint32_t>(), nTaxa, bad.as<uint32_t>() + 1);
     }
     uint32_t hbad[4] = {0, 0, 0, 0};
-    TRYHIP(hipMemcpy(hbad, bad.p, 16, hipMemcpyDeviceToHost));
+    TRYHIP(hipMemcpy(hbad, bad.p, sizeof(hbad), hipMemcpyDeviceToHost));
     if (hbad[0]) return cleanup(fail(KASA_E_ARG, "kasa_index_create: the index is not sorted by (kmer, taxid), not unique, or uses more than %d key bits (%u violations)", T::BITS, hbad[0]));
     if (hbad[1]) return cleanup(fail(KASA_E_ARG, "kasa_index_create: %u index entries carry a tax ID the content file does not know", hbad[1]));
 
@@ -503,15 +611,10 @@ static int index_create_impl(int device, const void *records, uint64_t nRecords,
     {
         TRY(order.reserve(n * 4));
         TRY(taxSorted.reserve(n * 4));
-        size_t tmpBytes = 0;
         unsigned bits = 1;
         while ((1ull << bits) < nTaxa) ++bits;
         rocprim::counting_iterator<uint32_t> cnt(0);
-        TRYHIP(rocprim::radix_sort_pairs(nullptr, tmpBytes, ix->tax.as<uint32_t>(), taxSorted.as<uint32_t>(), cnt,
-                                         order.as<uint32_t>(), (size_t)n, 0u, bits, (hipStream_t)0));
-        TRY(tmp.reserve(tmpBytes));
-        TRYHIP(rocprim::radix_sort_pairs(tmp.p, tmpBytes, ix->tax.as<uint32_t>(), taxSorted.as<uint32_t>(), cnt,
-                                         order.as<uint32_t>(), (size_t)n, 0u, bits, (hipStream_t)0));
+        TRY(dev_sort_pairs(tmp, (hipStream_t)0, ix->tax.as<uint32_t>(), taxSorted.as<uint32_t>(), cnt, order.as<uint32_t>(), (size_t)n, 0u, bits));
         dup_level_kernel<Key><<<blocks_for(n, 256), 256>>>(taxSorted.as<uint32_t>(), order.as<uint32_t>(), ix->kmer.as<Key>(), n, ix->meta.as<Meta>());
         TRYHIP(hipDeviceSynchronize());
         order.release(); taxSorted.release();
@@ -525,10 +628,7 @@ static int index_create_impl(int device, const void *records, uint64_t nRecords,
         TRY(ix->table.reserve(nb * 4));
         TRYHIP(hipMemset(ix->table.p, 0, nb * 4));
         table_mark_kernel<Key><<<blocks_for(n, 256), 256>>>(ix->kmer.as<Key>(), n, T::BITS - tb, ix->table.as<uint32_t>());
-        size_t tmpBytes = 0;
-        TRYHIP(rocprim::inclusive_scan(nullptr, tmpBytes, ix->table.as<uint32_t>(), ix->table.as<uint32_t>(), (size_t)nb, rocprim::maximum<uint32_t>(), (hipStream_t)0));
-        TRY(tmp.reserve(tmpBytes));
-        TRYHIP(rocprim::inclusive_scan(tmp.p, tmpBytes, ix->table.as<uint32_t>(), ix->table.as<uint32_t>(), (size_t)nb, rocprim::maximum<uint32_t>(), (hipStream_t)0));
+        TRY(dev_inclusive_scan(tmp, (hipStream_t)0, ix->table.as<uint32_t>(), ix->table.as<uint32_t>(), (size_t)nb, rocprim::maximum<uint32_t>()));
     }
     // the reference's `_trie` file, when given, must describe the same ranges (Trie.hpp:398-462)
     if (triePrefix && trieCount && nTrie) {
@@ -542,7 +642,7 @@ static int index_create_impl(int device, const void *records, uint64_t nRecords,
         TRYHIP(hipMemcpy(tcount.p, trieCount, nTrie * 8, hipMemcpyHostToDevice));
         TRYHIP(hipMemset(bad.p, 0, 16));
         trie_check_kernel<Key><<<blocks_for(nTrie, 256), 256>>>(tpre.as<uint32_t>(), tstart.as<uint64_t>(), tcount.as<uint64_t>(), nTrie, ix->kmer.as<Key>(), n, bad.as<uint32_t>());
-        TRYHIP(hipMemcpy(hbad, bad.p, 16, hipMemcpyDeviceToHost));
+        TRYHIP(hipMemcpy(hbad, bad.p, sizeof(hbad), hipMemcpyDeviceToHost));
         if (hbad[0]) return cleanup(fail(KASA_E_ARG, "kasa_index_create: the trie file does not match the index (%u ranges differ)", hbad[0]));
     }
     TRYHIP(hipDeviceSynchronize());
@@ -630,6 +730,7 @@ struct kasa_ctx {
     int lookupMode = 0;                        // 0 = streaming tiles, 1 = per-query search only
     DevBuf rec;                                // event records, recWords() u32 each, by slot
     DevBuf pool, plist, sortTmp, misc;         // taxon segment lists, positions by read (slot fix-up), rocPRIM temp, counters
+    CtxCounters *ctr() const { return static_cast<CtxCounters *>(misc.p); }  // DEVICE address of the counter block: for `&ctr()->field`, not for reading
     DevBuf recIn;                              // imported records in sorted order, before they go to their slots
     DevBuf slotBuf;                            // u32[nQ]: slot of every sorted position when it does not come out of the sort
     const uint32_t *slotOf = nullptr;          // slot of sorted position p (payload of the sort, or slotBuf); NULL: not known yet
@@ -715,26 +816,36 @@ static void coh_forget(kasa_ctx *c)                                  // the batc
     g_cohSeams.erase(c->cohKey);
 }
 
-static int timer_begin(kasa_ctx *c, StageTimer &t, hipEvent_t *a, hipEvent_t *b)
-{
-    auto get = [&](hipEvent_t *e) -> int {
-        if (!t.pool.empty()) { *e = t.pool.back(); t.pool.pop_back(); return KASA_OK; }
-        HIPCHK(hipEventCreate(e));
+// One timed span of the context's stream, filed with a StageTimer: begin() takes two events from the timer's pool and records
+// the first, end() records the second and files the pair (timer_resolve reads it).  A span that is left before its end()
+// -- an early return -- hands its events back to the pool.  It can be begun again after end(): the score stage's span is
+// closed around every wait of the host.
+class Span {
+    kasa_ctx *c; StageTimer &t;
+    hipEvent_t a = nullptr, b = nullptr;
+public:
+    Span(kasa_ctx *c, StageTimer &t) : c(c), t(t) {}
+    Span(const Span &) = delete;
+    ~Span() { for (hipEvent_t e : {a, b}) if (e) t.pool.push_back(e); }
+    bool open() const { return a != nullptr; }
+    int begin()
+    {
+        for (hipEvent_t *e : {&a, &b}) {
+            if (!t.pool.empty()) { *e = t.pool.back(); t.pool.pop_back(); }
+            else HIPCHK(hipEventCreate(e));
+        }
+        HIPCHK(hipEventRecord(a, c->stream));
         return KASA_OK;
-    };
-    int rc = get(a); if (rc) return rc;
-    rc = get(b); if (rc) return rc;
-    HIPCHK(hipEventRecord(*a, c->stream));
-    return KASA_OK;
-}
-
-static int timer_end(kasa_ctx *c, StageTimer &t, hipEvent_t a, hipEvent_t b)
-{
-    HIPCHK(hipEventRecord(b, c->stream));
-    t.open.emplace_back(a, b);
-    t.launches++;
-    return KASA_OK;
-}
+    }
+    int end()
+    {
+        HIPCHK(hipEventRecord(b, c->stream));
+        t.open.emplace_back(a, b);
+        t.launches++;
+        a = b = nullptr;
+        return KASA_OK;
+    }
+};
 
 static int timer_resolve(StageTimer &t)
 {
@@ -799,7 +910,7 @@ extern "C" int kasa_ctx_create(const kasa_index *ix, int kHigh, int kLow, int fr
     if (hipMemcpy(c->lut.p, lut, 366, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(KASA_E_HIP, "LUT upload failed"));
     const size_t cells = (size_t)c->nK * ix->nTaxa * 8;
     if ((rc = c->cntUnique.reserve(cells)) || (rc = c->cntTotal.reserve(cells)) || (rc = c->cntAllHi.reserve(cells)) ||
-        (rc = c->cntAllMid.reserve(cells)) || (rc = c->cntAllLo.reserve(cells)) || (rc = c->misc.reserve(512)))
+        (rc = c->cntAllMid.reserve(cells)) || (rc = c->cntAllLo.reserve(cells)) || (rc = c->misc.reserve(CTX_COUNTER_BYTES)))
         return bail(rc);
     *out = c;
     rc = kasa_profile_reset(c);
@@ -920,14 +1031,12 @@ static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets
     const int64_t zero = 0;
     if (nSeq == 0) { offsets = &zero; resident = false; }
     int64_t ends[2] = {0, 0};                                               // offsets[0], offsets[nSeq]
+    int rc;
     if (resident) {
-        HIPCHK(hipMemcpyAsync(&ends[0], offsets, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&ends[1], offsets + nSeq, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = fetch_async(c->stream, ends[0], offsets)) || (rc = fetch(c->stream, ends[1], offsets + nSeq))) return rc;
     } else { ends[0] = offsets[0]; ends[1] = offsets[nSeq]; }
     if (ends[1] < ends[0]) return fail(KASA_E_ARG, "kasa_batch_upload: offsets are not ascending");
     const uint64_t nBases = (uint64_t)(ends[1] - ends[0]);
-    int rc;
     const bool inPlace = resident && !ownCopy;
     if ((rc = inPlace ? KASA_OK : c->bases.reserve(nBases + 64)) || (rc = c->baseOff.reserve(((size_t)nSeq + 1) * 8)) ||
         (rc = c->kmerOff.reserve(((size_t)nReads + 1) * 8)) || (rc = c->seqOff.reserve(((size_t)nSeq + 1) * 8)) ||
@@ -942,36 +1051,30 @@ static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets
     c->haveSeqRead = seqRead != nullptr;
     if (seqRead && nSeq) HIPCHK(hipMemcpyAsync(c->seqRead.p, seqRead, (size_t)nSeq * 4, hipMemcpyHostToDevice, c->stream));
     // device: counts, checks, running sums
-    uint32_t *flags = c->misc.as<uint32_t>() + 46;                      // [46] error bits, [47] most k-mers of a read
-    unsigned long long *errAt = c->misc.as<unsigned long long>() + 24;  // [24], [25]: first offending sequence per error
-    HIPCHK(hipMemsetAsync(flags, 0, 8, c->stream));
-    HIPCHK(hipMemsetAsync(errAt, 0xFF, 16, c->stream));
+    UploadFlags *flags = &c->ctr()->upload;
+    unsigned long long *errAt = c->ctr()->uploadErrAt;                  // first offending sequence per error
+    HIPCHK(hipMemsetAsync(flags, 0, sizeof(UploadFlags), c->stream));
+    HIPCHK(hipMemsetAsync(errAt, 0xFF, sizeof(CtxCounters::uploadErrAt), c->stream));
     uint64_t *seqCnt = c->seqOff.as<uint64_t>(), *readCnt = c->kmerOff.as<uint64_t>();
     HIPCHK(hipMemsetAsync(readCnt, 0, ((size_t)nReads + 1) * 8, c->stream));
     upload_geometry_kernel<<<blocks_for((uint64_t)nSeq + 1, 256), 256, 0, c->stream>>>(c->rawOff.as<int64_t>(), nSeq, seqRead ? c->seqRead.as<uint32_t>() : nullptr, nReads,
-        c->enc_mode(), c->K(), c->kLow, c->strands(), c->baseOff.as<int64_t>(), seqCnt, readCnt, flags, errAt, flags + 1);
+        c->enc_mode(), c->K(), c->kLow, c->strands(), c->baseOff.as<int64_t>(), seqCnt, readCnt, &flags->errBits, errAt, &flags->maxKmers);
     HIPCHK(hipGetLastError());
-    if (nReads) upload_max_kernel<<<std::min<unsigned>(blocks_for((uint64_t)nReads, 256), 2048u), 256, 0, c->stream>>>(readCnt, nReads, flags + 1);
-    size_t tmpBytes = 0, tmp2 = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, seqCnt, seqCnt, (uint64_t)0, (size_t)nSeq + 1, rocprim::plus<uint64_t>(), c->stream));
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmp2, readCnt, readCnt, (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>(), c->stream));
-    if ((rc = c->sortTmp.reserve(std::max(tmpBytes, tmp2)))) return rc;
-    HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, seqCnt, seqCnt, (uint64_t)0, (size_t)nSeq + 1, rocprim::plus<uint64_t>(), c->stream));
-    HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmp2, readCnt, readCnt, (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>(), c->stream));
-    uint32_t hFlags[2] = {0, 0};
+    if (nReads) upload_max_kernel<<<std::min<unsigned>(blocks_for((uint64_t)nReads, 256), 2048u), 256, 0, c->stream>>>(readCnt, nReads, &flags->maxKmers);
+    // (as a rule the second scan finds its room reserved: there are seldom more reads than sequences)
+    if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, seqCnt, seqCnt, (uint64_t)0, (size_t)nSeq + 1, rocprim::plus<uint64_t>())) ||
+        (rc = dev_exclusive_scan(c->sortTmp, c->stream, readCnt, readCnt, (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>()))) return rc;
+    UploadFlags hFlags = {0, 0};
     unsigned long long hAt[2] = {0, 0};
     uint64_t run = 0;
-    HIPCHK(hipMemcpyAsync(hFlags, flags, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hAt, errAt, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&run, seqCnt + nSeq, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (hFlags[0] & 1u) return fail(KASA_E_ARG, "kasa_batch_upload: offsets are not ascending");
-    if (hFlags[0] & 2u) {
+    if ((rc = fetch_async(c->stream, hFlags, flags)) || (rc = fetch_async(c->stream, hAt, errAt)) || (rc = fetch(c->stream, run, seqCnt + nSeq))) return rc;
+    if (hFlags.errBits & 1u) return fail(KASA_E_ARG, "kasa_batch_upload: offsets are not ascending");
+    if (hFlags.errBits & 2u) {
         const int64_t sq = (int64_t)hAt[1];
         return fail(KASA_E_ARG, "kasa_batch_upload: sequence %lld names read %u (reads: %lld, ids must ascend)", (long long)sq, seqRead ? seqRead[sq] : (uint32_t)sq, (long long)nReads);
     }
     if (run >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_upload: %llu k-mers exceed the 32-bit position range of one batch; split the batch", (unsigned long long)run);
-    c->nQ = run; c->nEmitted = run; c->uniqueDone = false; c->readsUploaded = true; c->nBases = nBases; c->maxCnt = hFlags[1];
+    c->nQ = run; c->nEmitted = run; c->uniqueDone = false; c->readsUploaded = true; c->nBases = nBases; c->maxCnt = hFlags.maxKmers;
     c->state = 1;
     return KASA_OK;
 }
@@ -1372,8 +1475,7 @@ extern "C" int kasa_batch_encode(kasa_ctx *c, uint64_t *nKmers)
     const uint64_t nQ = c->nQ;
     coh_forget(c);                                                          // (an open coherence seam points into qKmerA)
     if ((rc = c->qKmerA.reserve(nQ * c->keyBytes() + 64)) || (rc = c->qReadA.reserve(nQ * 4 + 64))) return rc;
-    hipEvent_t a, b;
-    if ((rc = timer_begin(c, c->timers[KASA_STAGE_ENCODE], &a, &b))) return rc;
+    Span stage(c, c->timers[KASA_STAGE_ENCODE]); if ((rc = stage.begin())) return rc;
     // the encoder ranks a read's k-mers itself (payload of the sort = slot) when every read is one sequence with few enough
     // k-mers; else the payload is the read id and the slots come from a stable sort by read (slots_from_reads)
     const int rankSlots = (!c->haveSeqRead && c->maxCnt <= (uint32_t)ENC_RANK_MAX && !(c->debugFlags & 8)) ? 1 : 0;
@@ -1421,7 +1523,7 @@ extern "C" int kasa_batch_encode(kasa_ctx *c, uint64_t *nKmers)
             HIPCHK(hipGetLastError());
         }
     }
-    if ((rc = timer_end(c, c->timers[KASA_STAGE_ENCODE], a, b))) return rc;
+    if ((rc = stage.end())) return rc;
     c->qKmer = c->qKmerA.p;
     c->qRead = c->qReadA.as<uint32_t>();
     c->state = 2;
@@ -2038,17 +2140,11 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
     uint64_t nQ = c->nQ;
     int rc;
     if ((rc = c->qKmerB.reserve(nQ * sizeof(Key) + 64)) || (rc = c->qReadB.reserve(nQ * 4 + 64))) return rc;
-    hipEvent_t a, b;
-    if ((rc = timer_begin(c, c->timers[KASA_STAGE_SORT], &a, &b))) return rc;
+    Span stage(c, c->timers[KASA_STAGE_SORT]); if ((rc = stage.begin())) return rc;
     if (nQ > 0) {
         const unsigned BITS = (unsigned)KeyTraits<Key>::BITS;
         auto radix = [&](DevBuf &kIn, DevBuf &vIn, DevBuf &kOut, DevBuf &vOut, unsigned lo, unsigned hi) -> int {
-            size_t tmpBytes = 0;
-            HIPCHK(rocprim::radix_sort_pairs(nullptr, tmpBytes, kIn.as<Key>(), kOut.as<Key>(), vIn.as<uint32_t>(), vOut.as<uint32_t>(), (size_t)nQ, lo, hi, c->stream));
-            int rc2 = c->sortTmp.reserve(tmpBytes);
-            if (rc2) return rc2;
-            HIPCHK(rocprim::radix_sort_pairs(c->sortTmp.p, tmpBytes, kIn.as<Key>(), kOut.as<Key>(), vIn.as<uint32_t>(), vOut.as<uint32_t>(), (size_t)nQ, lo, hi, c->stream));
-            return KASA_OK;
+            return dev_sort_pairs(c->sortTmp, c->stream, kIn.as<Key>(), kOut.as<Key>(), vIn.as<uint32_t>(), vOut.as<uint32_t>(), (size_t)nQ, lo, hi);
         };
         if (c->debugFlags & 64) {                                       // test tap: the library sort over all key bits
             if ((rc = radix(c->qKmerA, c->qReadA, c->qKmerB, c->qReadB, 0u, BITS))) return rc;
@@ -2059,7 +2155,7 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
             // form of rounds 2-3 (measured at C3: a pass costs 12.6 ms, the longer buckets with 128-bit compares 14.4).  Test
             // tap 2097152: the other choice.
             const unsigned top = ((sizeof(Key) == 8) != ((c->debugFlags & 2097152) != 0)) ? SORT_TOP : SORT_TOP_OLD;
-            uint32_t *big = c->misc.as<uint32_t>() + 43, *longest = c->misc.as<uint32_t>() + 44;
+            uint32_t *big = &c->ctr()->sortBig.count, *longest = &c->ctr()->sortBig.longest;
             if ((rc = c->sortBig.reserve((size_t)SORT_BIG_CAP * 12 + 64))) return rc;
             uint32_t *bigHead = c->sortBig.as<uint32_t>(), *segBegin = bigHead + SORT_BIG_CAP, *segEnd = segBegin + SORT_BIG_CAP;
             if (c->debugFlags & 512) {                                  // test tap: the library's passes over the same bits
@@ -2068,17 +2164,15 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
                 // the hand-written passes (kasa_radix.h): A -> B -> A ... ; four passes end in A, which then takes B's name
                 if ((rc = c->sortTmp.reserve(kasa_radix::scratch_bytes<Key>(nQ)))) return rc;
                 Key *kRes; uint32_t *vRes;
-                hipEvent_t ka, kb;
-                if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_SORT_PASSES], &ka, &kb))) return rc;
+                Span passes(c, c->kernels[KASA_KERNEL_SORT_PASSES]); if ((rc = passes.begin())) return rc;
                 HIPCHK(kasa_radix::sort_pairs<Key>(c->qKmerA.as<Key>(), c->qReadA.as<uint32_t>(), c->qKmerB.as<Key>(), c->qReadB.as<uint32_t>(), (uint32_t)nQ,
                                                    (int)(BITS - top), (int)top, c->sortTmp.p, c->stream, &kRes, &vRes, (c->debugFlags & 524288) ? kasa_radix::MODE_FIRST : 0));   // (test tap 524288: the look-back before the keys are ordered in LDS)
-                if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SORT_PASSES], ka, kb))) return rc;
+                if ((rc = passes.end())) return rc;
                 if (kRes == c->qKmerA.as<Key>() && (top / 8) % 2 == 0) { std::swap(c->qKmerA, c->qKmerB); std::swap(c->qReadA, c->qReadB); }   // (an even number of passes ends where it began)
                 if (kRes != c->qKmerB.as<Key>()) return fail(KASA_E_HIP, "query sort: unexpected result buffer");
             }
-            HIPCHK(hipMemsetAsync(big, 0, 8, c->stream));
-            hipEvent_t ra, rb;
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_BUCKET_RANK], &ra, &rb))) return rc;
+            HIPCHK(hipMemsetAsync(&c->ctr()->sortBig, 0, sizeof(LongBuckets), c->stream));
+            Span rank(c, c->kernels[KASA_KERNEL_BUCKET_RANK]); if ((rc = rank.begin())) return rc;
             static_assert(KeyTraits<uint64_t>::BITS - SORT_TOP_OLD + 12 <= 32, "bucket_rank32_kernel: low key bits and window position share a word");
             static_assert(KeyTraits<uint64_t>::BITS - SORT_TOP + 12 <= 52, "bucket_rank64_kernel: low key bits and window position share a word");
             if (sizeof(Key) == 8 && top != SORT_TOP_OLD && !(c->debugFlags & 4194304))   // (test tap 4194304: the kernel for any key width)
@@ -2094,10 +2188,9 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
                 bucket_rank_kernel<Key><<<blocks_for(nQ, RANK_TILE), 256, 0, c->stream>>>(c->qKmerB.as<Key>(), c->qReadB.as<uint32_t>(), c->qKmerA.as<Key>(),
                                                                                           c->qReadA.as<uint32_t>(), (uint32_t)nQ, (int)(BITS - top), big, bigHead);
             HIPCHK(hipGetLastError());
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_BUCKET_RANK], ra, rb))) return rc;
+            if ((rc = rank.end())) return rc;
             uint32_t hBig = 0;
-            HIPCHK(hipMemcpyAsync(&hBig, big, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
+            if ((rc = fetch(c->stream, hBig, big))) return rc;
             if (hBig) {
                 // buckets too long to rank by counting (an input that repeats itself) were copied through as they are:
                 // each of them is sorted by the remaining bits on its own (segmented radix sort, B -> A in place of the
@@ -2108,16 +2201,11 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
                     bucket_bounds_kernel<Key><<<blocks_for(hBig, 256), 256, 0, c->stream>>>(c->qKmerB.as<Key>(), (uint32_t)nQ, (int)(BITS - top), bigHead, hBig,
                                                                                          segBegin, segEnd, longest);
                     HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpyAsync(&hLongest, longest, 4, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(hipStreamSynchronize(c->stream));
+                    if ((rc = fetch(c->stream, hLongest, longest))) return rc;
                 }
                 if (hBig <= SORT_BIG_CAP && hLongest <= SORT_BIG_LONGEST && !(c->debugFlags & 128)) {   // (test tap 128: the last resort)
-                    size_t tmpBytes = 0;
-                    HIPCHK(rocprim::segmented_radix_sort_pairs(nullptr, tmpBytes, c->qKmerB.as<Key>(), c->qKmerA.as<Key>(), c->qReadB.as<uint32_t>(), c->qReadA.as<uint32_t>(),
-                                                               (unsigned)nQ, hBig, segBegin, segEnd, 0u, BITS - top, c->stream));
-                    if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-                    HIPCHK(rocprim::segmented_radix_sort_pairs(c->sortTmp.p, tmpBytes, c->qKmerB.as<Key>(), c->qKmerA.as<Key>(), c->qReadB.as<uint32_t>(), c->qReadA.as<uint32_t>(),
-                                                               (unsigned)nQ, hBig, segBegin, segEnd, 0u, BITS - top, c->stream));
+                    if ((rc = dev_segmented_sort_pairs(c->sortTmp, c->stream, c->qKmerB.as<Key>(), c->qKmerA.as<Key>(), c->qReadB.as<uint32_t>(), c->qReadA.as<uint32_t>(),
+                                                       (unsigned)nQ, hBig, segBegin, segEnd, 0u, BITS - top))) return rc;
                 } else if ((rc = radix(c->qKmerB, c->qReadB, c->qKmerA, c->qReadA, 0u, BITS))) return rc;
             }
             std::swap(c->qKmerA, c->qKmerB);                            // the sorted pairs are in "B" again
@@ -2139,16 +2227,12 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
         if ((rc = c->rep.reserve(nQ * 4 + 64))) return rc;            // rep is free until the lookup: slots of the survivors
         uint32_t *slot = c->rep.as<uint32_t>();
         unique_flag_kernel<Key><<<blocks_for(nQ, 256), 256, 0, c->stream>>>(c->keys<Key>(), c->qRead, (uint32_t)nQ, slot);
-        size_t tmpBytes = 0;
-        HIPCHK(rocprim::inclusive_scan(nullptr, tmpBytes, slot, slot, (size_t)nQ, rocprim::plus<uint32_t>(), c->stream));
-        if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-        HIPCHK(rocprim::inclusive_scan(c->sortTmp.p, tmpBytes, slot, slot, (size_t)nQ, rocprim::plus<uint32_t>(), c->stream));
+        if ((rc = dev_inclusive_scan(c->sortTmp, c->stream, slot, slot, (size_t)nQ, rocprim::plus<uint32_t>()))) return rc;
         unique_scatter_kernel<Key><<<blocks_for(nQ, 256), 256, 0, c->stream>>>(c->keys<Key>(), c->qRead, (uint32_t)nQ, slot,
             c->qKmerA.as<Key>(), c->qReadA.as<uint32_t>());
         HIPCHK(hipGetLastError());
         uint32_t kept = 0;
-        HIPCHK(hipMemcpyAsync(&kept, slot + (nQ - 1), 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = fetch(c->stream, kept, slot + (nQ - 1)))) return rc;
         nQ = c->nQ = kept; c->uniqueDone = true;
         // back into the "sorted" buffers: later stages reuse the A buffers as scratch
         HIPCHK(hipMemcpyAsync(c->qKmerB.p, c->qKmerA.p, nQ * sizeof(Key), hipMemcpyDeviceToDevice, c->stream));
@@ -2157,11 +2241,9 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
         uint64_t *ko = c->kmerOff.as<uint64_t>();
         HIPCHK(hipMemsetAsync(ko, 0, ((size_t)c->nReads + 1) * 8, c->stream));
         read_count_kernel<<<blocks_for(nQ, 256), 256, 0, c->stream>>>(c->qReadB.as<uint32_t>(), (uint32_t)nQ, ko);
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, ko, ko, (uint64_t)0, (size_t)c->nReads + 1, rocprim::plus<uint64_t>(), c->stream));
-        if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-        HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, ko, ko, (uint64_t)0, (size_t)c->nReads + 1, rocprim::plus<uint64_t>(), c->stream));
+        if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, ko, ko, (uint64_t)0, (size_t)c->nReads + 1, rocprim::plus<uint64_t>()))) return rc;
     }
-    if ((rc = timer_end(c, c->timers[KASA_STAGE_SORT], a, b))) return rc;
+    if ((rc = stage.end())) return rc;
     return lookup_part<Key>(c);
 }
 
@@ -2171,34 +2253,33 @@ static int lookup_part(kasa_ctx *c)
 {
     const uint64_t nQ = c->nQ;
     int rc;
-    hipEvent_t a, b;
     if ((rc = c->depth.reserve(nQ + 64)) || (rc = c->rep.reserve(nQ * 4 + 64))) return rc;
     const uint32_t nTiles = (uint32_t)((nQ + TILE - 1) / TILE);
     if ((rc = c->tileFirst.reserve((size_t)c->nK * (nTiles + 1) * 4)) || (rc = c->tileNext.reserve((size_t)c->nK * (nTiles + 1) * 4)) ||
         (rc = c->tileBounds.reserve(((size_t)nTiles + 1) * 8)))
         return rc;
 
-    if ((rc = timer_begin(c, c->timers[KASA_STAGE_LOOKUP], &a, &b))) return rc;
+    Span stage(c, c->timers[KASA_STAGE_LOOKUP]); if ((rc = stage.begin())) return rc;
     if (nQ > 0) {
-        hipEvent_t ka, kb;
+        Span kernel(c, c->kernels[KASA_KERNEL_LOOKUP]);
         if (c->lookupMode == 1) {
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_LOOKUP], &ka, &kb))) return rc;
+            if ((rc = kernel.begin())) return rc;
             lookup_kernel<Key><<<nTiles, TILE_THREADS, 0, c->stream>>>(c->keys<Key>(), (uint32_t)nQ, c->ix->kmer.as<Key>(), (uint32_t)c->ix->n,
                 c->ix->table.as<uint32_t>(), c->ix->tb, c->kHigh, c->kLow, c->depth.as<uint8_t>(), c->rep.as<uint32_t>(),
                 c->tileFirst.as<uint32_t>(), nTiles);
         } else {
             tile_bounds_kernel<Key><<<blocks_for(2ull * nTiles, 256), 256, 0, c->stream>>>(c->keys<Key>(), (uint32_t)nQ, c->ix->kmer.as<Key>(),
                 c->ix->table.as<uint32_t>(), c->ix->tb, nTiles, c->tileBounds.as<uint32_t>());
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_LOOKUP], &ka, &kb))) return rc;   // lookup_tile_kernel alone
+            if ((rc = kernel.begin())) return rc;                          // lookup_tile_kernel alone
             lookup_tile_kernel<Key><<<nTiles, TILE_THREADS, 0, c->stream>>>(c->keys<Key>(), (uint32_t)nQ, c->ix->kmer.as<Key>(), (uint32_t)c->ix->n,
                 c->ix->table.as<uint32_t>(), c->ix->tb, c->tileBounds.as<uint32_t>(), c->kHigh, c->kLow, c->depth.as<uint8_t>(),
                 c->rep.as<uint32_t>(), c->tileFirst.as<uint32_t>(), nTiles);
         }
         HIPCHK(hipGetLastError());
-        if ((rc = timer_end(c, c->kernels[KASA_KERNEL_LOOKUP], ka, kb))) return rc;
+        if ((rc = kernel.end())) return rc;
         if ((rc = tile_suffix(c, nTiles))) return rc;
     }
-    if ((rc = timer_end(c, c->timers[KASA_STAGE_LOOKUP], a, b))) return rc;
+    if ((rc = stage.end())) return rc;
     c->state = 3;
     return KASA_OK;
 }
@@ -5840,22 +5921,16 @@ static int slots_from_reads(kasa_ctx *c)
     const uint64_t nQ = c->nQ;
     int rc;
     if ((rc = c->plist.reserve(nQ * 4 + 64)) || (rc = c->slotBuf.reserve(nQ * 4 + 64)) || (rc = c->qReadA.reserve(nQ * 4 + 64))) return rc;
-    hipEvent_t a, b;
-    if ((rc = timer_begin(c, c->timers[KASA_STAGE_REGROUP], &a, &b))) return rc;
+    Span stage(c, c->timers[KASA_STAGE_REGROUP]); if ((rc = stage.begin())) return rc;
     if (nQ) {
         unsigned bits = 1;
         while ((1ull << bits) < (uint64_t)std::max<int64_t>(c->nReads, 1)) ++bits;
         rocprim::counting_iterator<uint32_t> iota(0);
-        size_t tmpBytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmpBytes, c->qRead, c->qReadA.as<uint32_t>(), iota, c->plist.as<uint32_t>(),
-                                         (size_t)nQ, 0u, bits, c->stream));
-        if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-        HIPCHK(rocprim::radix_sort_pairs(c->sortTmp.p, tmpBytes, c->qRead, c->qReadA.as<uint32_t>(), iota, c->plist.as<uint32_t>(),
-                                         (size_t)nQ, 0u, bits, c->stream));
+        if ((rc = dev_sort_pairs(c->sortTmp, c->stream, c->qRead, c->qReadA.as<uint32_t>(), iota, c->plist.as<uint32_t>(), (size_t)nQ, 0u, bits))) return rc;
         invert_kernel<<<blocks_for(nQ, 256), 256, 0, c->stream>>>(c->plist.as<uint32_t>(), (uint32_t)nQ, c->slotBuf.as<uint32_t>());
         HIPCHK(hipGetLastError());
     }
-    if ((rc = timer_end(c, c->timers[KASA_STAGE_REGROUP], a, b))) return rc;
+    if ((rc = stage.end())) return rc;
     c->slotOf = c->slotBuf.as<uint32_t>();
     return KASA_OK;
 }
@@ -5865,7 +5940,7 @@ static int launch_group(kasa_ctx *c, const uint32_t *slotOf, uint32_t nTiles, ui
                         const uint32_t *tileList = nullptr, uint32_t nListed = 0)
 {
     const uint64_t nQ = c->nQ;
-    uint32_t *needCoop = reinterpret_cast<uint32_t *>(cursor + 3);        // (misc word [19]: free during the kernel)
+    uint32_t *needCoop = &c->ctr()->group.needCoop;                       // (the low half of cursor[3])
     const uint32_t grid = tileList ? nListed : nTiles;                    // (a list: only the tiles group2_kernel left over)
 #define KASA_GROUP_ARGS(KEY, META) c->keys<KEY>(), c->depth.as<uint8_t>(), c->rep.as<uint32_t>(), slotOf, (uint32_t)nQ, \
         c->tileNext.as<uint32_t>(), nTiles, c->ix->meta.as<META>(), c->ix->tax.as<uint32_t>(), (uint32_t)c->ix->n, \
@@ -6197,9 +6272,9 @@ static int profile_from_keys(kasa_ctx *c, uint64_t nKeys, bool grouped)
     if (tables) {
         int nCu = 0;
         HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
-        unsigned long long *leftCursor = c->misc.as<unsigned long long>() + 19;
+        unsigned long long *leftCursor = c->ctr()->cursor + CUR_LEFT_OVER;   // (group_stage's flag word: it has read it by now)
         unsigned long long left = 0;
-        HIPCHK(hipMemsetAsync(leftCursor, 0, 8, ps));
+        HIPCHK(hipMemsetAsync(leftCursor, 0, sizeof(*leftCursor), ps));
         for (const auto &L : passes) {
             ProfTablePacked TL;
             if (!prof_table_pack(L, TL) || (grouped && nK > 8)) return fail(KASA_E_LIMIT, "profile tables: a window of more than eight levels");
@@ -6216,8 +6291,7 @@ static int profile_from_keys(kasa_ctx *c, uint64_t nKeys, bool grouped)
                 c->profSorted.as<uint64_t>(), leftCursor);
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipMemcpyAsync(&left, leftCursor, 8, hipMemcpyDeviceToHost, ps));
-        HIPCHK(hipStreamSynchronize(ps));
+        if ((rc = fetch(ps, left, leftCursor))) return rc;
         nSort = std::min<uint64_t>(left, leftCap); sortIn = c->profSorted.as<uint64_t>();
         sortOut = grouped ? c->profSorted2.as<uint64_t>() : c->profKeys.as<uint64_t>();   // (per-read keys: what is left is sorted back into the key buffer)
         if (grouped && left > leftCap) c->profLeftHint = left + left / 4;
@@ -6276,8 +6350,8 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
     }
     if (!c->recOut && (rc = (RW == 8 && c->recCW == 8u) ? reserve_placed(c->rec, nQ * (size_t)32 + 64, c->stream, &c->recPlacement)   // (32-byte slots: partial cells)
                                                           : c->rec.reserve(nQ * (size_t)c->recCW * 4 + 64))) return rc;
-    unsigned long long *cursor = c->misc.as<unsigned long long>() + 16;   // 64-bit cursors: [16] pool, [17] staging, [18] profile keys
-    hipEvent_t a, b;
+    unsigned long long *cursor = c->ctr()->cursor;                        // 64-bit cursors: pool, staging, profile keys, flag word
+    Span stage(c, c->timers[KASA_STAGE_GROUP]);
     if (c->poolCap == 0) c->poolCap = std::max<uint64_t>(1u << 16, nQ);   // (a word per query: a first batch with crowded taxon lists -- 0.75 words per query on the bench data -- need not run group_kernel twice)
     if (c->keyCap == 0) c->keyCap = RW == 8 ? std::max<uint64_t>(1u << 20, nQ / 2 + nQ / 4) : 64;   // (group keys: narrow records only; at least 2^20: the buffer also takes the sorted leftovers of the table pass)
     uint64_t nKeys = 0;
@@ -6285,17 +6359,16 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
         if (c->keyCap >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "the profile of this batch needs %llu keys (limit 2^32); split the batch", (unsigned long long)c->keyCap);
         if ((rc = c->pool.reserve(c->poolCap * 4)) || (rc = c->profKeys.reserve(c->keyCap * 8 + 64))) return rc;
         const unsigned long long one = 1, zero = 0;
-        HIPCHK(hipMemcpyAsync(cursor, &one, 8, hipMemcpyHostToDevice, c->stream)); // offset 0 is never handed out
-        HIPCHK(hipMemcpyAsync(cursor + 2, &zero, 8, hipMemcpyHostToDevice, c->stream));
-        if ((rc = timer_begin(c, c->timers[KASA_STAGE_GROUP], &a, &b))) return rc;
+        HIPCHK(hipMemcpyAsync(cursor + CUR_POOL, &one, sizeof(one), hipMemcpyHostToDevice, c->stream)); // offset 0 is never handed out
+        HIPCHK(hipMemcpyAsync(cursor + CUR_PROF_KEYS, &zero, sizeof(zero), hipMemcpyHostToDevice, c->stream));
+        if ((rc = stage.begin())) return rc;
         const uint32_t cap = (uint32_t)std::min<uint64_t>(c->poolCap, 0xFFFFFFF0ull);
         static const int g2tap = getenv("KASA_G2_TAP") ? atoi(getenv("KASA_G2_TAP")) : 0;   // (timing taps of group2_kernel: 32, 64, 128)
         static const int longSteps = getenv("KASA_LONG_STEPS") ? (atoi(getenv("KASA_LONG_STEPS")) & 127) : 0;   // (experiments: where a lane gives its walk to the wavefront)
         const int cov = (g2tap & (32 | 64 | 128 | 256)) | ((longSteps ? longSteps : (c->groupCoop ? (int)LONG_STEPS_CROWDED : 0)) << 9) | ((coverage && attempt == 0) ? 1 : 0) | ((c->debugFlags & 2048) ? 2 : 0) | ((c->debugFlags & 4096) ? 4 : 0) | ((c->debugFlags & 32768) ? 8 : 0) | ((c->debugFlags & 65536) ? 16 : 0);   // (test taps: no followers; no LDS span for 64-byte records)
         const uint32_t *slotOf = exportSorted ? nullptr : c->slotOf;
-        hipEvent_t ka, kb;
-        if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_GROUP], &ka, &kb))) return rc;
-        HIPCHK(hipMemcpyAsync(cursor + 3, &zero, 8, hipMemcpyHostToDevice, c->stream));   // "a list too long for the lean kernel" | tiles group2_kernel lists << 32
+        Span kernel(c, c->kernels[KASA_KERNEL_GROUP]); if ((rc = kernel.begin())) return rc;
+        HIPCHK(hipMemcpyAsync(cursor + CUR_GROUP_FLAG, &zero, sizeof(zero), hipMemcpyHostToDevice, c->stream));   // "a list too long for the lean kernel" | tiles group2_kernel lists << 32
         if (c->debugFlags & 262144) c->groupCoop = true;                   // (test tap 262144: the cooperative form from the first batch on)
         const bool coop = c->groupCoop && !(c->debugFlags & 131072);       // (test tap 131072: never the cooperative form)
         // narrow records: group2_kernel (leaders dense on the lanes) takes every ordinary tile and LISTS the others -- long taxon
@@ -6305,10 +6378,9 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
         unsigned long long used[4] = {0, 0, 0, 0};
         if (g2) {
             if ((rc = c->tileList.reserve((size_t)nTiles * 8 + 256))) return rc;   // (the first launch's list, then the second chance's)
-            if ((rc = launch_group2(c, slotOf, nTiles, cap, (uint32_t)c->keyCap, cov, cursor, reinterpret_cast<uint32_t *>(cursor + 3) + 1))) return rc;
-            HIPCHK(hipMemcpyAsync(used, cursor, 32, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            const uint32_t nListed = (uint32_t)(used[3] >> 32);
+            if ((rc = launch_group2(c, slotOf, nTiles, cap, (uint32_t)c->keyCap, cov, cursor, &c->ctr()->group.listedTiles))) return rc;
+            if ((rc = fetch(c->stream, used, cursor))) return rc;
+            const uint32_t nListed = (uint32_t)(used[CUR_GROUP_FLAG] >> 32);
             c->lastSlowTiles = nListed; c->lastSlowTiles2 = nListed;
             if (nListed && getenv("KASA_DEBUG_WHY")) {
                 std::vector<uint32_t> h(nListed);
@@ -6325,12 +6397,11 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
             uint32_t nCoop = nListed;
             static const bool g2Always = getenv("KASA_G2_ALWAYS") && atoi(getenv("KASA_G2_ALWAYS")) != 0;   // (experiment: group2_kernel + its second launch whatever the share of listed tiles)
             if (nListed && c->nK == 6 && !c->ix->wide && !(cov & (32 | 64 | 128 | 256)) && ((uint64_t)nListed * 4 <= nTiles || g2Always) && !getenv("KASA_NO_SECOND_CHANCE")) {
-                uint32_t *count2 = c->misc.as<uint32_t>() + 78, *list2 = c->tileList.as<uint32_t>() + nTiles + 16;
-                HIPCHK(hipMemsetAsync(count2, 0, 4, c->stream));
+                uint32_t *count2 = &c->ctr()->group2Second, *list2 = c->tileList.as<uint32_t>() + nTiles + 16;
+                HIPCHK(hipMemsetAsync(count2, 0, sizeof(*count2), c->stream));
                 if ((rc = launch_group2(c, slotOf, nTiles, cap, (uint32_t)c->keyCap, cov, cursor, count2, c->tileList.as<uint32_t>(), nListed, list2))) return rc;
                 uint32_t n2 = 0;
-                HIPCHK(hipMemcpyAsync(&n2, count2, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
+                if ((rc = fetch(c->stream, n2, count2))) return rc;
                 coopList = list2; nCoop = n2;
                 c->lastSlowTiles2 = n2;
                 if (getenv("KASA_DEBUG_WHY")) fprintf(stderr, "[kasa] group2's second launch left %u of %u listed tiles to the cooperative kernel\n", n2, nListed);
@@ -6341,32 +6412,28 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
             c->lastSlowTiles = 0; c->lastSlowTiles2 = 0;
             if ((rc = (RW == 8 ? launch_group<8>(c, slotOf, nTiles, cap, (uint32_t)c->keyCap, cov, cursor, coop) : launch_group<16>(c, slotOf, nTiles, cap, (uint32_t)c->keyCap, cov, cursor, false)))) return rc;
         }
-        if ((rc = timer_end(c, c->kernels[KASA_KERNEL_GROUP], ka, kb))) return rc;
-        if ((rc = timer_end(c, c->timers[KASA_STAGE_GROUP], a, b))) return rc;
-        HIPCHK(hipMemcpyAsync(used, cursor, 32, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (g2 && (used[3] & 1ull)) return fail(KASA_E_LIMIT, "a query meets 255 or more taxa of a 128-bit index through narrow records; use the index's own k range");
-        if (RW == 8 && !g2 && !coop && !(c->debugFlags & 131072) && ((used[3] & 1ull) || used[0] > 6ull * nQ)) {
+        if ((rc = kernel.end()) || (rc = stage.end())) return rc;
+        if ((rc = fetch(c->stream, used, cursor))) return rc;
+        const unsigned long long poolUsed = used[CUR_POOL], keysUsed = used[CUR_PROF_KEYS];
+        const bool tooLong = (used[CUR_GROUP_FLAG] & 1ull) != 0;
+        if (g2 && tooLong) return fail(KASA_E_LIMIT, "a query meets 255 or more taxa of a 128-bit index through narrow records; use the index's own k range");
+        if (RW == 8 && !g2 && !coop && !(c->debugFlags & 131072) && (tooLong || poolUsed > 6ull * nQ)) {
             // a list of 255 or more segments (the lean kernel cannot count it), or long lists on average: whole wavefronts
             // take the long lists from here on -- this batch again if it must be, the context's further batches anyway
             c->groupCoop = true;
-            if (used[3] & 1ull) { if (used[0] > c->poolCap) c->poolCap = used[0] + used[0] / 8 + 1024; continue; }
+            if (tooLong) { if (poolUsed > c->poolCap) c->poolCap = poolUsed + poolUsed / 8 + 1024; continue; }
         }
-        if (used[0] <= c->poolCap && used[2] <= c->keyCap) { c->poolUsed = (uint32_t)used[0]; nKeys = used[2]; break; }
-        if (used[0] >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "the taxon lists of this batch need %llu pool entries (limit 2^32); split the batch", used[0]);
-        if (used[0] > c->poolCap) c->poolCap = used[0] + used[0] / 8 + 1024;
-        if (used[2] > c->keyCap) c->keyCap = used[2] + used[2] / 8 + 1024;
+        if (poolUsed <= c->poolCap && keysUsed <= c->keyCap) { c->poolUsed = (uint32_t)poolUsed; nKeys = keysUsed; break; }
+        if (poolUsed >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "the taxon lists of this batch need %llu pool entries (limit 2^32); split the batch", poolUsed);
+        if (poolUsed > c->poolCap) c->poolCap = poolUsed + poolUsed / 8 + 1024;
+        if (keysUsed > c->keyCap) c->keyCap = keysUsed + keysUsed / 8 + 1024;
         if (attempt > 3) return fail(KASA_E_LIMIT, "taxon-list pool did not converge");
     }
     // the profile of the batch: the leaders' keys into the tables (the per-read score stage adds nothing to them)
-    if ((rc = timer_begin(c, c->timers[KASA_STAGE_GROUP], &a, &b))) return rc;
-    {
-        hipEvent_t ka, kb;
-        if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_PROFILE_TABLES], &ka, &kb))) return rc;
-        if (RW == 8 && (rc = profile_from_keys(c, nKeys, true))) return rc;
-        if ((rc = timer_end(c, c->kernels[KASA_KERNEL_PROFILE_TABLES], ka, kb))) return rc;
-    }
-    if ((rc = timer_end(c, c->timers[KASA_STAGE_GROUP], a, b))) return rc;
+    Span tables(c, c->kernels[KASA_KERNEL_PROFILE_TABLES]);
+    if ((rc = stage.begin()) || (rc = tables.begin())) return rc;
+    if (RW == 8 && (rc = profile_from_keys(c, nKeys, true))) return rc;
+    if ((rc = tables.end()) || (rc = stage.end())) return rc;
     c->lastKeys = nKeys;
     c->grouped = true;
     return KASA_OK;
@@ -6400,7 +6467,337 @@ __global__ void list_counts_kernel(const uint32_t *__restrict__ list, uint32_t n
     if (i == nList) cnt[i] = 0;
 }
 
+// ---- the score stage: what its steps share, the kernels they choose, the steps ------------------------------------------------
+struct ScoreRun {
+    ScoreArgs A;                                 // A.list / A.nList: the reads still to be scored by a slower kernel
+    uint32_t nSlow = 0;                          // ... their number (all reads where no fast kernel ran)
+    uint32_t nCls[3] = {0, 0, 0}, nHanded = 0;   // rows score_main_kernel listed per upper row-merge class; reads the fast pair handed on
+    uint64_t staged = 0, nKeys = 0;              // staging records, profile keys (wide records) of the batch
+    bool slowProfileDone = false, replayAddedProfile = false;   // score_kernel (the replay) adds to the profile tables itself: only once, whatever is rerun
+    bool wantPerRead, gp, fast, bitmapMerge;     // of the batch.  gp, narrow records: the profile is group_stage's, the kernels here leave no keys (they still add their zero)
+    uint32_t clsLo[3];
+    Span stage;                                  // KASA_STAGE_SCORE: closed around every wait of the host for a capacity
+    ScoreRun(kasa_ctx *c, bool wantPerRead) : wantPerRead(wantPerRead), stage(c, c->timers[KASA_STAGE_SCORE]) {}
+};
+
 #include "kasa_replay.h"
+
+typedef void (*ScoreKernel)(ScoreArgs);
+
+// score_main_kernel<RW, PER, FB, NLV, ...>: 8-bit counter fields (FB, twice the wavefronts per CU) where no read has more than
+// 255 k-mers; the level counts of the defaults (-k 12 7: six, smaller LDS tables, one more wavefront per SIMD; -k 25 7: 19)
+static ScoreKernel score_main_choice(const kasa_ctx *c, bool per)
+{
+    const int RW = c->recWords(), nK = c->nK;
+    const bool fb8 = c->maxCnt <= 255u, lv6 = RW == 8 && nK <= 6, lv19 = RW == 16 && nK <= 19;
+    return (RW == 8 && fb8 && per && (c->debugFlags & 1024)) ? score_main_kernel<8, true, 8, 8, true> :
+           (lv6 && fb8) ? (per ? score_main_kernel<8, true, 8, 6> : score_main_kernel<8, false, 8, 6>) :
+           RW == 8 ? (fb8 ? (per ? score_main_kernel<8, true, 8> : score_main_kernel<8, false, 8>)
+                          : (per ? score_main_kernel<8, true> : score_main_kernel<8, false>))
+         : lv19 ? (fb8 ? (per ? score_main_kernel<16, true, 8, 19> : score_main_kernel<16, false, 8, 19>)
+                       : (per ? score_main_kernel<16, true, 16, 19> : score_main_kernel<16, false, 16, 19>))
+                : (fb8 ? (per ? score_main_kernel<16, true, 8> : score_main_kernel<16, false, 8>)
+                       : (per ? score_main_kernel<16, true> : score_main_kernel<16, false>));
+}
+
+// the score_other* family.  Wide records: score_other_flat16_kernel, workgroups of 128 (else of 256); narrow ones:
+// score_other_flat_kernel; debug flag 32: the per-lane kernels for both
+static ScoreKernel score_other_choice(const kasa_ctx *c, bool per, unsigned *threads, unsigned *maxBlocks)
+{
+    const int RW = c->recWords();
+    const bool perLane = (c->debugFlags & 32) != 0, flat = RW == 8 && !perLane;
+    *threads = (RW == 16 && !perLane) ? 128u : 256u;
+    *maxBlocks = (RW == 16 && !perLane) ? 256u * 128u : 256u * 64u;
+    if (RW == 16 && !perLane)
+        return c->nK <= 19 ? (per ? score_other_flat16_kernel<true, 19> : score_other_flat16_kernel<false, 19>)
+                           : (per ? score_other_flat16_kernel<true> : score_other_flat16_kernel<false>);
+    return per ? (RW == 8 ? (flat ? score_other_flat_kernel<true> : score_other_kernel<8, true>) : score_other_kernel<16, true>)
+               : (RW == 8 ? (flat ? score_other_flat_kernel<false> : score_other_kernel<8, false>) : score_other_kernel<16, false>);
+}
+
+// A fresh attempt: the counters the kernels add to are cleared, A names the batch's buffers at their present sizes.
+static int score_begin_attempt(kasa_ctx *c, ScoreRun &R)
+{
+    CtxCounters *ctr = c->ctr(); ScoreArgs &A = R.A;
+    const uint32_t nReads = (uint32_t)c->nReads, nTaxa = c->ix->nTaxa;
+    unsigned long long *stCursor = ctr->cursor + CUR_STAGING, *keyCursor = R.gp ? &ctr->scoreKeyCursor : ctr->cursor + CUR_PROF_KEYS;
+    HIPCHK(hipMemsetAsync(&ctr->score, 0, sizeof(ScoreFlags), c->stream));
+    HIPCHK(hipMemsetAsync(ctr->why, 0, sizeof(CtxCounters::why), c->stream));
+    HIPCHK(hipMemsetAsync(stCursor, 0, sizeof(*stCursor), c->stream));
+    HIPCHK(hipMemsetAsync(keyCursor, 0, sizeof(*keyCursor), c->stream));
+    HIPCHK(hipMemsetAsync(ctr->rowClass, 0, sizeof(CtxCounters::rowClass), c->stream));   // a rerun lists the rows anew
+    R.nCls[0] = R.nCls[1] = R.nCls[2] = 0; R.nHanded = 0;
+    HIPCHK(hipMemsetAsync(c->rowLen.p, 0, (size_t)nReads * 4, c->stream));
+    A.rec = c->rec.as<uint32_t>(); A.recCW = c->recCW; A.recQS = c->recCW == 8u ? 1u : 2u; A.kmerOff = c->kmerOff.as<uint64_t>();
+    // long rows for long reads: the streaming row merge keeps a slot per taxon in LDS (up to 4096 taxa), the bitmap merge must be the one in use (test tap 4: the sorting merge)
+    A.rowPerQuery = (nTaxa <= 4096u && !(c->debugFlags & 4) && !(getenv("KASA_NO_LONG_ROWS") && atoi(getenv("KASA_NO_LONG_ROWS")))) ? 8u : 0u;   // (KASA_NO_LONG_ROWS=1: round 5's limit, tests)
+    A.pool = c->pool.as<uint32_t>(); A.nReads = nReads; A.kHigh = c->kHigh; A.kLow = c->kLow; A.nTaxa = nTaxa;
+    A.scratch = nullptr; A.mainOut = nullptr; A.otherOff64 = nullptr; A.nQ = (uint32_t)c->nQ;
+    A.cntUnique = c->cntUnique.as<uint64_t>(); A.cntAllHi = c->cntAllHi.as<uint64_t>(); A.cntAllMid = c->cntAllMid.as<uint64_t>(); A.cntAllLo = c->cntAllLo.as<uint64_t>();
+    A.rowPos = c->rowPos.as<uint32_t>(); A.rowLen = c->rowLen.as<uint32_t>(); A.st = c->st.as<uint2>();
+    A.stCap = (uint32_t)c->stCap; A.stCursor = stCursor; A.errFlag = &ctr->score.err;
+    A.rowKey = c->rowKey.as<uint32_t>(); A.keyCap = R.gp ? 0xFFFFFFFFu : (uint32_t)c->keyCapScore; A.keyCursor = keyCursor;
+    A.wantPerRead = R.wantPerRead ? 1 : 0; A.addProfile = R.gp ? 0 : (R.slowProfileDone ? 0 : 1);
+    A.list = nullptr; A.nList = 0; A.flushPos = nullptr; A.flushOff = nullptr;
+    A.fbList = c->fbList.as<uint32_t>(); A.fbCount = &ctr->score.fallbacks; A.why = ctr->why;
+    for (int k = 0; k < 3; ++k) { A.clsLo[k] = R.clsLo[k]; A.clsList[k] = c->clsList.as<uint32_t>() + (size_t)k * nReads; }
+    A.clsCount = R.bitmapMerge ? ctr->rowClass : nullptr;              // (the sorting merge takes every row in one launch)
+    A.ovList = nullptr; A.ovCount = nullptr; A.workCursor = nullptr; A.forceHandOn = (c->debugFlags & 16384) ? 1 : 0;
+    R.nSlow = nReads;
+    return KASA_OK;
+}
+
+// score_main_kernel + score_other*: persistent wavefronts, as many as are resident at once, each takes 64 reads at a time from a
+// work counter.  They have no side effects: *rerun when the staging records or (wide records) the keys need more room.
+static int score_fast_pair(kasa_ctx *c, ScoreRun &R, bool *rerun)
+{
+    CtxCounters *ctr = c->ctr(); ScoreArgs &A = R.A;
+    const uint32_t nReads = (uint32_t)c->nReads;
+    int rc, perCu = 0, nCu = 0; unsigned othreads = 0, omax = 0;
+    const ScoreKernel kern = score_main_choice(c, R.wantPerRead), other = score_other_choice(c, R.wantPerRead, &othreads, &omax);
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *)kern, 64, 0));
+    HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
+    const uint32_t fblocks = std::min<uint32_t>((nReads + 63) / 64, (uint32_t)std::max(1, perCu) * (uint32_t)std::max(1, nCu));
+    if ((rc = c->fastScratch.reserve((size_t)nReads * 16 + 64)) || (rc = c->plist.reserve((c->nQ / 64 + 2) * 4 + 64))) return rc;   // (plist: free once the slots are known)
+    A.mainOut = c->fastScratch.as<uint32_t>(); A.otherOff64 = c->plist.as<uint32_t>(); A.workCursor = &ctr->workCursor;
+    HIPCHK(hipMemsetAsync(A.workCursor, 0, sizeof(ctr->workCursor), c->stream));
+    Span mainSpan(c, c->kernels[KASA_KERNEL_SCORE_MAIN]), otherSpan(c, c->kernels[KASA_KERNEL_SCORE_OTHER]);
+    if ((rc = mainSpan.begin())) return rc;
+    kern<<<fblocks, 64, 0, c->stream>>>(A);
+    HIPCHK(hipGetLastError());
+    if ((rc = mainSpan.end()) || (rc = otherSpan.begin())) return rc;
+    other<<<std::min<unsigned>(blocks_for(c->nQ, othreads), omax), othreads, 0, c->stream>>>(A);
+    HIPCHK(hipGetLastError());
+    if ((rc = otherSpan.end())) return rc;
+    uint32_t h3 = 0; unsigned long long want[2] = {0, 0};                   // staging records, keys (wide records): the true demand
+    if ((rc = fetch_async(c->stream, h3, &ctr->score.fallbacks)) || (rc = R.gp ? fetch_async(c->stream, want[0], A.stCursor) : fetch_async(c->stream, want, A.stCursor)) ||
+        (rc = fetch(c->stream, R.nCls, ctr->rowClass))) return rc;
+    R.nSlow = h3; R.nHanded = h3;
+    *rerun = want[0] > c->stCap || (!R.gp && want[1] > c->keyCapScore);
+    if (*rerun) {
+        if ((rc = R.stage.end())) return rc;
+        if (want[0] > c->stCap) c->stCap = want[0] + want[0] / 8 + (uint64_t)R.nSlow * 64 + 1024;
+        if (!R.gp && want[1] > c->keyCapScore) c->keyCapScore = want[1] + want[1] / 8 + 1024;
+        return KASA_OK;
+    }
+    R.nKeys = R.gp ? 0 : want[1];
+    A.list = c->fbList.as<uint32_t>(); A.nList = R.nSlow;
+    return KASA_OK;
+}
+
+// score_dense_kernel: the reads the fast kernels handed over (long rows, as a rule) that keep the order rule need no pending window
+static int score_dense_pass(kasa_ctx *c, ScoreRun &R)
+{
+    ScoreArgs &A = R.A;
+    int rc;
+    if ((rc = c->fbList2.reserve((size_t)R.nSlow * 4 + 64))) return rc;
+    uint32_t *handCount = &c->ctr()->denseHanded;
+    HIPCHK(hipMemsetAsync(handCount, 0, sizeof(*handCount), c->stream));
+    Span span(c, c->kernels[KASA_KERNEL_SCORE_DENSE]); if ((rc = span.begin())) return rc;
+    static const int denseTap = getenv("KASA_DENSE_TAP") ? atoi(getenv("KASA_DENSE_TAP")) : 0;
+    const int keepHandOn = A.forceHandOn;
+    A.forceHandOn = denseTap;
+    const size_t rowLds = ((size_t)A.nTaxa * 4 + (((size_t)A.nTaxa + 3) / 4) * 4) * SD_WAVES;
+    const uint32_t dblocks = std::min<uint32_t>((R.nSlow + SD_WAVES - 1) / SD_WAVES, 256u * 8u);
+    void (*const kern)(ScoreArgs, uint32_t *, uint32_t *) = c->nK <= 6 ? score_dense_kernel<6> : score_dense_kernel<8>;
+    HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
+    kern<<<dblocks, 64 * SD_WAVES, rowLds, c->stream>>>(A, c->fbList2.as<uint32_t>(), handCount);
+    HIPCHK(hipGetLastError());
+    A.forceHandOn = keepHandOn;
+    if ((rc = span.end())) return rc;
+    uint32_t handed = 0;
+    if ((rc = fetch(c->stream, handed, handCount))) return rc;
+    c->lastDenseReads = R.nSlow - handed;
+    R.nSlow = handed;
+    A.list = c->fbList2.as<uint32_t>(); A.nList = R.nSlow;
+    return KASA_OK;
+}
+
+// very long reads: events sorted by (read, taxon, flush position, level), one float chain per (read, taxon) (kasa_replay.h)
+static int score_replay_handover(kasa_ctx *c, ScoreRun &R)
+{
+    int rc;
+    const uint32_t minEnv = getenv("KASA_ESR_MIN_KMERS") ? (uint32_t)strtoul(getenv("KASA_ESR_MIN_KMERS"), nullptr, 10) : 0u;   // (tests: short reads through it)
+    const uint32_t minK = (c->debugFlags & 1073741824) ? 1u : (minEnv ? minEnv : ESR_MIN_KMERS);   // (test tap 1073741824: every read of the general kernel's list)
+    Span span(c, c->kernels[KASA_KERNEL_SCORE_REPLAY]); if ((rc = span.begin())) return rc;
+    const uint32_t *rest = nullptr; uint32_t nRest = 0;
+    if ((rc = esr_stage(c, R.A, R.nSlow, minK, &rest, &nRest)) || (rc = span.end())) return rc;
+    if (c->lastReplayReads) { R.A.list = rest; R.A.nList = nRest; R.nSlow = nRest; if (!R.gp) R.replayAddedProfile = true; }
+    return KASA_OK;
+}
+
+// A pass of the general kernel over a list of reads (NULL: all): their queries' flush positions -- the records hold only the
+// order inside a query -- are addressed through the list, so its offsets are made anew for every pass.  *longest: the most
+// queries of a listed read, where asked for.
+static int score_flush_positions(kasa_ctx *c, ScoreRun &R, const uint32_t *list, uint32_t n, DevBuf &off, DevBuf &pos, uint32_t *longest)
+{
+    int rc;
+    const uint64_t *flushOff = c->kmerOff.as<uint64_t>();
+    uint64_t nFq = c->nQ;
+    if (list) {
+        if ((rc = off.reserve(((size_t)n + 1) * 8 + 64))) return rc;
+        uint32_t *longestDev = longest ? &c->ctr()->longestListed : nullptr;
+        if (longestDev) HIPCHK(hipMemsetAsync(longestDev, 0, sizeof(*longestDev), c->stream));
+        list_counts_kernel<<<blocks_for((uint64_t)n + 1, 256), 256, 0, c->stream>>>(list, n, c->kmerOff.as<uint64_t>(), off.as<uint64_t>(), longestDev);
+        if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, off.as<uint64_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>()))) return rc;
+        if ((rc = fetch_async(c->stream, nFq, off.as<uint64_t>() + n)) || (longestDev && (rc = fetch_async(c->stream, *longest, longestDev)))) return rc;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        flushOff = off.as<uint64_t>();
+    }
+    if ((rc = pos.reserve(nFq * (size_t)c->nK * 4 + 64))) return rc;
+    R.A.flushPos = pos.as<uint32_t>(); R.A.flushOff = flushOff;
+    return c->recWords() == 8 ? launch_flush<8>(c, list, n, flushOff, pos.as<uint32_t>()) : launch_flush<16>(c, list, n, flushOff, pos.as<uint32_t>());
+}
+
+// score_kernel<PCAP..., RW, dense, gwin>, the general kernel.  pass 1: the small pending window (leaves every score row zeroed
+// again); 2: PCAP groups in LDS; 3 (narrow records): the window in device memory.  dense: the score row in LDS (else, test
+// tap 8192: the lane-owns-its-cells form)
+static int launch_score_kernel(kasa_ctx *c, const ScoreArgs &A, int pass, uint32_t blocks, bool dense)
+{
+    const bool narrow = c->recWords() == 8;
+    const size_t rowLds = dense ? (size_t)A.nTaxa * 4 : 0;
+    const ScoreKernel kern = (dense && pass == 1) ? (narrow ? score_kernel<PCAP_SMALL, 8, true> : score_kernel<PCAP_SMALL, 16, true>) :
+                             (dense && pass == 2) ? (narrow ? score_kernel<PCAP, 8, true> : score_kernel<PCAP, 16, true>) :
+                             pass == 1 ? (narrow ? score_kernel<PCAP_SMALL, 8> : score_kernel<PCAP_SMALL, 16>) :
+                             pass == 3 ? (dense ? score_kernel<1, 8, true, true> : score_kernel<1, 8, false, true>)
+                                       : (narrow ? score_kernel<PCAP, 8> : score_kernel<PCAP, 16>);
+    if (dense) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
+    kern<<<blocks, 64, rowLds, c->stream>>>(A);
+    HIPCHK(hipGetLastError());
+    return KASA_OK;
+}
+
+// Later passes over the reads a pass handed on.  pass 2: the window of PCAP groups in LDS; narrow records hand a read whose window
+// overflows even that to pass 3: the window in device memory (GWIN), as long as the longest read has queries times levels.
+static int score_later_pass(kasa_ctx *c, ScoreRun &R, const uint32_t *list, uint32_t n, int pass, uint32_t *ovOut, uint32_t *ovCnt, uint32_t blocks, bool dense)
+{
+    ScoreArgs &A = R.A;
+    int rc; uint32_t hLongest = 0;
+    if ((rc = score_flush_positions(c, R, list, n, c->flushOff2, c->flushPos2, &hLongest))) return rc;
+    A.list = list; A.nList = n; A.ovList = ovOut; A.ovCount = ovCnt;
+    A.forceHandOn = (ovOut && (c->debugFlags & 8388608)) ? 1 : 0;   // (test tap 8388608: the second pass hands every read to the third)
+    if (pass == 2) return launch_score_kernel(c, A, 2, std::min<uint32_t>(n, std::min<uint32_t>(blocks, 256u * 16u)), dense);
+    // (per block four arrays as long as the batch's longest read has queries times levels: no read can overflow them)
+    const uint64_t cap = std::max<uint64_t>(64, (uint64_t)hLongest * (uint64_t)c->nK + 64);
+    const uint32_t b3 = std::min<uint32_t>(n, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(256, (2ull << 30) / (cap * 16))));
+    if (cap > 0xFFFFFFFFull) return fail(KASA_E_LIMIT, "a read of %llu k-mers keeps more groups pending than this build can hold", (unsigned long long)hLongest);
+    if ((rc = c->gwin.reserve((size_t)b3 * cap * 16 + 64))) return rc;
+    A.gwin = c->gwin.as<uint32_t>(); A.gwinCap = (uint32_t)cap;
+    return launch_score_kernel(c, A, 3, b3, dense);
+}
+
+// score_kernel over what is left, then its later passes over the reads whose pending window overflowed
+static int score_general(kasa_ctx *c, ScoreRun &R)
+{
+    CtxCounters *ctr = c->ctr(); ScoreArgs &A = R.A;
+    const uint32_t nSlow = R.nSlow, nTaxa = c->ix->nTaxa;
+    int rc;
+    Span span(c, c->kernels[KASA_KERNEL_SCORE_GENERAL]); if ((rc = span.begin())) return rc;
+    if ((rc = score_flush_positions(c, R, A.list, nSlow, c->flushOff, c->flushPos, nullptr))) return rc;
+    const uint64_t rowBytes = (uint64_t)nTaxa * 4;
+    const uint32_t maxBlocks = (uint32_t)std::max<uint64_t>(1024, std::min<uint64_t>(256u * 32u, (8ull << 30) / rowBytes));
+    const uint32_t blocks = std::min<uint32_t>(nSlow, maxBlocks);
+    if ((rc = c->scratch.reserve((size_t)blocks * rowBytes)) || (rc = c->ovList.reserve((size_t)nSlow * 4 + 64))) return rc;
+    HIPCHK(hipMemsetAsync(c->scratch.p, 0, (size_t)blocks * rowBytes, c->stream));
+    HIPCHK(hipMemsetAsync(&ctr->secondPass, 0, sizeof(ctr->secondPass), c->stream));
+    A.scratch = c->scratch.as<float>(); A.ovList = c->ovList.as<uint32_t>(); A.ovCount = &ctr->secondPass;
+    const bool dense = nTaxa <= (uint32_t)DENSE_TAXA && !(c->debugFlags & 8192);   // (test tap 8192: the lane-owns-its-cells form)
+    if ((rc = launch_score_kernel(c, A, 1, blocks, dense))) return rc;
+    uint32_t nOver = 0;
+    if ((rc = fetch(c->stream, nOver, &ctr->secondPass))) return rc;
+    if (nOver > 0) {
+        // second pass.  64-byte records add to the profile as they go (nothing to take back): their window must hold --
+        // KASA_E_LIMIT otherwise.  Narrow records leave no trace of a read they hand on (the profile is group_stage's).
+        uint32_t *ov2 = nullptr, *ov2Cnt = nullptr;
+        if (R.gp) {
+            if ((rc = c->ovList2.reserve((size_t)nOver * 4 + 64))) return rc;
+            ov2 = c->ovList2.as<uint32_t>(); ov2Cnt = &ctr->thirdPass;
+            HIPCHK(hipMemsetAsync(ov2Cnt, 0, sizeof(*ov2Cnt), c->stream));
+        }
+        if ((rc = score_later_pass(c, R, c->ovList.as<uint32_t>(), nOver, 2, ov2, ov2Cnt, blocks, dense))) return rc;
+        if (ov2) {
+            uint32_t nOver2 = 0;
+            if ((rc = fetch(c->stream, nOver2, ov2Cnt))) return rc;
+            if (nOver2 > 0 && (rc = score_later_pass(c, R, ov2, nOver2, 3, nullptr, nullptr, blocks, dense))) return rc;
+            c->lastThirdPassReads = std::max(c->lastThirdPassReads, nOver2);
+        }
+    }
+    c->lastOverflowReads = std::max(c->lastOverflowReads, nOver);   // over the staging retries of this batch
+    R.slowProfileDone = true;
+    return span.end();
+}
+
+// The fast kernels' records resolved: the per-read merge of every staging row, then (wide records) the rows' keys into the tables.
+// Row-merge classes by row length (the LDS a row needs is what limits the resident wavefronts of that latency-bound kernel):
+// up to 2048 taxa 256 / 512 / RMAX, up to BM_WORDS * 32 taxa 256 / RMAX over the wide bitmap (no second class), LONG beyond RMAX
+static int score_row_merge(kasa_ctx *c, ScoreRun &R)
+{
+    const uint32_t nReads = (uint32_t)c->nReads, nTaxa = c->ix->nTaxa;
+    const ProfLayout PL = prof_layout(nTaxa, c->nK);
+    int rc;
+    if ((rc = R.stage.begin())) return rc;
+    Span span(c, c->kernels[KASA_KERNEL_ROW_MERGE]); if ((rc = span.begin())) return rc;
+    uint64_t *noKeys = R.gp ? nullptr : c->profKeys.as<uint64_t>();   // (narrow records: the rows' events leave no profile keys -- group_stage)
+    if (R.bitmapMerge) {
+        // The first class sweeps all reads (nearly every row is its own); the upper classes and LONG walk the rows
+        // score_main_kernel listed for them and are not launched when there are none.  As many workgroups as are resident.
+        typedef void (*MergeKernel)(const uint32_t *, uint32_t *, const uint32_t *, const uint32_t *, uint32_t, uint2 *, uint64_t *, int, uint32_t, uint32_t, ProfLayout);
+        int nCu = 0;
+        HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
+        auto merge = [&](MergeKernel kern, const uint32_t *list, uint32_t rows, uint32_t mLo) -> int {
+            if (rows == 0) return KASA_OK;
+            int perCu = 0;
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *)kern, 64, 0));
+            uint32_t grid = (uint32_t)std::max(1, perCu) * (uint32_t)std::max(1, nCu);
+            if (c->rowMergeBlocks) grid = std::min(grid, c->rowMergeBlocks);
+            kern<<<std::min(rows, grid), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), list, rows,
+                                                           c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, mLo, PL);
+            HIPCHK(hipGetLastError());
+            return KASA_OK;
+        };
+        const bool narrow = nTaxa <= 2048u;                      // (the wide bitmap beyond: the same sizes, no second class)
+        if ((rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<256, 64> : (MergeKernel)row_merge_bitmap_kernel<256, BM_WORDS>, nullptr, nReads, 0u)) ||
+            (rc = merge(row_merge_bitmap_kernel<512, 64>, R.A.clsList[0], narrow ? R.nCls[0] : 0u, R.clsLo[0])) ||
+            (rc = merge(row_merge_bitmap_kernel<RMAX, BM_WORDS>, R.A.clsList[1], R.nCls[1], R.clsLo[1])) ||
+            // long reads' rows (beyond RMAX records): streamed, slots in LDS
+            (rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<2048, 64, true> : (MergeKernel)row_merge_bitmap_kernel<4096, 128, true>, R.A.clsList[2], R.nCls[2], R.clsLo[2])))
+            return rc;
+    } else
+        row_merge_kernel<<<std::min<uint32_t>(nReads, c->rowMergeBlocks ? c->rowMergeBlocks : 256u * 24u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(),
+            c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, PL);
+    HIPCHK(hipGetLastError());
+    if ((rc = span.end())) return rc;
+    c->lastStaged = R.staged;
+    if (!R.gp) {
+        c->lastKeys = R.nKeys;
+        Span tables(c, c->kernels[KASA_KERNEL_PROFILE_TABLES]);
+        if ((rc = tables.begin()) || (rc = profile_from_keys(c, R.nKeys, false)) || (rc = tables.end())) return rc;
+    }
+    return KASA_OK;
+}
+
+// CSR offsets = exclusive scan of the row lengths.  The rows stay where the score kernels left them ({taxon, score} pairs in the
+// staging buffer, row r at rowPos[r], rowOff = the running sum of their lengths): kasa_batch_rank reads them there.  Only a host
+// that asks for the whole CSR (kasa_batch_scores_fetch) has them packed into two arrays first (csr_pack: the copy every batch
+// paid until round 4).
+static int score_csr_offsets(kasa_ctx *c, ScoreRun &R)
+{
+    const uint32_t nReads = (uint32_t)c->nReads;
+    int rc;
+    if (!R.stage.open() && (rc = R.stage.begin())) return rc;
+    DevBuf &len64 = c->qReadA; // reuse
+    if ((rc = len64.reserve(((size_t)nReads + 1) * 8 + 64))) return rc;
+    Span span(c, c->kernels[KASA_KERNEL_ROW_COPY]); if ((rc = span.begin())) return rc;
+    HIPCHK(hipMemsetAsync(len64.p, 0, ((size_t)nReads + 1) * 8, c->stream));
+    widen_kernel<<<blocks_for(nReads, 256), 256, 0, c->stream>>>(c->rowLen.as<uint32_t>(), len64.as<uint64_t>(), nReads);
+    // (scanTmp, not sortTmp: the profile's leftover sort is queued with that)
+    if ((rc = dev_exclusive_scan(c->scanTmp, c->stream, len64.as<uint64_t>(), c->rowOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>()))) return rc;
+    uint64_t nnz = 0;
+    if ((rc = fetch(c->stream, nnz, c->rowOff.as<uint64_t>() + nReads))) return rc;
+    c->nnz = nnz;
+    c->csrPacked = false;
+    return span.end();
+}
 
 static int score_stage(kasa_ctx *c, int wantPerRead)
 {
@@ -6410,8 +6807,6 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
     const uint64_t nQ = c->nQ;
     const uint32_t nReads = (uint32_t)c->nReads;
     const uint32_t nTaxa = c->ix->nTaxa;
-    const int nK = c->nK;
-    const int RW = c->recWords();
     int rc;
     c->haveScores = false; c->nnz = 0;
     for (int k = 0; k < 4; ++k) c->rowClasses[k] = 0;
@@ -6426,282 +6821,42 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         c->state = 4;
         return KASA_OK;
     }
-    uint32_t *counters = c->misc.as<uint32_t>(); // [2] error flags, [3] fallback count, [5] second-pass count, [8..15] reasons, [84..86] rows per upper row-merge class; u64 [16] pool cursor, [17] staging cursor
-    const bool gp = RW == 8;                     // narrow records: the profile is group_stage's, the kernels here leave no keys (they still add their zero)
-    unsigned long long *stCursor = c->misc.as<unsigned long long>() + 17, *keyCursor = c->misc.as<unsigned long long>() + (gp ? 30 : 18);
-    hipEvent_t a, b;
-
     if ((rc = c->rowPos.reserve((size_t)nReads * 4 + 64)) || (rc = c->rowLen.reserve((size_t)nReads * 4 + 64)) || (rc = c->rowKey.reserve((size_t)nReads * 4 + 64)) ||
         (rc = c->rowOff.reserve(((size_t)nReads + 1) * 8 + 64)) || (rc = c->fbList.reserve((size_t)nReads * 4 + 64)) ||
         (rc = c->clsList.reserve((size_t)nReads * 12 + 64)))
         return rc;
-    // row-merge classes by row length (the LDS a row needs is what limits the resident wavefronts of that latency-bound kernel):
-    // up to 2048 taxa 256 / 512 / RMAX, up to BM_WORDS * 32 taxa 256 / RMAX over the wide bitmap (no second class), LONG beyond RMAX
-    const bool bitmapMerge = nTaxa <= (uint32_t)BM_WORDS * 32u && !(c->debugFlags & 4);
-    const uint32_t clsLo[3] = {256u, nTaxa <= 2048u ? 512u : 256u, (uint32_t)RMAX};
-    uint32_t *clsCount = counters + 84;          // [84..86] rows listed for the second, third and long class
-    uint32_t nCls[3] = {0, 0, 0}, nHanded = 0;
+    ScoreRun R(c, wantPerRead != 0);
+    const bool gp = R.gp = c->recWords() == 8;
+    R.bitmapMerge = nTaxa <= (uint32_t)BM_WORDS * 32u && !(c->debugFlags & 4);
+    R.clsLo[0] = 256u; R.clsLo[1] = nTaxa <= 2048u ? 512u : 256u; R.clsLo[2] = (uint32_t)RMAX;
+    R.fast = c->nK <= 25 && nTaxa <= (1u << 20) && !c->forceSlowScore;   // staging records keep the taxon in 20 bits
     if (c->stCap == 0) c->stCap = std::max<uint64_t>(1u << 16, (uint64_t)nReads * 8);
-    const bool fast = nK <= 25 && nTaxa <= (1u << 20) && !c->forceSlowScore;   // staging records keep the taxon in 20 bits
-    bool slowProfileDone = false;   // score_kernel adds to the profile tables itself: only once, whatever is rerun
-    bool replayAddedProfile = false;
     c->lastOverflowReads = 0; c->lastThirdPassReads = 0;
-    uint64_t staged = 0, nKeys = 0;
     if (!gp && c->keyCapScore == 0) c->keyCapScore = c->stCap;
-    ScoreArgs A;
     for (int attempt = 0;; ++attempt) {
         if (attempt > 4) return fail(KASA_E_LIMIT, "score staging did not converge");
         if (c->stCap >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "the score rows of this batch need %llu staging records (limit 2^32); split the batch", (unsigned long long)c->stCap);
         if (!gp && c->keyCapScore >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "the profile of this batch needs %llu keys (limit 2^32); split the batch", (unsigned long long)c->keyCapScore);
         if ((rc = c->st.reserve(c->stCap * 8)) || (!gp && (rc = c->profKeys.reserve(c->keyCapScore * 8 + 64)))) return rc;
-        HIPCHK(hipMemsetAsync(counters + 2, 0, 8, c->stream));  // error flags, fallback count
-        HIPCHK(hipMemsetAsync(counters + 8, 0, 32, c->stream));
-        HIPCHK(hipMemsetAsync(stCursor, 0, 8, c->stream));             // staging cursor
-        HIPCHK(hipMemsetAsync(keyCursor, 0, 8, c->stream));
-        HIPCHK(hipMemsetAsync(clsCount, 0, 12, c->stream));            // a rerun lists the rows anew
-        nCls[0] = nCls[1] = nCls[2] = 0; nHanded = 0;
-        HIPCHK(hipMemsetAsync(c->rowLen.p, 0, (size_t)nReads * 4, c->stream));
-        A.rec = c->rec.as<uint32_t>(); A.recCW = c->recCW; A.recQS = c->recCW == 8u ? 1u : 2u; A.kmerOff = c->kmerOff.as<uint64_t>();
-        // long rows for long reads: the streaming row merge keeps a slot per taxon in LDS (up to 4096 taxa), the bitmap merge must be the one in use (test tap 4: the sorting merge)
-        A.rowPerQuery = (nTaxa <= 4096u && !(c->debugFlags & 4) && !(getenv("KASA_NO_LONG_ROWS") && atoi(getenv("KASA_NO_LONG_ROWS")))) ? 8u : 0u;   // (KASA_NO_LONG_ROWS=1: round 5's limit, tests)
-        A.pool = c->pool.as<uint32_t>(); A.nReads = nReads; A.kHigh = c->kHigh; A.kLow = c->kLow; A.nTaxa = nTaxa;
-        A.scratch = nullptr; A.mainOut = nullptr; A.otherOff64 = nullptr; A.nQ = (uint32_t)nQ;
-        A.cntUnique = c->cntUnique.as<uint64_t>(); A.cntAllHi = c->cntAllHi.as<uint64_t>(); A.cntAllMid = c->cntAllMid.as<uint64_t>(); A.cntAllLo = c->cntAllLo.as<uint64_t>();
-        A.rowPos = c->rowPos.as<uint32_t>(); A.rowLen = c->rowLen.as<uint32_t>();
-        A.st = c->st.as<uint2>();
-        A.stCap = (uint32_t)c->stCap; A.stCursor = stCursor; A.errFlag = counters + 2;
-        A.rowKey = c->rowKey.as<uint32_t>(); A.keyCap = gp ? 0xFFFFFFFFu : (uint32_t)c->keyCapScore; A.keyCursor = keyCursor;
-        A.wantPerRead = wantPerRead ? 1 : 0;
-        A.addProfile = gp ? 0 : (slowProfileDone ? 0 : 1);
-        A.list = nullptr; A.nList = 0; A.flushPos = nullptr; A.flushOff = nullptr;
-        A.fbList = c->fbList.as<uint32_t>(); A.fbCount = counters + 3; A.why = counters + 8;
-        for (int k = 0; k < 3; ++k) { A.clsLo[k] = clsLo[k]; A.clsList[k] = c->clsList.as<uint32_t>() + (size_t)k * nReads; }
-        A.clsCount = bitmapMerge ? clsCount : nullptr;                  // (the sorting merge takes every row in one launch)
-        A.ovList = nullptr; A.ovCount = nullptr; A.workCursor = nullptr; A.forceHandOn = (c->debugFlags & 16384) ? 1 : 0;
-        if ((rc = timer_begin(c, c->timers[KASA_STAGE_SCORE], &a, &b))) return rc;
-        uint32_t nSlow = nReads;
-        if (fast) {
-            // persistent wavefronts: as many as are resident at once, each takes 64 reads at a time from a work counter
-            int perCu = 0, nCu = 0;
-            const bool fb8 = c->maxCnt <= 255u;                              // 8-bit counter fields: twice the wavefronts per CU
-            const bool lv19 = RW == 16 && nK <= 19;                          // (the default -k 25 7 has 19 levels)
-            typedef void (*MainKernel)(ScoreArgs);
-            const bool lv6 = RW == 8 && nK <= 6;                             // (the default -k 12 7 has 6 levels: smaller LDS tables, one more wavefront per SIMD)
-            const MainKernel kern = (RW == 8 && fb8 && wantPerRead && (c->debugFlags & 1024)) ? score_main_kernel<8, true, 8, 8, true> :
-                                    (lv6 && fb8) ? (wantPerRead ? score_main_kernel<8, true, 8, 6> : score_main_kernel<8, false, 8, 6>) :
-                                    RW == 8 ? (fb8 ? (wantPerRead ? score_main_kernel<8, true, 8> : score_main_kernel<8, false, 8>)
-                                                   : (wantPerRead ? score_main_kernel<8, true> : score_main_kernel<8, false>))
-                                  : lv19 ? (fb8 ? (wantPerRead ? score_main_kernel<16, true, 8, 19> : score_main_kernel<16, false, 8, 19>)
-                                                : (wantPerRead ? score_main_kernel<16, true, 16, 19> : score_main_kernel<16, false, 16, 19>))
-                                         : (fb8 ? (wantPerRead ? score_main_kernel<16, true, 8> : score_main_kernel<16, false, 8>)
-                                                : (wantPerRead ? score_main_kernel<16, true> : score_main_kernel<16, false>));
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *)kern, 64, 0));
-            HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
-            const uint32_t fblocks = std::min<uint32_t>((nReads + 63) / 64, (uint32_t)std::max(1, perCu) * (uint32_t)std::max(1, nCu));
-            if ((rc = c->fastScratch.reserve((size_t)nReads * 16 + 64))) return rc;
-            A.mainOut = c->fastScratch.as<uint32_t>();
-            if ((rc = c->plist.reserve((nQ / 64 + 2) * 4 + 64))) return rc;      // (free once the slots are known)
-            A.otherOff64 = c->plist.as<uint32_t>();
-            A.workCursor = counters + 6;
-            HIPCHK(hipMemsetAsync(counters + 6, 0, 4, c->stream));
-            const unsigned oblocks = std::min<unsigned>(blocks_for(nQ, 256), 256u * 64u);
-            hipEvent_t ka, kb;
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_SCORE_MAIN], &ka, &kb))) return rc;
-            kern<<<fblocks, 64, 0, c->stream>>>(A);
-            HIPCHK(hipGetLastError());
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SCORE_MAIN], ka, kb))) return rc;
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_SCORE_OTHER], &ka, &kb))) return rc;
-            const bool flat = RW == 8 && !(c->debugFlags & 32);              // debug flag 32: the per-lane kernels
-            if (RW == 16 && !(c->debugFlags & 32)) {
-                const unsigned fblocks16 = std::min<unsigned>(blocks_for(nQ, 128), 256u * 128u);
-                if (nK <= 19) {
-                    if (wantPerRead) score_other_flat16_kernel<true, 19><<<fblocks16, 128, 0, c->stream>>>(A);
-                    else score_other_flat16_kernel<false, 19><<<fblocks16, 128, 0, c->stream>>>(A);
-                } else if (wantPerRead) score_other_flat16_kernel<true><<<fblocks16, 128, 0, c->stream>>>(A);
-                else score_other_flat16_kernel<false><<<fblocks16, 128, 0, c->stream>>>(A);
-            } else
-            if (wantPerRead) { if (flat) score_other_flat_kernel<true><<<oblocks, 256, 0, c->stream>>>(A); else if (RW == 8) score_other_kernel<8, true><<<oblocks, 256, 0, c->stream>>>(A); else score_other_kernel<16, true><<<oblocks, 256, 0, c->stream>>>(A); }
-            else { if (flat) score_other_flat_kernel<false><<<oblocks, 256, 0, c->stream>>>(A); else if (RW == 8) score_other_kernel<8, false><<<oblocks, 256, 0, c->stream>>>(A); else score_other_kernel<16, false><<<oblocks, 256, 0, c->stream>>>(A); }
-            HIPCHK(hipGetLastError());
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SCORE_OTHER], ka, kb))) return rc;
-            uint32_t h3 = 0; unsigned long long want[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(&h3, counters + 3, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(want, stCursor, gp ? 8 : 16, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(nCls, clsCount, 12, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            nSlow = h3; nHanded = h3;
-            if (want[0] > c->stCap || (!gp && want[1] > c->keyCapScore)) {   // the fast kernels have no side effects: grow and rerun
-                if ((rc = timer_end(c, c->timers[KASA_STAGE_SCORE], a, b))) return rc;
-                if (want[0] > c->stCap) c->stCap = want[0] + want[0] / 8 + (uint64_t)nSlow * 64 + 1024;
-                if (!gp && want[1] > c->keyCapScore) c->keyCapScore = want[1] + want[1] / 8 + 1024;
-                continue;
-            }
-            nKeys = gp ? 0 : want[1];
-            A.list = c->fbList.as<uint32_t>(); A.nList = nSlow;
+        if ((rc = score_begin_attempt(c, R)) || (rc = R.stage.begin())) return rc;
+        if (R.fast) {
+            bool rerun = false;
+            if ((rc = score_fast_pair(c, R, &rerun))) return rc;
+            if (rerun) continue;
         }
         c->lastDenseReads = 0;
-        if (fast && nSlow > 0 && gp && wantPerRead && nTaxa * 5u * SD_WAVES <= 160u * 1024u - 1024u && !(c->debugFlags & 33554432)) {   // (the rows of a workgroup's reads fit LDS; test tap 33554432: never)
-            // reads the fast kernels handed over (long rows, as a rule): those that keep the order rule need no pending window
-            hipEvent_t da, db;
-            if ((rc = c->fbList2.reserve((size_t)nSlow * 4 + 64))) return rc;
-            uint32_t *handCount = counters + 70;
-            HIPCHK(hipMemsetAsync(handCount, 0, 4, c->stream));
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_SCORE_DENSE], &da, &db))) return rc;
-            static const int denseTap = getenv("KASA_DENSE_TAP") ? atoi(getenv("KASA_DENSE_TAP")) : 0;
-            const int keepHandOn = A.forceHandOn;
-            A.forceHandOn = denseTap;
-            const size_t rowLds = ((size_t)nTaxa * 4 + (((size_t)nTaxa + 3) / 4) * 4) * SD_WAVES;
-            const uint32_t dblocks = std::min<uint32_t>((nSlow + SD_WAVES - 1) / SD_WAVES, 256u * 8u);
-            if (nK <= 6) {
-                HIPCHK(hipFuncSetAttribute((const void *)score_dense_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                score_dense_kernel<6><<<dblocks, 64 * SD_WAVES, rowLds, c->stream>>>(A, c->fbList2.as<uint32_t>(), handCount);
-            } else {
-                HIPCHK(hipFuncSetAttribute((const void *)score_dense_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                score_dense_kernel<8><<<dblocks, 64 * SD_WAVES, rowLds, c->stream>>>(A, c->fbList2.as<uint32_t>(), handCount);
-            }
-            HIPCHK(hipGetLastError());
-            A.forceHandOn = keepHandOn;
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SCORE_DENSE], da, db))) return rc;
-            uint32_t handed = 0;
-            HIPCHK(hipMemcpyAsync(&handed, handCount, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            c->lastDenseReads = nSlow - handed;
-            nSlow = handed;
-            A.list = c->fbList2.as<uint32_t>(); A.nList = nSlow;
-        }
+        if (R.fast && R.nSlow > 0 && gp && wantPerRead && nTaxa * 5u * SD_WAVES <= 160u * 1024u - 1024u && !(c->debugFlags & 33554432) &&   // (the rows of a workgroup's reads fit LDS; test tap 33554432: never)
+            (rc = score_dense_pass(c, R))) return rc;
         c->lastReplayReads = 0; c->lastReplayEvents = 0;
-        if (nSlow > 0 && (wantPerRead || !gp) && !(c->debugFlags & 536870912)) {   // (test tap 536870912: never)
-            // very long reads: events sorted by (read, taxon, flush position, level), one float chain per (read, taxon) (kasa_replay.h)
-            const uint32_t minEnv = getenv("KASA_ESR_MIN_KMERS") ? (uint32_t)strtoul(getenv("KASA_ESR_MIN_KMERS"), nullptr, 10) : 0u;   // (tests: short reads through it)
-            const uint32_t minK = (c->debugFlags & 1073741824) ? 1u : (minEnv ? minEnv : ESR_MIN_KMERS);   // (test tap 1073741824: every read of the general kernel's list)
-            hipEvent_t ea, eb;
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_SCORE_REPLAY], &ea, &eb))) return rc;
-            const uint32_t *rest = nullptr; uint32_t nRest = 0;
-            if ((rc = esr_stage(c, A, nSlow, minK, &rest, &nRest, counters))) return rc;
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SCORE_REPLAY], ea, eb))) return rc;
-            if (c->lastReplayReads) { A.list = rest; A.nList = nRest; nSlow = nRest; if (!gp) replayAddedProfile = true; }
-        }
-        hipEvent_t ga = nullptr, gb = nullptr;
-        if (nSlow > 0 && (rc = timer_begin(c, c->kernels[KASA_KERNEL_SCORE_GENERAL], &ga, &gb))) return rc;
-        if (nSlow > 0) {
-            // flush positions of the listed reads' queries (the records hold only the order inside a query)
-            const uint64_t *flushOff = c->kmerOff.as<uint64_t>();
-            uint64_t nFq = nQ;
-            if (A.list) {
-                if ((rc = c->flushOff.reserve(((size_t)nSlow + 1) * 8 + 64))) return rc;
-                list_counts_kernel<<<blocks_for((uint64_t)nSlow + 1, 256), 256, 0, c->stream>>>(A.list, nSlow, c->kmerOff.as<uint64_t>(), c->flushOff.as<uint64_t>());
-                size_t tmpBytes = 0;
-                HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, c->flushOff.as<uint64_t>(), c->flushOff.as<uint64_t>(), (uint64_t)0, (size_t)nSlow + 1, rocprim::plus<uint64_t>(), c->stream));
-                if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-                HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, c->flushOff.as<uint64_t>(), c->flushOff.as<uint64_t>(), (uint64_t)0, (size_t)nSlow + 1, rocprim::plus<uint64_t>(), c->stream));
-                HIPCHK(hipMemcpyAsync(&nFq, c->flushOff.as<uint64_t>() + nSlow, 8, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                flushOff = c->flushOff.as<uint64_t>();
-            }
-            if ((rc = c->flushPos.reserve(nFq * (size_t)nK * 4 + 64))) return rc;
-            if ((rc = (RW == 8 ? launch_flush<8>(c, A.list, nSlow, flushOff, c->flushPos.as<uint32_t>()) : launch_flush<16>(c, A.list, nSlow, flushOff, c->flushPos.as<uint32_t>())))) return rc;
-            A.flushPos = c->flushPos.as<uint32_t>(); A.flushOff = flushOff;
-            const uint64_t rowBytes = (uint64_t)nTaxa * 4;
-            const uint32_t maxBlocks = (uint32_t)std::max<uint64_t>(1024, std::min<uint64_t>(256u * 32u, (8ull << 30) / rowBytes));
-            const uint32_t blocks = std::min<uint32_t>(nSlow, maxBlocks);
-            if ((rc = c->scratch.reserve((size_t)blocks * rowBytes)) || (rc = c->ovList.reserve((size_t)nSlow * 4 + 64))) return rc;
-            HIPCHK(hipMemsetAsync(c->scratch.p, 0, (size_t)blocks * rowBytes, c->stream));
-            HIPCHK(hipMemsetAsync(counters + 5, 0, 4, c->stream));
-            A.scratch = c->scratch.as<float>();
-            A.ovList = c->ovList.as<uint32_t>(); A.ovCount = counters + 5;
-            const bool dense = nTaxa <= (uint32_t)DENSE_TAXA && !(c->debugFlags & 8192);   // (test tap 8192: the lane-owns-its-cells form)
-            const size_t rowLds = dense ? (size_t)nTaxa * 4 : 0;
-            if (dense) {
-                HIPCHK(hipFuncSetAttribute((const void *)score_kernel<PCAP_SMALL, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                HIPCHK(hipFuncSetAttribute((const void *)score_kernel<PCAP_SMALL, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                HIPCHK(hipFuncSetAttribute((const void *)score_kernel<PCAP, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                HIPCHK(hipFuncSetAttribute((const void *)score_kernel<PCAP, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                if (RW == 8) score_kernel<PCAP_SMALL, 8, true><<<blocks, 64, rowLds, c->stream>>>(A);
-                else score_kernel<PCAP_SMALL, 16, true><<<blocks, 64, rowLds, c->stream>>>(A);
-            } else
-            if (RW == 8) score_kernel<PCAP_SMALL, 8><<<blocks, 64, 0, c->stream>>>(A);      // leaves every score row zeroed again
-            else score_kernel<PCAP_SMALL, 16><<<blocks, 64, 0, c->stream>>>(A);
-            HIPCHK(hipGetLastError());
-            uint32_t nOver = 0;
-            HIPCHK(hipMemcpyAsync(&nOver, counters + 5, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            // Later passes over a list of reads: the flush positions are addressed through the list, so its offsets are made anew.
-            // which = 2: the window of PCAP groups in LDS; narrow records hand a read whose window overflows even that to
-            // which = 3: the window in device memory (GWIN), as long as the longest read has queries times levels.
-            auto laterPass = [&](const uint32_t *list, uint32_t n, int which, uint32_t *ovOut, uint32_t *ovCnt) -> int {
-                int rc2;
-                if ((rc2 = c->flushOff2.reserve(((size_t)n + 1) * 8 + 64))) return rc2;
-                uint32_t *longest = counters + 4;
-                HIPCHK(hipMemsetAsync(longest, 0, 4, c->stream));
-                list_counts_kernel<<<blocks_for((uint64_t)n + 1, 256), 256, 0, c->stream>>>(list, n, c->kmerOff.as<uint64_t>(), c->flushOff2.as<uint64_t>(), longest);
-                size_t tmpBytes = 0;
-                HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, c->flushOff2.as<uint64_t>(), c->flushOff2.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), c->stream));
-                if ((rc2 = c->sortTmp.reserve(tmpBytes))) return rc2;
-                HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, c->flushOff2.as<uint64_t>(), c->flushOff2.as<uint64_t>(), (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), c->stream));
-                uint64_t nFq2 = 0; uint32_t hLongest = 0;
-                HIPCHK(hipMemcpyAsync(&nFq2, c->flushOff2.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipMemcpyAsync(&hLongest, longest, 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if ((rc2 = c->flushPos2.reserve(nFq2 * (size_t)nK * 4 + 64))) return rc2;
-                if ((rc2 = (RW == 8 ? launch_flush<8>(c, list, n, c->flushOff2.as<uint64_t>(), c->flushPos2.as<uint32_t>()) : launch_flush<16>(c, list, n, c->flushOff2.as<uint64_t>(), c->flushPos2.as<uint32_t>())))) return rc2;
-                A.list = list; A.nList = n;
-                A.flushPos = c->flushPos2.as<uint32_t>(); A.flushOff = c->flushOff2.as<uint64_t>();
-                A.ovList = ovOut; A.ovCount = ovCnt;
-                A.forceHandOn = (ovOut && (c->debugFlags & 8388608)) ? 1 : 0;   // (test tap 8388608: the second pass hands every read to the third)
-                if (which == 3) {
-                    // (per block four arrays as long as the batch's longest read has queries times levels: no read can overflow them)
-                    const uint64_t cap = std::max<uint64_t>(64, (uint64_t)hLongest * (uint64_t)nK + 64);
-                    const uint32_t b3 = std::min<uint32_t>(n, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(256, (2ull << 30) / (cap * 16))));
-                    if (cap > 0xFFFFFFFFull) return fail(KASA_E_LIMIT, "a read of %llu k-mers keeps more groups pending than this build can hold", (unsigned long long)hLongest);
-                    if ((rc2 = c->gwin.reserve((size_t)b3 * cap * 16 + 64))) return rc2;
-                    A.gwin = c->gwin.as<uint32_t>(); A.gwinCap = (uint32_t)cap;
-                    if (dense) {
-                        HIPCHK(hipFuncSetAttribute((const void *)score_kernel<1, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rowLds));
-                        score_kernel<1, 8, true, true><<<b3, 64, rowLds, c->stream>>>(A);
-                    } else score_kernel<1, 8, false, true><<<b3, 64, 0, c->stream>>>(A);
-                } else {
-                    const uint32_t b2 = std::min<uint32_t>(n, std::min<uint32_t>(blocks, 256u * 16u));
-                    if (dense) {
-                        if (RW == 8) score_kernel<PCAP, 8, true><<<b2, 64, rowLds, c->stream>>>(A);
-                        else score_kernel<PCAP, 16, true><<<b2, 64, rowLds, c->stream>>>(A);
-                    } else
-                    if (RW == 8) score_kernel<PCAP, 8><<<b2, 64, 0, c->stream>>>(A);
-                    else score_kernel<PCAP, 16><<<b2, 64, 0, c->stream>>>(A);
-                }
-                HIPCHK(hipGetLastError());
-                return KASA_OK;
-            };
-            if (nOver > 0) {
-                // second pass.  64-byte records add to the profile as they go (nothing to take back): their window must hold --
-                // KASA_E_LIMIT otherwise.  Narrow records leave no trace of a read they hand on (the profile is group_stage's).
-                uint32_t *ov2 = nullptr, *ov2Cnt = nullptr;
-                if (RW == 8 && gp) {
-                    if ((rc = c->ovList2.reserve((size_t)nOver * 4 + 64))) return rc;
-                    ov2 = c->ovList2.as<uint32_t>(); ov2Cnt = counters + 7;
-                    HIPCHK(hipMemsetAsync(ov2Cnt, 0, 4, c->stream));
-                }
-                if ((rc = laterPass(c->ovList.as<uint32_t>(), nOver, 2, ov2, ov2Cnt))) return rc;
-                if (ov2) {
-                    uint32_t nOver2 = 0;
-                    HIPCHK(hipMemcpyAsync(&nOver2, ov2Cnt, 4, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(hipStreamSynchronize(c->stream));
-                    if (nOver2 > 0 && (rc = laterPass(ov2, nOver2, 3, nullptr, nullptr))) return rc;
-                    c->lastThirdPassReads = std::max(c->lastThirdPassReads, nOver2);
-                }
-            }
-            c->lastOverflowReads = std::max(c->lastOverflowReads, nOver);   // over the staging retries of this batch
-            slowProfileDone = true;
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_SCORE_GENERAL], ga, gb))) return rc;
-        }
-        if (replayAddedProfile) slowProfileDone = true;              // (64-byte records: the replay added its reads' events to the tables -- once, whatever is rerun)
-        c->lastSlowReads = nSlow;
-        if ((rc = timer_end(c, c->timers[KASA_STAGE_SCORE], a, b))) return rc;
+        if (R.nSlow > 0 && (wantPerRead || !gp) && !(c->debugFlags & 536870912) && (rc = score_replay_handover(c, R))) return rc;   // (test tap 536870912: never)
+        if (R.nSlow > 0 && (rc = score_general(c, R))) return rc;
+        if (R.replayAddedProfile) R.slowProfileDone = true;          // (64-byte records: the replay added its reads' events to the tables -- once, whatever is rerun)
+        c->lastSlowReads = R.nSlow;
+        if ((rc = R.stage.end())) return rc;
         uint32_t err = 0; unsigned long long want = 0;
-        HIPCHK(hipMemcpyAsync(&err, counters + 2, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&want, stCursor, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = fetch_async(c->stream, err, &c->ctr()->score.err)) || (rc = fetch(c->stream, want, R.A.stCursor))) return rc;
         if (err & 2u) return fail(KASA_E_LIMIT, "a read keeps more than %d distinct groups pending; this build cannot order it", PCAP);
-        if (want <= c->stCap) { staged = want; break; }
+        if (want <= c->stCap) { R.staged = want; break; }
         c->stCap = want + want / 8 + 1024;
     }
     if (c->keepStagedLengths) {                  // (tests: the rows' lengths as the score kernels left them)
@@ -6710,82 +6865,14 @@ static int score_stage(kasa_ctx *c, int wantPerRead)
         HIPCHK(hipStreamSynchronize(c->stream));
         for (uint32_t &v : c->stagedLengths) v &= ~ROW_MERGE;
     } else c->stagedLengths.clear();
-    // ---- resolve the fast kernels' records: per-read merge
-    if (fast) {                                  // (the first class: the reads the fast kernels kept, rows without records among them)
-        c->rowClasses[0] = (uint64_t)nReads - nHanded - nCls[0] - nCls[1] - nCls[2];
-        for (int k = 0; k < 3; ++k) c->rowClasses[k + 1] = nCls[k];
+    if (R.fast) {                                // (the first class: the reads the fast kernels kept, rows without records among them)
+        c->rowClasses[0] = (uint64_t)nReads - R.nHanded - R.nCls[0] - R.nCls[1] - R.nCls[2];
+        for (int k = 0; k < 3; ++k) c->rowClasses[k + 1] = R.nCls[k];
     }
-    bool mergePending = false;
-    if (fast && staged > 0) {
-        const ProfLayout PL = prof_layout(nTaxa, nK);
-        if ((rc = timer_begin(c, c->timers[KASA_STAGE_SCORE], &a, &b))) return rc;
-        hipEvent_t ka, kb;
-        if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_ROW_MERGE], &ka, &kb))) return rc;
-        uint64_t *noKeys = gp ? nullptr : c->profKeys.as<uint64_t>();   // (narrow records: the rows' events leave no profile keys -- group_stage)
-        if (bitmapMerge) {
-            // The first class sweeps all reads (nearly every row is its own); the upper classes and LONG walk the rows
-            // score_main_kernel listed for them and are not launched when there are none.  As many workgroups as are resident.
-            typedef void (*MergeKernel)(const uint32_t *, uint32_t *, const uint32_t *, const uint32_t *, uint32_t, uint2 *, uint64_t *, int, uint32_t, uint32_t, ProfLayout);
-            int nCu = 0;
-            HIPCHK(hipDeviceGetAttribute(&nCu, hipDeviceAttributeMultiprocessorCount, c->device));
-            auto merge = [&](MergeKernel kern, const uint32_t *list, uint32_t rows, uint32_t mLo) -> int {
-                if (rows == 0) return KASA_OK;
-                int perCu = 0;
-                HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *)kern, 64, 0));
-                uint32_t grid = (uint32_t)std::max(1, perCu) * (uint32_t)std::max(1, nCu);
-                if (c->rowMergeBlocks) grid = std::min(grid, c->rowMergeBlocks);
-                kern<<<std::min(rows, grid), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(), c->rowKey.as<uint32_t>(), list, rows,
-                                                               c->st.as<uint2>(), noKeys, c->kHigh, nTaxa, mLo, PL);
-                HIPCHK(hipGetLastError());
-                return KASA_OK;
-            };
-            const bool narrow = nTaxa <= 2048u;                      // (the wide bitmap beyond: the same sizes, no second class)
-            if ((rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<256, 64> : (MergeKernel)row_merge_bitmap_kernel<256, BM_WORDS>, nullptr, nReads, 0u)) ||
-                (rc = merge(row_merge_bitmap_kernel<512, 64>, A.clsList[0], narrow ? nCls[0] : 0u, clsLo[0])) ||
-                (rc = merge(row_merge_bitmap_kernel<RMAX, BM_WORDS>, A.clsList[1], nCls[1], clsLo[1])) ||
-                // long reads' rows (beyond RMAX records): streamed, slots in LDS
-                (rc = merge(narrow ? (MergeKernel)row_merge_bitmap_kernel<2048, 64, true> : (MergeKernel)row_merge_bitmap_kernel<4096, 128, true>, A.clsList[2], nCls[2], clsLo[2])))
-                return rc;
-        } else
-            row_merge_kernel<<<std::min<uint32_t>(nReads, c->rowMergeBlocks ? c->rowMergeBlocks : 256u * 24u), 64, 0, c->stream>>>(c->rowPos.as<uint32_t>(), c->rowLen.as<uint32_t>(),
-                c->rowKey.as<uint32_t>(), nReads, c->st.as<uint2>(), noKeys, c->kHigh, PL);
-        HIPCHK(hipGetLastError());
-        if ((rc = timer_end(c, c->kernels[KASA_KERNEL_ROW_MERGE], ka, kb))) return rc;
-        c->lastStaged = staged;
-        if (!gp) {
-            c->lastKeys = nKeys;
-            if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_PROFILE_TABLES], &ka, &kb))) return rc;
-            if ((rc = profile_from_keys(c, nKeys, false))) return rc;
-            if ((rc = timer_end(c, c->kernels[KASA_KERNEL_PROFILE_TABLES], ka, kb))) return rc;
-        }
-        mergePending = true;
-    }
-    if (wantPerRead) {
-        // CSR offsets = exclusive scan of the row lengths, then rows copied in read order
-        if (!mergePending && (rc = timer_begin(c, c->timers[KASA_STAGE_SCORE], &a, &b))) return rc;
-        DevBuf &len64 = c->qReadA; // reuse
-        if ((rc = len64.reserve(((size_t)nReads + 1) * 8 + 64))) return rc;
-        hipEvent_t ca, cb;
-        if ((rc = timer_begin(c, c->kernels[KASA_KERNEL_ROW_COPY], &ca, &cb))) return rc;
-        HIPCHK(hipMemsetAsync(len64.p, 0, ((size_t)nReads + 1) * 8, c->stream));
-        widen_kernel<<<blocks_for(nReads, 256), 256, 0, c->stream>>>(c->rowLen.as<uint32_t>(), len64.as<uint64_t>(), nReads);
-        size_t tmpBytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, len64.as<uint64_t>(), c->rowOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1,
-                                       rocprim::plus<uint64_t>(), c->stream));
-        if ((rc = c->scanTmp.reserve(tmpBytes))) return rc;              // (not sortTmp: the profile's leftover sort is queued with that)
-        HIPCHK(rocprim::exclusive_scan(c->scanTmp.p, tmpBytes, len64.as<uint64_t>(), c->rowOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1,
-                                       rocprim::plus<uint64_t>(), c->stream));
-        uint64_t nnz = 0;
-        HIPCHK(hipMemcpyAsync(&nnz, c->rowOff.as<uint64_t>() + nReads, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->nnz = nnz;
-        // The rows stay where the score kernels left them ({taxon, score} pairs in the staging buffer, row r at rowPos[r], rowOff
-        // = the running sum of their lengths): kasa_batch_rank reads them there.  Only a host that asks for the whole CSR
-        // (kasa_batch_scores_fetch) has them packed into two arrays first (csr_pack: the copy every batch paid until round 4).
-        c->csrPacked = false;
-        if ((rc = timer_end(c, c->kernels[KASA_KERNEL_ROW_COPY], ca, cb))) return rc;
-    }
-    if (mergePending || wantPerRead) { if ((rc = timer_end(c, c->timers[KASA_STAGE_SCORE], a, b))) return rc; }
+    // the stage's span is opened by the first of the two steps that runs, and closed behind the last
+    if (R.fast && R.staged > 0 && (rc = score_row_merge(c, R))) return rc;
+    if (wantPerRead && (rc = score_csr_offsets(c, R))) return rc;
+    if (R.stage.open() && (rc = R.stage.end())) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     if (wantPerRead) c->haveScores = true;
     c->state = 4;
@@ -7113,13 +7200,8 @@ static int wire_offsets(kasa_ctx *c, const uint32_t *rec, const uint8_t *classes
     HIPCHK(hipMemsetAsync(off + nBlocks, 0, 8, c->stream));
     if (c->recWords() == 8) wire_count_kernel<8, FROM_RECORDS><<<(unsigned)nBlocks, 256, 0, c->stream>>>(rec, classes, n, off);
     else wire_count_kernel<16, FROM_RECORDS><<<(unsigned)nBlocks, 256, 0, c->stream>>>(rec, classes, n, off);
-    size_t tmpBytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, off, off, (uint64_t)0, (size_t)nBlocks + 1, rocprim::plus<uint64_t>(), c->stream));
-    if ((rc = c->scanTmp.reserve(tmpBytes))) return rc;
-    HIPCHK(rocprim::exclusive_scan(c->scanTmp.p, tmpBytes, off, off, (uint64_t)0, (size_t)nBlocks + 1, rocprim::plus<uint64_t>(), c->stream));
-    HIPCHK(hipMemcpyAsync(totalWords, off + nBlocks, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return KASA_OK;
+    if ((rc = dev_exclusive_scan(c->scanTmp, c->stream, off, off, (uint64_t)0, (size_t)nBlocks + 1, rocprim::plus<uint64_t>()))) return rc;
+    return fetch(c->stream, *totalWords, off + nBlocks);
 }
 
 extern "C" int kasa_batch_records_pack_size(kasa_ctx *c, const uint32_t *recordsDev, uint64_t nQueries, uint64_t *nBytes)
@@ -7609,16 +7691,16 @@ extern "C" int kasa_batch_rank(kasa_ctx *c, const double *den, uint32_t nClasses
         return rc;
     HIPCHK(hipMemcpyAsync(c->rankDen.p, den, (size_t)nClasses * nTaxa * 8, hipMemcpyHostToDevice, c->stream));
     if (nReads) HIPCHK(hipMemcpyAsync(c->rankClass.p, readClass, (size_t)nReads * 4, hipMemcpyHostToDevice, c->stream));
-    unsigned long long *cursor = c->misc.as<unsigned long long>() + 20;
-    uint32_t *flagged = c->misc.as<uint32_t>() + 42, *nClass = c->misc.as<uint32_t>() + 64;   // ([64..67]: flagged reads per class of hit count)
+    unsigned long long *cursor = &c->ctr()->rankCursor;
+    uint32_t *flagged = &c->ctr()->rankFlagged, *nClass = c->ctr()->rankClass;          // (flagged reads per class of hit count)
     if (c->rankCap == 0) c->rankCap = std::max<uint64_t>(1 << 20, (uint64_t)nReads * 4 + (uint64_t)RANK_SLAB * 256u * 32u * 4u);
     c->rankEntries = 0; *nEntries = 0; *nFlagged = 0; c->rankValid = false; c->txtValid = false;
     if (nReads == 0) { c->rankValid = true; c->rankFlagged = 0; return KASA_OK; }
     for (int attempt = 0; attempt < 6; ++attempt) {
         if ((rc = c->rankOut.reserve(c->rankCap * sizeof(RankEntry)))) return rc;
-        HIPCHK(hipMemsetAsync(cursor, 0, 8, c->stream));
-        HIPCHK(hipMemsetAsync(flagged, 0, 4, c->stream));
-        HIPCHK(hipMemsetAsync(nClass, 0, 16, c->stream));
+        HIPCHK(hipMemsetAsync(cursor, 0, sizeof(*cursor), c->stream));
+        HIPCHK(hipMemsetAsync(flagged, 0, sizeof(*flagged), c->stream));
+        HIPCHK(hipMemsetAsync(nClass, 0, sizeof(CtxCounters::rankClass), c->stream));
         // reads with tied hits are handed to rank_exact_kernel: their compacted hits wait where the row lies (16 bytes per cell)
         const bool exact = c->nnz > 0 && !(c->debugFlags & 256);           // (test tap 256: leave them to the host)
         // (20 bytes per CSR cell.  The event records are dead once the batch is scored: their buffer serves when it is large
@@ -7634,24 +7716,16 @@ extern "C" int kasa_batch_rank(kasa_ctx *c, const double *den, uint32_t nClasses
                                                    c->rankMeta.as<uint4>(), c->rankOut.as<RankEntry>(), c->rankCap, cursor, flagged, handOver, handKey, nClass);
         HIPCHK(hipGetLastError());
         unsigned long long used = 0; uint32_t nf = 0, hClass[4] = {0u, 0u, 0u, 0u};
-        HIPCHK(hipMemcpyAsync(&used, cursor, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(&nf, flagged, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(hClass, nClass, 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = fetch_async(c->stream, used, cursor)) || (rc = fetch_async(c->stream, nf, flagged)) || (rc = fetch(c->stream, hClass, nClass))) return rc;
         if (nf > 0 && used <= c->rankCap && exact) {
             // the reads the wavefront-per-read kernel left: std::sort's own order, one thread per read (rank_exact_kernel)
             if ((rc = c->rankList.reserve((size_t)nf * 16 + 64))) return rc;
             uint32_t *list0 = c->rankList.as<uint32_t>(), *key0 = list0 + nf, *list1 = key0 + nf, *key1 = list1 + nf;
-            uint32_t *nList = c->misc.as<uint32_t>() + 45;
-            HIPCHK(hipMemsetAsync(nList, 0, 4, c->stream));
-            HIPCHK(hipMemsetAsync(flagged, 0, 4, c->stream));
+            uint32_t *nList = &c->ctr()->rankListLen;
+            HIPCHK(hipMemsetAsync(nList, 0, sizeof(*nList), c->stream));
+            HIPCHK(hipMemsetAsync(flagged, 0, sizeof(*flagged), c->stream));
             rank_list_kernel<<<blocks_for(nReads, 256), 256, 0, c->stream>>>(c->rankMeta.as<uint4>(), nReads, list0, key0, nList);
-            {
-                size_t tmpBytes = 0;
-                HIPCHK(rocprim::radix_sort_pairs(nullptr, tmpBytes, key0, key1, list0, list1, (size_t)nf, 0u, 16u, c->stream));
-                if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-                HIPCHK(rocprim::radix_sort_pairs(c->sortTmp.p, tmpBytes, key0, key1, list0, list1, (size_t)nf, 0u, 16u, c->stream));
-            }
+            if ((rc = dev_sort_pairs(c->sortTmp, c->stream, key0, key1, list0, list1, (size_t)nf, 0u, 16u))) return rc;
             // the list is sorted by the number of hits: one launch per class, the LDS a read's hits take cut to the class
             if (hClass[0] + hClass[1] + hClass[2] + hClass[3] != nf) return fail(KASA_E_HIP, "kasa_batch_rank: the classes of the flagged reads do not add up");
             uint32_t from = 0;
@@ -7671,9 +7745,7 @@ extern "C" int kasa_batch_rank(kasa_ctx *c, const double *den, uint32_t nClasses
                 HIPCHK(hipGetLastError());
                 from += nCl;
             }
-            HIPCHK(hipMemcpyAsync(&used, cursor, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(&nf, flagged, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
+            if ((rc = fetch_async(c->stream, used, cursor)) || (rc = fetch(c->stream, nf, flagged))) return rc;
         }
         if (used <= c->rankCap) { c->rankEntries = used; *nEntries = used; *nFlagged = nf; c->rankValid = true; c->rankFlagged = nf; c->txtValid = false; return KASA_OK; }
         // the kernel has no side effects: grow and rerun.  Output space is handed out in slabs per wavefront, so `used` depends a
@@ -7755,13 +7827,9 @@ extern "C" int kasa_batch_text(kasa_ctx *c, const kasa_text_params *tp, uint64_t
     HIPCHK(hipMemsetAsync(c->txtBytes.p, 0, ((size_t)nReads + 1) * 8, c->stream));
     kasa_text::text_size_kernel<<<blocks_for(nReads, 256), 256, 0, c->stream>>>(A, c->txtBytes.as<uint64_t>(), c->txtFlags.as<uint8_t>());
     HIPCHK(hipGetLastError());
-    size_t tmpBytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, c->txtBytes.as<uint64_t>(), c->txtOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>(), c->stream));
-    if ((rc = c->scanTmp.reserve(tmpBytes))) return rc;
-    HIPCHK(rocprim::exclusive_scan(c->scanTmp.p, tmpBytes, c->txtBytes.as<uint64_t>(), c->txtOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>(), c->stream));
+    if ((rc = dev_exclusive_scan(c->scanTmp, c->stream, c->txtBytes.as<uint64_t>(), c->txtOff.as<uint64_t>(), (uint64_t)0, (size_t)nReads + 1, rocprim::plus<uint64_t>()))) return rc;
     uint64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, c->txtOff.as<uint64_t>() + nReads, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = fetch(c->stream, total, c->txtOff.as<uint64_t>() + nReads))) return rc;
     if ((rc = c->txtOut.reserve(total + 64))) return rc;
     kasa_text::text_write_kernel<<<blocks_for(nReads, 64), 64, 0, c->stream>>>(A, c->txtOff.as<uint64_t>(), c->txtOut.as<char>());
     HIPCHK(hipGetLastError());
@@ -7834,20 +7902,17 @@ static int bgzf_stream(const char *who, const uint8_t *text, uint64_t n, DevBuf 
     if ((rc = members.reserve((size_t)chunk * STRIDE + 64)) || (rc = size.reserve((size_t)(chunk + 1) * 8)) || (rc = off.reserve((size_t)(chunk + 1) * 8)) ||
         (rc = out.reserve((size_t)n + (size_t)nBlk * (HEADER + 5 + TRAILER) + 64)))
         return rc;
-    size_t tmpBytes = 0;                                           // asked once, for the longest chunk: rocPRIM's need does not fall as the count grows, so it covers the shorter last one
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, size.as<uint64_t>(), off.as<uint64_t>(), (uint64_t)0, (size_t)chunk + 1, rocprim::plus<uint64_t>(), stream));
-    if ((rc = scanTmp.reserve(tmpBytes))) return rc;
-    uint64_t at = 0;                                               // bytes of the stream so far
+    uint64_t at = 0;                                              // bytes of the stream so far
     for (uint64_t b0 = 0; b0 < nBlk; b0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, nBlk - b0);
         HIPCHK(hipMemsetAsync(size.p, 0, (size_t)(cnt + 1) * 8, stream));
         deflate_kernel<<<(uint32_t)cnt, THREADS, 0, stream>>>(text + b0 * BLOCK_IN, n - b0 * BLOCK_IN, members.as<uint8_t>(), size.as<uint64_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(rocprim::exclusive_scan(scanTmp.p, tmpBytes, size.as<uint64_t>(), off.as<uint64_t>(), at, (size_t)cnt + 1, rocprim::plus<uint64_t>(), stream));
+        // (the first chunk is the longest: it reserves the scan's room for all of them)
+        if ((rc = dev_exclusive_scan(scanTmp, stream, size.as<uint64_t>(), off.as<uint64_t>(), at, (size_t)cnt + 1, rocprim::plus<uint64_t>()))) return rc;
         pack_kernel<<<(uint32_t)cnt, 256, 0, stream>>>(members.as<uint8_t>(), size.as<uint64_t>(), off.as<uint64_t>(), out.as<uint8_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&at, off.as<uint64_t>() + cnt, 8, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        if ((rc = fetch(stream, at, off.as<uint64_t>() + cnt))) return rc;
     }
     *total = at;
     return KASA_OK;
@@ -7925,7 +7990,7 @@ static int bgzf_inflate_impl(int device, const uint8_t *stream, uint64_t nBytes,
     kasa_inflate::inflate_kernel<<<(uint32_t)tab.size(), 64>>>(dStream.as<uint8_t>(), dTab.as<kasa_inflate::Member>(), (uint32_t)tab.size(), dOut.as<uint8_t>(), dStatus.as<unsigned long long>());
     HIPCHK(hipGetLastError());
     unsigned long long st = ~0ull;
-    HIPCHK(hipMemcpy(&st, dStatus.p, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&st, dStatus.p, sizeof(st), hipMemcpyDeviceToHost));
     if (st != ~0ull) { *status = (int)(st & 0xFF); *member = st >> 8; return KASA_OK; }
     if (total) HIPCHK(hipMemcpy(text, dOut.p, total, hipMemcpyDeviceToHost));
     return KASA_OK;
@@ -8198,10 +8263,11 @@ static int coh_finish(kasa_ctx *c, float *scores, uint64_t *throwsAt, const char
     unsigned long long *entryUsed = c->cohState.as<unsigned long long>(), *exitIdx = entryUsed + nChunks;
     uint32_t *failed = reinterpret_cast<uint32_t *>(exitIdx + nChunks);
     float *dScores = reinterpret_cast<float *>(failed + nChunks + (nChunks & 1u));
-    unsigned long long *firstMatch = c->misc.as<unsigned long long>() + 26;
-    uint32_t *changed = c->misc.as<uint32_t>() + 54;                                   // [54] changed exits, [55] same exits, [56] any failure
-    HIPCHK(hipMemsetAsync(firstMatch, 0xFF, 8, c->stream));
-    HIPCHK(hipMemsetAsync(changed, 0, 12, c->stream));
+    unsigned long long *firstMatch = &c->ctr()->cohFirstMatch;
+    CohExits *exits = &c->ctr()->coh;
+    uint32_t *changed = exits->walked;                                                 // changed exits, same exits
+    HIPCHK(hipMemsetAsync(firstMatch, 0xFF, sizeof(*firstMatch), c->stream));
+    HIPCHK(hipMemsetAsync(exits, 0, sizeof(CohExits), c->stream));
     if (nE > 0) {
         coh_first_kernel<<<blocks_for(nE, 256 * COH_FIRST_BYTES), 256, 0, c->stream>>>(c->cohLen.as<uint8_t>(), nE, firstMatch);
         HIPCHK(hipGetLastError());
@@ -8213,15 +8279,15 @@ static int coh_finish(kasa_ctx *c, float *scores, uint64_t *throwsAt, const char
         HIPCHK(hipGetLastError());
         if (round == 0) continue;                                                      // (round 1 compares with round 0's exits)
         uint32_t h[2] = {0, 0};
-        HIPCHK(hipMemcpyAsync(h, changed, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemsetAsync(changed, 0, 8, c->stream));
+        if ((rc = fetch_async(c->stream, h, changed))) return rc;
+        HIPCHK(hipMemsetAsync(changed, 0, sizeof(exits->walked), c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (h[0] == 0u) break;                                                         // every recomputed chunk left where it had left before
         if (round > (int)nChunks + 2) return fail(KASA_E_LIMIT, "%s: the walk did not settle", who);
     }
-    coh_any_kernel<<<blocks_for(nChunks, 256), 256, 0, c->stream>>>(failed, nChunks, changed + 2);
+    coh_any_kernel<<<blocks_for(nChunks, 256), 256, 0, c->stream>>>(failed, nChunks, &exits->anyFail);
     uint32_t anyFail = 0;
-    HIPCHK(hipMemcpyAsync(&anyFail, changed + 2, 4, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = fetch_async(c->stream, anyFail, &exits->anyFail))) return rc;
     HIPCHK(hipMemcpyAsync(scores, dScores, (size_t)nReads * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (anyFail) *throwsAt = nE;
@@ -8838,7 +8904,7 @@ extern "C" int kasa_ctx_debug(kasa_ctx *c, int forceSlowScore, uint32_t *lastSlo
     if (lastSlowReads) *lastSlowReads = c->lastSlowReads;
     if (getenv("KASA_DEBUG_WHY")) {
         uint32_t w[8];
-        if (hipMemcpy(w, c->misc.as<uint32_t>() + 8, 32, hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(w, c->ctr()->why, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "[kasa] fallback reasons: cnt=%u taxa=%u log=%u big=%u pending=%u; general kernel: %u reads, %u of them handed to the second pass\n",
                     w[0], w[1], w[2], w[3], w[4], c->lastSlowReads, c->lastOverflowReads);
     }

@@ -310,16 +310,6 @@ static int pool_compact(kasa_parser *p)
     return KASA_OK;
 }
 
-static int scan64(kasa_parser *p, uint64_t *a, size_t n)
-{
-    size_t tmpBytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, a, a, (uint64_t)0, n, rocprim::plus<uint64_t>(), p->stream));
-    int rc = p->scanTmp.reserve(tmpBytes);
-    if (rc) return rc;
-    HIPCHK(rocprim::exclusive_scan(p->scanTmp.p, tmpBytes, a, a, (uint64_t)0, n, rocprim::plus<uint64_t>(), p->stream));
-    return KASA_OK;
-}
-
 static int refuse(kasa_parser *p, int code, uint64_t at, int *parsable)
 {
     p->lastCode = code; p->lastAt = at;
@@ -371,19 +361,11 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
     uint32_t *tileCnt = p->tileCnt.as<uint32_t>();
     prs_count_kernel<<<blocks_for(nTiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint4>(), nTiles, tileCnt);
     HIPCHK(hipGetLastError());
-    {
-        size_t tmpBytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>(), p->stream));
-        if ((rc = p->scanTmp.reserve(tmpBytes))) return rc;
-        HIPCHK(rocprim::exclusive_scan(p->scanTmp.p, tmpBytes, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>(), p->stream));
-    }
+    if ((rc = dev_exclusive_scan(p->scanTmp, p->stream, tileCnt, tileCnt, 0u, (size_t)nTiles + 1, rocprim::plus<uint32_t>()))) return rc;
     uint32_t nFeeds = 0;
     uint8_t ends[2] = {(uint8_t)firstByte, (uint8_t)lastByte};
-    HIPCHK(hipMemcpyAsync(&nFeeds, tileCnt + nTiles, 4, hipMemcpyDeviceToHost, p->stream));
-    if (cut) {                                                                       // (nobody on the host has seen this text)
-        HIPCHK(hipMemcpyAsync(&ends[0], p->text.p, 1, hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(hipMemcpyAsync(&ends[1], p->text.as<uint8_t>() + nBytes - 1, 1, hipMemcpyDeviceToHost, p->stream));
-    }
+    if ((rc = fetch_async(p->stream, nFeeds, tileCnt + nTiles))) return rc;
+    if (cut && ((rc = fetch_async(p->stream, ends[0], p->text.as<uint8_t>())) || (rc = fetch_async(p->stream, ends[1], p->text.as<uint8_t>() + nBytes - 1)))) return rc;   // (nobody on the host has seen this text)
     HIPCHK(hipStreamSynchronize(p->stream));
     int trailingFeed = ends[1] == '\n';
     uint32_t nLines = nFeeds + (trailingFeed ? 0u : 1u);                               // of the whole text: the line table covers all of it
@@ -402,15 +384,14 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
         uint32_t useLines = 0, cutAt = 0;
         if (!fasta) {                                                                // the last line feed that closes a fourth line
             useLines = nFeeds & ~3u;
-            if (useLines) HIPCHK(hipMemcpyAsync(&cutAt, lineStart + useLines, 4, hipMemcpyDeviceToHost, p->stream));
+            if (useLines && (rc = fetch_async(p->stream, cutAt, lineStart + useLines))) return rc;
             HIPCHK(hipStreamSynchronize(p->stream));
         } else {                                                                     // the start of the last line that begins with '>'
             unsigned long long *last = status + 1, key = 0;                          // (behind the status word)
             HIPCHK(hipMemsetAsync(last, 0, 8, p->stream));
             prs_last_header_kernel<<<blocks_for(nLines, 256), 256, 0, p->stream>>>(p->text.as<uint8_t>(), lineStart, nLines, (uint32_t)nBytes, last);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(&key, last, 8, hipMemcpyDeviceToHost, p->stream));
-            HIPCHK(hipStreamSynchronize(p->stream));
+            if ((rc = fetch(p->stream, key, last))) return rc;
             useLines = (uint32_t)(key >> 32); cutAt = (uint32_t)key;
         }
         if (useLines == 0 || cutAt == 0) return KASA_OK;                             // no whole record yet: everything is carried
@@ -420,15 +401,13 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
     // ---- classify
     prs_classify_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(p->text.as<uint8_t>(), lineStart, nLines, fasta, p->longSeq, k1, k2, status);
     HIPCHK(hipGetLastError());
-    if ((rc = scan64(p, k1, (size_t)nLines + 1)) || (rc = scan64(p, k2, (size_t)nLines + 1))) return rc;
+    if ((rc = dev_exclusive_scan(p->scanTmp, p->stream, k1, k1, (uint64_t)0, (size_t)nLines + 1, rocprim::plus<uint64_t>())) ||
+        (rc = dev_exclusive_scan(p->scanTmp, p->stream, k2, k2, (uint64_t)0, (size_t)nLines + 1, rocprim::plus<uint64_t>()))) return rc;
     prs_index_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(lineStart, k1, k2, nLines, p->hdrLine.as<uint32_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>());
     HIPCHK(hipGetLastError());
     uint64_t tot[2] = {0, 0};
     unsigned long long st = ~0ull;
-    HIPCHK(hipMemcpyAsync(&tot[0], k1 + nLines, 8, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipMemcpyAsync(&tot[1], k2 + nLines, 8, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipMemcpyAsync(&st, status, 8, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
+    if ((rc = fetch_async(p->stream, tot[0], k1 + nLines)) || (rc = fetch_async(p->stream, tot[1], k2 + nLines)) || (rc = fetch(p->stream, st, status))) return rc;
     if (st != ~0ull) {                                                             // (the text went up all the same: it counts)
         float up = 0.0f;
         if (!cut && hipEventElapsedTime(&up, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += up;
@@ -461,8 +440,7 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(p->ev[2], p->stream));
-    HIPCHK(hipMemcpyAsync(&st, status, 8, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
+    if ((rc = fetch(p->stream, st, status))) return rc;
     float ms = 0.0f;
     if (!cut && hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += ms;       // (a span's upload and inflate are counted where they happen)
     if (hipEventElapsedTime(&ms, cut ? p->evz[1] : p->ev[1], p->ev[2]) == hipSuccess) p->msParse += ms;
@@ -515,7 +493,7 @@ static int append_bgzf_impl(kasa_parser *p, const uint8_t *span, uint64_t nBytes
     HIPCHK(hipMemsetAsync(text + total, 0, padded - total, p->stream));
     HIPCHK(hipEventRecord(p->evz[1], p->stream));
     unsigned long long st = ~0ull;
-    if (!tab.empty() && nText) HIPCHK(hipMemcpyAsync(&st, p->status.p, 8, hipMemcpyDeviceToHost, p->stream));
+    if (!tab.empty() && nText && (rc = fetch_async(p->stream, st, p->status.as<unsigned long long>()))) return rc;
     HIPCHK(hipStreamSynchronize(p->stream));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, p->ev[0], p->evz[0]) == hipSuccess) p->msUpload += ms;
@@ -545,7 +523,7 @@ static int append_bgzf_impl(kasa_parser *p, const uint8_t *span, uint64_t nBytes
     return KASA_OK;
 }
 
-static int pool_ends(kasa_parser *p, uint64_t r0, uint64_t n, uint64_t e[4])
+static int pool_ends(kasa_parser *p, uint64_t r0, uint64_t n, uint64_t (&e)[4])
 {
     const PoolArrays &a = p->arrays[p->cur];
     int rc = p->status.reserve(64);
@@ -553,9 +531,7 @@ static int pool_ends(kasa_parser *p, uint64_t r0, uint64_t n, uint64_t e[4])
     uint64_t *d = p->status.as<uint64_t>() + 2;                                   // (behind the status word)
     prs_ends_kernel<<<1, 1, 0, p->stream>>>(a.off.as<int64_t>(), a.nameOff.as<uint64_t>(), r0, n, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e, d, 32, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    return KASA_OK;
+    return fetch(p->stream, e, d);
 }
 
 static int fetch_impl(kasa_parser *p, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases)

@@ -268,9 +268,10 @@ __global__ void esr_row_base_kernel(unsigned long long *__restrict__ stCursor, u
 }
 
 // The reads of A.list (nSlow of them; NULL: all reads) with at least minK k-mers are scored here; what is left for the general
-// kernel comes back in *listOut / *nOut.  counters: the context's misc words (this stage uses [72..79]).
-static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, const uint32_t **listOut, uint32_t *nOut, uint32_t *counters)
+// kernel comes back in *listOut / *nOut.  Its counters: CtxCounters::replay.
+static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, const uint32_t **listOut, uint32_t *nOut)
 {
+    ReplayCounters *ctr = &c->ctr()->replay;
     int rc;
     const uint32_t nReads = (uint32_t)c->nReads;
     const int nK = c->nK;
@@ -285,33 +286,25 @@ static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, c
         esr_iota_kernel<<<blocks_for(nReads, 256), 256, 0, c->stream>>>(c->esrIota.as<uint32_t>(), nReads);
         list = c->esrIota.as<uint32_t>();
     }
-    uint32_t *cnt2 = counters + 72;
-    HIPCHK(hipMemsetAsync(cnt2, 0, 8, c->stream));
-    esr_split_kernel<<<blocks_for(nSlow, 256), 256, 0, c->stream>>>(list, nSlow, A.kmerOff, minK, c->esrLong.as<uint32_t>(), c->esrShort.as<uint32_t>(), cnt2);
+    HIPCHK(hipMemsetAsync(ctr->split, 0, sizeof(ctr->split), c->stream));
+    esr_split_kernel<<<blocks_for(nSlow, 256), 256, 0, c->stream>>>(list, nSlow, A.kmerOff, minK, c->esrLong.as<uint32_t>(), c->esrShort.as<uint32_t>(), ctr->split);
     uint32_t h2[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h2, cnt2, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = fetch(c->stream, h2, ctr->split))) return rc;
     uint32_t nLong = h2[0], nShort = h2[1];
     if (nLong == 0) return KASA_OK;
     const uint32_t *longList = c->esrLong.as<uint32_t>();
     // queries of the long reads (running sum), events of every query (running sum)
     if ((rc = c->esrQOff.reserve(((size_t)nLong + 1) * 8 + 64)) || (rc = c->esrReadEv.reserve(((size_t)nLong + 1) * 8 + 64))) return rc;
     list_counts_kernel<<<blocks_for((uint64_t)nLong + 1, 256), 256, 0, c->stream>>>(longList, nLong, A.kmerOff, c->esrQOff.as<uint64_t>());
-    size_t tmpBytes = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, c->esrQOff.as<uint64_t>(), c->esrQOff.as<uint64_t>(), (uint64_t)0, (size_t)nLong + 1, rocprim::plus<uint64_t>(), c->stream));
-    if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-    HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, c->esrQOff.as<uint64_t>(), c->esrQOff.as<uint64_t>(), (uint64_t)0, (size_t)nLong + 1, rocprim::plus<uint64_t>(), c->stream));
+    if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, c->esrQOff.as<uint64_t>(), c->esrQOff.as<uint64_t>(), (uint64_t)0, (size_t)nLong + 1, rocprim::plus<uint64_t>()))) return rc;
     uint64_t nq = 0;
-    HIPCHK(hipMemcpyAsync(&nq, c->esrQOff.as<uint64_t>() + nLong, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if ((rc = fetch(c->stream, nq, c->esrQOff.as<uint64_t>() + nLong))) return rc;
     if ((rc = c->esrEvCnt.reserve((nq + 1) * 4 + 64)) || (rc = c->esrEvOff.reserve((nq + 1) * 8 + 64))) return rc;
     HIPCHK(hipMemsetAsync(c->esrEvCnt.as<uint32_t>() + nq, 0, 4, c->stream));
     if (c->recWords() == 8) esr_count_kernel<8><<<std::min<unsigned>(blocks_for(nq, 256), 256u * 64u), 256, 0, c->stream>>>(A, longList, nLong, c->esrQOff.as<uint64_t>(), nq, c->esrEvCnt.as<uint32_t>());
     else esr_count_kernel<16><<<std::min<unsigned>(blocks_for(nq, 256), 256u * 64u), 256, 0, c->stream>>>(A, longList, nLong, c->esrQOff.as<uint64_t>(), nq, c->esrEvCnt.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, c->esrEvCnt.as<uint32_t>(), c->esrEvOff.as<uint64_t>(), (uint64_t)0, (size_t)nq + 1, rocprim::plus<uint64_t>(), c->stream));
-    if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-    HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, c->esrEvCnt.as<uint32_t>(), c->esrEvOff.as<uint64_t>(), (uint64_t)0, (size_t)nq + 1, rocprim::plus<uint64_t>(), c->stream));
+    if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, c->esrEvCnt.as<uint32_t>(), c->esrEvOff.as<uint64_t>(), (uint64_t)0, (size_t)nq + 1, rocprim::plus<uint64_t>()))) return rc;
     esr_read_events_kernel<<<blocks_for((uint64_t)nLong + 1, 256), 256, 0, c->stream>>>(c->esrQOff.as<uint64_t>(), nLong, c->esrEvOff.as<uint64_t>(), c->esrReadEv.as<uint64_t>());
     std::vector<uint64_t> readEv((size_t)nLong + 1), qOffH((size_t)nLong + 1);
     HIPCHK(hipMemcpyAsync(readEv.data(), c->esrReadEv.p, ((size_t)nLong + 1) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -329,8 +322,8 @@ static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, c
     const uint64_t capEnv = getenv("KASA_ESR_ROUND_EVENTS") ? strtoull(getenv("KASA_ESR_ROUND_EVENTS"), nullptr, 10) : 0;   // (tests: several rounds on small inputs)
     if (capEnv) budget = std::min<uint64_t>(budget, capEnv);
     const uint32_t nTiles = (uint32_t)((c->nQ + TILE - 1) / TILE);
-    unsigned long long *rowBase = reinterpret_cast<unsigned long long *>(counters + 74);
-    uint32_t *nBigDev = counters + 76;
+    unsigned long long *rowBase = &ctr->rowBase;
+    uint32_t *nBigDev = &ctr->bigChains;
     std::vector<uint32_t> back;                                            // long reads that do not fit a round: the general kernel's after all
     uint32_t w0 = 0;
     while (w0 < nLong) {
@@ -351,9 +344,8 @@ static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, c
             int rb = 0;
             while ((1u << rb) < w1 - w0) ++rb;
             const unsigned endBit = (unsigned)(37 + taxBits + rb);
-            HIPCHK(rocprim::radix_sort_pairs(nullptr, tmpBytes, c->esrKeyA.as<uint64_t>(), c->esrKeyB.as<uint64_t>(), c->esrValA.as<uint32_t>(), c->esrValB.as<uint32_t>(), (size_t)E, 0u, endBit, c->stream));   // (the addends travel as 32-bit words: the query sort's fallback is the same instantiation of the library's sort)
-            if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-            HIPCHK(rocprim::radix_sort_pairs(c->sortTmp.p, tmpBytes, c->esrKeyA.as<uint64_t>(), c->esrKeyB.as<uint64_t>(), c->esrValA.as<uint32_t>(), c->esrValB.as<uint32_t>(), (size_t)E, 0u, endBit, c->stream));   // (the addends travel as 32-bit words: the query sort's fallback is the same instantiation of the library's sort)
+            // (the addends travel as 32-bit words: the query sort's fallback is the same instantiation of the library's sort)
+            if ((rc = dev_sort_pairs(c->sortTmp, c->stream, c->esrKeyA.as<uint64_t>(), c->esrKeyB.as<uint64_t>(), c->esrValA.as<uint32_t>(), c->esrValB.as<uint32_t>(), (size_t)E, 0u, endBit))) return rc;
             const uint32_t n = (uint32_t)E;
             esr_addend_kernel<<<blocks_for(n, 256), 256, 0, c->stream>>>(c->esrKeyB.as<uint64_t>(), c->esrValB.as<uint32_t>(), n, taxBits, A, A.addProfile);
             HIPCHK(hipGetLastError());
@@ -361,21 +353,16 @@ static int esr_stage(kasa_ctx *c, ScoreArgs &A, uint32_t nSlow, uint32_t minK, c
             // chains: heads -> ranks (a running sum, in the dead key buffer) -> starts
             uint32_t *head = c->esrKeyA.as<uint32_t>(), *headRank = head + ((size_t)n + 16);
             esr_heads_kernel<<<blocks_for(n, 256), 256, 0, c->stream>>>(c->esrKeyB.as<uint64_t>(), n, head);
-            HIPCHK(rocprim::exclusive_scan(nullptr, tmpBytes, head, headRank, 0u, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
-            if ((rc = c->sortTmp.reserve(tmpBytes))) return rc;
-            HIPCHK(rocprim::exclusive_scan(c->sortTmp.p, tmpBytes, head, headRank, 0u, (size_t)n, rocprim::plus<uint32_t>(), c->stream));
+            if ((rc = dev_exclusive_scan(c->sortTmp, c->stream, head, headRank, 0u, (size_t)n, rocprim::plus<uint32_t>()))) return rc;
             uint32_t lastRank = 0, lastHead = 0;
-            HIPCHK(hipMemcpyAsync(&lastRank, headRank + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(&lastHead, head + (n - 1), 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
+            if ((rc = fetch_async(c->stream, lastRank, headRank + (n - 1))) || (rc = fetch(c->stream, lastHead, head + (n - 1)))) return rc;
             const uint32_t nChains = lastRank + lastHead;
             if ((rc = c->esrChain.reserve(((size_t)nChains + 1) * 4 + 64)) || (rc = c->esrChainScore.reserve((size_t)nChains * 4 + 64)) || (rc = c->esrBig.reserve((size_t)nChains * 4 + 64))) return rc;
             esr_starts_kernel<<<blocks_for(n, 256), 256, 0, c->stream>>>(c->esrKeyB.as<uint64_t>(), n, headRank, c->esrChain.as<uint32_t>(), nChains);
-            HIPCHK(hipMemsetAsync(nBigDev, 0, 4, c->stream));
+            HIPCHK(hipMemsetAsync(nBigDev, 0, sizeof(*nBigDev), c->stream));
             esr_big_list_kernel<<<blocks_for(nChains, 256), 256, 0, c->stream>>>(c->esrChain.as<uint32_t>(), nChains, c->esrBig.as<uint32_t>(), nBigDev);
             uint32_t nBig = 0;
-            HIPCHK(hipMemcpyAsync(&nBig, nBigDev, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
+            if ((rc = fetch(c->stream, nBig, nBigDev))) return rc;
             esr_chain_small_kernel<<<blocks_for(nChains, 256), 256, 0, c->stream>>>(c->esrValB.as<float>(), c->esrChain.as<uint32_t>(), nChains, c->esrChainScore.as<float>());
             if (nBig) esr_chain_big_kernel<<<std::min<uint32_t>(nBig, 256u * 16u), 64, 0, c->stream>>>(c->esrValB.as<float>(), c->esrChain.as<uint32_t>(), nChains, c->esrBig.as<uint32_t>(), nBig, c->esrChainScore.as<float>());
             esr_row_base_kernel<<<blocks_for(w1 - w0, 256), 256, 0, c->stream>>>(A.stCursor, nChains, rowBase, longList, w0, w1, A.rowPos, A.rowLen);
