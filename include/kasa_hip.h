@@ -720,6 +720,26 @@ int kasa_bgzf_parse_append(kasa_parser *p, const void *members, uint64_t nBytes,
                            uint64_t *nTextBytes, uint64_t *carryBytes);
 int kasa_bgzf_parse_status(kasa_parser *p, int *code, uint64_t *member);
 int kasa_bgzf_parse_ms(kasa_parser *p, double *inflateMs);
+/* Paired-end input (-1 <file> -2 <file>): TWO pools on one device, file 1 parsed into `first`, file 2 into `second`; pooled
+ * read r of the one and pooled read r of the other are the mates of pair r.  The pools need not hold the same number of
+ * reads: the one that ran ahead keeps its surplus.  Pairs come out in the form kasa_batch_upload_segments takes:
+ *   bases    mate1(0) mate2(0) mate1(1) mate2(1) ..., untouched
+ *   off      [2 n + 1] over the sequences (sequence s belongs to read s >> 1)
+ *   names    name1(r) name2(r) back to back (each ends in its one space), with nameOff[n + 1]
+ *   lengths  lengths1[r] + lengths2[r]
+ * made on the device from the pools' running offsets in closed form (no scan) and ONE pass over the letters.
+ *   kasa_pair_take   the first nPairs reads of both pools become ctx's batch of nPairs reads in 2 nPairs sequences and leave
+ *                    the pools.  The letters are gathered straight into the context's own buffer (the pools' memory is
+ *                    reused by their next append) and the context goes on as kasa_batch_upload_segments does.  Read-backs:
+ *                    32 bytes per pool for the ends, the 8-byte k-mer count.  The call returns with the stream idle.  Both
+ *                    heads advance together, or -- when the call fails -- neither.  nPairs = 0 gives an empty batch.
+ *                    KASA_E_ARG, pools untouched: a pool holds fewer than nPairs reads, first == second, the pools or the
+ *                    context lie on different devices, a pointer is NULL.
+ *   kasa_pair_fetch  pairs [firstPair, firstPair + nPairs) in that form to host memory; any output pointer may be NULL; off
+ *                    and nameOff are rebased to the first pair.  The pools stay as they are. */
+int kasa_pair_take(kasa_parser *first, kasa_parser *second, kasa_ctx *ctx, uint64_t nPairs);
+int kasa_pair_fetch(kasa_parser *first, kasa_parser *second, uint64_t firstPair, uint64_t nPairs, uint32_t *lengths, uint64_t *nameOff, char *names,
+                    int64_t *off, uint8_t *bases);
 void kasa_parse_destroy(kasa_parser *p);
 
 #ifdef __cplusplus

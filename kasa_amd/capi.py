@@ -39,6 +39,7 @@ EXPORTS = [
     "kasa_encode_group_reads",
     "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
+    "kasa_pair_take", "kasa_pair_fetch",
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate",
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
     "kasa_ctx_row_classes", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
@@ -199,6 +200,8 @@ def lib():
         L.kasa_parse_tile_bytes.argtypes = []
         L.kasa_parse_stage_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_parse_destroy.argtypes = [C.c_void_p]
+        L.kasa_pair_take.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.kasa_pair_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
         L.kasa_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_inflate_status_text.argtypes = [C.c_int]
         L.kasa_inflate_status_text.restype = C.c_char_p
@@ -713,6 +716,35 @@ class Parser:
             self.close()
         except Exception:
             pass
+
+
+def _pool_handle(p):
+    return p.h if p is not None else None
+
+
+def pair_take(first: Parser, second: Parser, ctx: "Context", n: int):
+    """The first n reads of both pools become ctx's batch of n reads in 2n sequences, mate 1 and mate 2 of every pair in
+    turn (kasa_pair_take), and leave the pools."""
+    _check(lib().kasa_pair_take(_pool_handle(first), _pool_handle(second), ctx.h if ctx is not None else None, C.c_uint64(n)))
+    ctx.n_reads = int(n)
+
+
+def pair_fetch(first: Parser, second: Parser, first_pair: int = 0, n: int = None):
+    """Pairs [first_pair, first_pair + n) of two pools in the interleaved form (kasa_pair_fetch): (lengths u32[n], name_off
+    u64[n+1], names u8[...], off i64[2n+1], bases u8[...]); the offsets are rebased to `first_pair`.  n None: all pairs the
+    two pools hold."""
+    L = lib()
+    if n is None:
+        n = min(first.sizes()[0], second.sizes()[0]) - first_pair
+    lengths = np.zeros(n, dtype=np.uint32)
+    name_off = np.zeros(n + 1, dtype=np.uint64)
+    off = np.zeros(2 * n + 1, dtype=np.int64)
+    h1, h2 = _pool_handle(first), _pool_handle(second)
+    _check(L.kasa_pair_fetch(h1, h2, C.c_uint64(first_pair), C.c_uint64(n), _p(lengths), _p(name_off), None, _p(off), None))
+    names = np.zeros(int(name_off[-1]), dtype=np.uint8)
+    bases = np.zeros(int(off[-1]), dtype=np.uint8)
+    _check(L.kasa_pair_fetch(h1, h2, C.c_uint64(first_pair), C.c_uint64(n), None, None, _p(names), None, _p(bases)))
+    return lengths, name_off, names, off, bases
 
 
 class Context:

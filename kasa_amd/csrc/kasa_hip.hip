@@ -1019,29 +1019,48 @@ __global__ void upload_max_kernel(const uint64_t *__restrict__ readCnt, int64_t 
 // k-mers before every sequence and read) are made on the device -- the host loop over ten million reads took 0.1 s.
 // resident: `bases` and `offsets` both lie in device memory and stay the caller's; the bases are read in place -- or, ownCopy
 // (kasa_parse_take: the pool's memory is reused by its next append), copied into the context's buffer like a host's.
+// It comes in two halves: upload_impl brings the caller's arrays into the context's buffers, upload_tail works on what lies
+// there (kasa_pair_take writes those buffers with kernels of its own and shares the tail).
+static int upload_tail(kasa_ctx *c, int64_t nSeq, const uint32_t *seqRead, int64_t nReads, uint64_t nBases);
+
+// the batch a context held is forgotten: what every upload starts with
+static int upload_reset(kasa_ctx *c, int64_t nSeq, int64_t nReads)
+{
+    if ((uint64_t)nReads >= 0xFFFFFFF0ull || (uint64_t)nSeq >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_upload: more than 2^32 reads in one batch");
+    HIPCHK(hipSetDevice(c->ix->device));
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
+    c->recOut = nullptr; c->recSorted = false;
+    return KASA_OK;
+}
+
+// the tables of a batch of nSeq sequences in nReads reads (the bases' own buffer is the caller's business)
+static int upload_reserve(kasa_ctx *c, int64_t nSeq, int64_t nReads)
+{
+    int rc;
+    if ((rc = c->baseOff.reserve(((size_t)nSeq + 1) * 8)) || (rc = c->kmerOff.reserve(((size_t)nReads + 1) * 8)) || (rc = c->seqOff.reserve(((size_t)nSeq + 1) * 8)) ||
+        (rc = c->seqRead.reserve((size_t)nSeq * 4 + 64)) || (rc = c->rawOff.reserve(((size_t)nSeq + 1) * 8)))
+        return rc;
+    return KASA_OK;
+}
+
+// The front: the host's (or the caller's device) arrays come into the context's buffers; upload_tail does the rest.
 static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets, int64_t nSeq, const uint32_t *seqRead, int64_t nReads, bool resident = false,
                        bool ownCopy = false)
 {
     if (!c) return fail(KASA_E_ARG, "ctx is NULL");
     if (nSeq < 0 || nReads < 0 || (nSeq > 0 && (!offsets || !bases))) return fail(KASA_E_ARG, "kasa_batch_upload: bad arguments");
-    if ((uint64_t)nReads >= 0xFFFFFFF0ull || (uint64_t)nSeq >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_upload: more than 2^32 reads in one batch");
-    HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
-    c->recOut = nullptr; c->recSorted = false;
+    int rc;
+    if ((rc = upload_reset(c, nSeq, nReads))) return rc;
     const int64_t zero = 0;
     if (nSeq == 0) { offsets = &zero; resident = false; }
     int64_t ends[2] = {0, 0};                                               // offsets[0], offsets[nSeq]
-    int rc;
     if (resident) {
         if ((rc = fetch_async(c->stream, ends[0], offsets)) || (rc = fetch(c->stream, ends[1], offsets + nSeq))) return rc;
     } else { ends[0] = offsets[0]; ends[1] = offsets[nSeq]; }
     if (ends[1] < ends[0]) return fail(KASA_E_ARG, "kasa_batch_upload: offsets are not ascending");
     const uint64_t nBases = (uint64_t)(ends[1] - ends[0]);
     const bool inPlace = resident && !ownCopy;
-    if ((rc = inPlace ? KASA_OK : c->bases.reserve(nBases + 64)) || (rc = c->baseOff.reserve(((size_t)nSeq + 1) * 8)) ||
-        (rc = c->kmerOff.reserve(((size_t)nReads + 1) * 8)) || (rc = c->seqOff.reserve(((size_t)nSeq + 1) * 8)) ||
-        (rc = c->seqRead.reserve((size_t)nSeq * 4 + 64)) || (rc = c->rawOff.reserve(((size_t)nSeq + 1) * 8)))
-        return rc;
+    if ((rc = inPlace ? KASA_OK : c->bases.reserve(nBases + 64)) || (rc = upload_reserve(c, nSeq, nReads))) return rc;
     if (inPlace) c->basesPtr = bases + ends[0];
     else {
         if (nBases) HIPCHK(hipMemcpyAsync(c->bases.p, bases + ends[0], nBases, hipMemcpyDefault, c->stream));   // `bases` may live in device memory (a host that keeps its reads in HBM)
@@ -1050,14 +1069,23 @@ static int upload_impl(kasa_ctx *c, const uint8_t *bases, const int64_t *offsets
     HIPCHK(hipMemcpyAsync(c->rawOff.p, offsets, ((size_t)nSeq + 1) * 8, resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     c->haveSeqRead = seqRead != nullptr;
     if (seqRead && nSeq) HIPCHK(hipMemcpyAsync(c->seqRead.p, seqRead, (size_t)nSeq * 4, hipMemcpyHostToDevice, c->stream));
-    // device: counts, checks, running sums
+    return upload_tail(c, nSeq, seqRead, nReads, nBases);
+}
+
+// The device half of an upload: c->rawOff holds the nSeq + 1 offsets, c->seqRead the sequences' reads where c->haveSeqRead
+// (seqRead: the host's copy for the error text, or NULL), c->basesPtr the bases; all of it queued on the context's stream or
+// complete.  Counts, checks, running sums, ONE wait for the k-mer count.
+static int upload_tail(kasa_ctx *c, int64_t nSeq, const uint32_t *seqRead, int64_t nReads, uint64_t nBases)
+{
+    int rc;
+    const bool bySeqRead = c->haveSeqRead;
     UploadFlags *flags = &c->ctr()->upload;
     unsigned long long *errAt = c->ctr()->uploadErrAt;                  // first offending sequence per error
     HIPCHK(hipMemsetAsync(flags, 0, sizeof(UploadFlags), c->stream));
     HIPCHK(hipMemsetAsync(errAt, 0xFF, sizeof(CtxCounters::uploadErrAt), c->stream));
     uint64_t *seqCnt = c->seqOff.as<uint64_t>(), *readCnt = c->kmerOff.as<uint64_t>();
     HIPCHK(hipMemsetAsync(readCnt, 0, ((size_t)nReads + 1) * 8, c->stream));
-    upload_geometry_kernel<<<blocks_for((uint64_t)nSeq + 1, 256), 256, 0, c->stream>>>(c->rawOff.as<int64_t>(), nSeq, seqRead ? c->seqRead.as<uint32_t>() : nullptr, nReads,
+    upload_geometry_kernel<<<blocks_for((uint64_t)nSeq + 1, 256), 256, 0, c->stream>>>(c->rawOff.as<int64_t>(), nSeq, bySeqRead ? c->seqRead.as<uint32_t>() : nullptr, nReads,
         c->enc_mode(), c->K(), c->kLow, c->strands(), c->baseOff.as<int64_t>(), seqCnt, readCnt, &flags->errBits, errAt, &flags->maxKmers);
     HIPCHK(hipGetLastError());
     if (nReads) upload_max_kernel<<<std::min<unsigned>(blocks_for((uint64_t)nReads, 256), 2048u), 256, 0, c->stream>>>(readCnt, nReads, &flags->maxKmers);

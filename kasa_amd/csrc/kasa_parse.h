@@ -232,6 +232,88 @@ __global__ void prs_ends_kernel(const int64_t *__restrict__ off, const uint64_t 
     out[0] = (uint64_t)off[r0]; out[1] = (uint64_t)off[r0 + n]; out[2] = nameOff[r0]; out[3] = nameOff[r0 + n];
 }
 
+// ---- pairs: two pools read as ONE run of mate-interleaved entries (kasa_pair_take, kasa_pair_fetch) ----
+// Entry j of 2n is mate j & 1 of pair j >> 1.  With a, b the two pools' running offsets from the first pair on and a0, b0
+// their values there, entry j starts at output byte
+//   D(j) = (a[(j >> 1) + (j & 1)] - a0) + (b[j >> 1] - b0),        D(2n) = total,
+// and its bytes lie at src1 + a[j >> 1] (mate 1) or src2 + b[j >> 1] (mate 2): no scan and no table of entries.  Letters
+// (off) and names (nameOff) are laid out alike, so one gather serves both.  An entry may be EMPTY (a FASTA record without
+// sequence lines): D ascends, but not strictly.
+struct PairOffsets {
+    const uint64_t *a, *b;
+    uint64_t a0, b0;
+    __device__ __forceinline__ uint64_t dst(uint64_t j) const { return (a[(j >> 1) + (j & 1)] - a0) + (b[j >> 1] - b0); }
+    __device__ __forceinline__ uint64_t src(uint64_t j) const { return (j & 1) ? b[j >> 1] : a[j >> 1]; }
+    // largest j in [lo, hi] with D(j) <= o; for o < D(hi + 1) that entry holds byte o: the empty ones before it are stepped over
+    __device__ __forceinline__ uint64_t find(uint64_t lo, uint64_t hi, uint64_t o) const
+    {
+        while (lo < hi) { const uint64_t mid = lo + ((hi - lo + 1) >> 1); if (dst(mid) <= o) lo = mid; else hi = mid - 1; }
+        return lo;
+    }
+};
+
+// one lane per pair and one for the end; every output may be NULL.  lo: the letters' offsets, na: the names'.
+__global__ void pair_layout_kernel(PairOffsets lo, PairOffsets na, const uint32_t *__restrict__ len1, const uint32_t *__restrict__ len2, uint64_t n,
+                                   int64_t *__restrict__ off, uint32_t *__restrict__ seqRead, uint64_t *__restrict__ nameOff, uint32_t *__restrict__ lengths)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > n) return;
+    if (off) {
+        const uint64_t y = lo.b[r] - lo.b0;
+        off[2 * r] = (int64_t)((lo.a[r] - lo.a0) + y);
+        if (r < n) off[2 * r + 1] = (int64_t)((lo.a[r + 1] - lo.a0) + y);
+    }
+    if (nameOff) nameOff[r] = (na.a[r] - na.a0) + (na.b[r] - na.b0);
+    if (r == n) return;
+    if (seqRead) { seqRead[2 * r] = (uint32_t)r; seqRead[2 * r + 1] = (uint32_t)r; }
+    if (lengths) lengths[r] = len1[r] + len2[r];
+}
+
+// The copy, split by OUTPUT bytes like prs_gather_kernel: a wavefront owns TILE_BYTES of `out` (16-byte aligned), finds the
+// entries of its tile by bisection in D, every lane the entry of its 16 bytes.  16 bytes of one entry: five dwords from the
+// 4-byte aligned address below (both sources are padded behind their end, pool_room), shifted into place, one aligned store.
+// Lanes whose 16 bytes cross a junction, and the tail, go byte by byte.  n >= 1, total >= 1; positions are 64-bit.
+__global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *__restrict__ src1, const uint8_t *__restrict__ src2, PairOffsets d, uint64_t n,
+                                                                 uint64_t total, uint8_t *__restrict__ out)
+{
+    const uint64_t tile = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t v0 = tile * TILE_BYTES;
+    if (v0 >= total) return;
+    const uint64_t v1 = v0 + TILE_BYTES < total ? v0 + TILE_BYTES : total;
+    const uint64_t jLo = d.find(0, 2 * n - 1, v0), jHi = d.find(jLo, 2 * n - 1, v1 - 1);
+    for (int s = 0; s < STEPS; ++s) {
+        const uint64_t va = v0 + (uint64_t)s * STEP_BYTES + lane * 16;
+        if (va >= total) continue;
+        const uint64_t vb = va + 16 < total ? va + 16 : total;
+        uint64_t j = d.find(jLo, jHi, va);
+        uint64_t d0 = d.dst(j), d1 = d.dst(j + 1);
+        const uint8_t *sp = ((j & 1) ? src2 : src1) + d.src(j);
+        uint32_t w[4] = {0, 0, 0, 0};
+        const bool whole = vb - va == 16;
+        if (whole && va + 16 <= d1) {
+            const uint8_t *p = sp + (va - d0);
+            const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(p - sh);
+            const uint32_t x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3], x4 = q[4];
+            w[0] = __builtin_amdgcn_alignbyte(x1, x0, sh); w[1] = __builtin_amdgcn_alignbyte(x2, x1, sh);
+            w[2] = __builtin_amdgcn_alignbyte(x3, x2, sh); w[3] = __builtin_amdgcn_alignbyte(x4, x3, sh);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const uint64_t k = va + q;
+                if (k >= vb) continue;
+                while (k >= d1) { ++j; d0 = d1; d1 = d.dst(j + 1); sp = ((j & 1) ? src2 : src1) + d.src(j); }   // (k < total = D(2n): it ends; empty entries fall through)
+                w[q >> 2] |= (uint32_t)sp[k - d0] << (8 * (q & 3));
+            }
+        }
+        if (whole) *reinterpret_cast<uint4 *>(out + va) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+#pragma unroll
+            for (int q = 0; q < 16; ++q) { const uint64_t k = va + q; if (k < vb) out[k] = (uint8_t)(w[q >> 2] >> (8 * (q & 3))); }
+    }
+}
+
 struct PoolArrays { DevBuf bases, off, names, nameOff, lengths; };
 
 }  // namespace kasa_parse_impl
@@ -254,6 +336,8 @@ struct kasa_parser {
     hipEvent_t evz[2] = {nullptr, nullptr};
     int inflateCode = 0; uint64_t inflateMember = 0;
     double msInflate = 0;
+    // kasa_pair_fetch (this pool as the first of the two): the interleaved arrays before they cross to the host
+    DevBuf pairOff, pairNameOff, pairLengths, pairNames, pairBases;
 };
 
 namespace kasa_parse_impl {
@@ -575,6 +659,101 @@ static int take_impl(kasa_parser *p, kasa_ctx *c, uint64_t n)
     return KASA_OK;
 }
 
+// ---- pairs ----
+static int pair_check(const char *who, kasa_parser *p, kasa_parser *q)
+{
+    if (!p || !q) return fail(KASA_E_ARG, "%s: a parser is NULL", who);
+    if (p == q) return fail(KASA_E_ARG, "%s: both mates from one pool", who);
+    if (p->device != q->device) return fail(KASA_E_ARG, "%s: the pools are on devices %d and %d", who, p->device, q->device);
+    return KASA_OK;
+}
+
+// the closed-form offsets of pairs [r1, r1 + n) / [r2, r2 + n) of the two pools, letters and names (e1, e2: pool_ends of those ranges)
+static void pair_offsets(const kasa_parser *p, const kasa_parser *q, uint64_t r1, uint64_t r2, const uint64_t (&e1)[4], const uint64_t (&e2)[4],
+                         PairOffsets &letters, PairOffsets &names)
+{
+    const PoolArrays &a = p->arrays[p->cur], &b = q->arrays[q->cur];
+    letters = PairOffsets{reinterpret_cast<const uint64_t *>(a.off.as<int64_t>()) + r1, reinterpret_cast<const uint64_t *>(b.off.as<int64_t>()) + r2, e1[0], e2[0]};
+    names = PairOffsets{a.nameOff.as<uint64_t>() + r1, b.nameOff.as<uint64_t>() + r2, e1[2], e2[2]};
+}
+
+static int pair_gather(const uint8_t *src1, const uint8_t *src2, const PairOffsets &d, uint64_t n, uint64_t total, uint8_t *out, hipStream_t stream)
+{
+    if (n == 0 || total == 0) return KASA_OK;
+    const uint64_t tiles = (total + TILE_BYTES - 1) / TILE_BYTES;
+    if (tiles / WAVES >= 0x7FFFFFFFull) return fail(KASA_E_LIMIT, "kasa_pair: %llu bytes in one call", (unsigned long long)total);
+    pair_gather_kernel<<<blocks_for(tiles, WAVES), 64 * WAVES, 0, stream>>>(src1, src2, d, n, total, out);
+    HIPCHK(hipGetLastError());
+    return KASA_OK;
+}
+
+static int pair_fetch_impl(kasa_parser *p, kasa_parser *q, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases)
+{
+    int rc = pair_check("kasa_pair_fetch", p, q);
+    if (rc) return rc;
+    const uint64_t pooled = std::min(p->nReads - p->head, q->nReads - q->head);
+    if (first > pooled || n > pooled - first)
+        return fail(KASA_E_ARG, "kasa_pair_fetch: pairs [%llu, +%llu) outside the %llu pooled", (unsigned long long)first, (unsigned long long)n, (unsigned long long)pooled);
+    HIPCHK(hipSetDevice(p->device));
+    uint64_t e1[4] = {0, 0, 0, 0}, e2[4] = {0, 0, 0, 0};
+    if ((rc = pool_ends(p, p->head + first, n, e1)) || (rc = pool_ends(q, q->head + first, n, e2))) return rc;
+    const uint64_t nBases = (e1[1] - e1[0]) + (e2[1] - e2[0]), nNames = (e1[3] - e1[2]) + (e2[3] - e2[2]);
+    const PoolArrays &a = p->arrays[p->cur], &b = q->arrays[q->cur];
+    PairOffsets dl, dn;
+    pair_offsets(p, q, p->head + first, q->head + first, e1, e2, dl, dn);
+    if ((off && (rc = p->pairOff.reserve((2 * n + 1) * 8))) || (nameOff && (rc = p->pairNameOff.reserve((n + 1) * 8))) || (lengths && (rc = p->pairLengths.reserve(n * 4 + 64))) ||
+        (names && (rc = p->pairNames.reserve(nNames + 64))) || (bases && (rc = p->pairBases.reserve(nBases + 64))))
+        return rc;
+    // the second pool's stream is idle (every call on a pool returns so): all of it runs on the first one's
+    if (off || nameOff || lengths) {
+        pair_layout_kernel<<<blocks_for(n + 1, 256), 256, 0, p->stream>>>(dl, dn, a.lengths.as<uint32_t>() + p->head + first, b.lengths.as<uint32_t>() + q->head + first, n,
+            off ? p->pairOff.as<int64_t>() : nullptr, nullptr, nameOff ? p->pairNameOff.as<uint64_t>() : nullptr, lengths ? p->pairLengths.as<uint32_t>() : nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    if ((names && (rc = pair_gather(a.names.as<uint8_t>(), b.names.as<uint8_t>(), dn, n, nNames, p->pairNames.as<uint8_t>(), p->stream))) ||
+        (bases && (rc = pair_gather(a.bases.as<uint8_t>(), b.bases.as<uint8_t>(), dl, n, nBases, p->pairBases.as<uint8_t>(), p->stream))))
+        return rc;
+    if (off) HIPCHK(hipMemcpyAsync(off, p->pairOff.p, (2 * n + 1) * 8, hipMemcpyDeviceToHost, p->stream));
+    if (nameOff) HIPCHK(hipMemcpyAsync(nameOff, p->pairNameOff.p, (n + 1) * 8, hipMemcpyDeviceToHost, p->stream));
+    if (lengths && n) HIPCHK(hipMemcpyAsync(lengths, p->pairLengths.p, n * 4, hipMemcpyDeviceToHost, p->stream));
+    if (names && n && nNames) HIPCHK(hipMemcpyAsync(names, p->pairNames.p, nNames, hipMemcpyDeviceToHost, p->stream));
+    if (bases && n && nBases) HIPCHK(hipMemcpyAsync(bases, p->pairBases.p, nBases, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return KASA_OK;
+}
+
+// The first n reads of both pools become the context's batch of n reads in 2n sequences.  The context's own buffers are
+// written by the two kernels (offsets and read ids; the letters, in their one pass), upload_tail does the rest and returns
+// with the stream idle: the pools' memory is free for the next append.  The heads move only when all of it went well.
+static int pair_take_impl(kasa_parser *p, kasa_parser *q, kasa_ctx *c, uint64_t n)
+{
+    int rc = pair_check("kasa_pair_take", p, q);
+    if (rc) return rc;
+    if (!c) return fail(KASA_E_ARG, "ctx is NULL");
+    if (c->ix->device != p->device) return fail(KASA_E_ARG, "kasa_pair_take: the context is on device %d, the pools on device %d", c->ix->device, p->device);
+    if (n > p->nReads - p->head || n > q->nReads - q->head)
+        return fail(KASA_E_ARG, "kasa_pair_take: %llu pairs asked for, %llu and %llu reads pooled", (unsigned long long)n, (unsigned long long)(p->nReads - p->head),
+                    (unsigned long long)(q->nReads - q->head));
+    HIPCHK(hipSetDevice(p->device));
+    uint64_t e1[4] = {0, 0, 0, 0}, e2[4] = {0, 0, 0, 0};                           // one 32-byte read-back per pool
+    if ((rc = pool_ends(p, p->head, n, e1)) || (rc = pool_ends(q, q->head, n, e2))) return rc;
+    const uint64_t nBases = (e1[1] - e1[0]) + (e2[1] - e2[0]);
+    const int64_t nSeq = (int64_t)(2 * n);
+    if ((rc = upload_reset(c, nSeq, (int64_t)n)) || (rc = c->bases.reserve(nBases + 64)) || (rc = upload_reserve(c, nSeq, (int64_t)n))) return rc;
+    const PoolArrays &a = p->arrays[p->cur], &b = q->arrays[q->cur];
+    PairOffsets dl, dn;
+    pair_offsets(p, q, p->head, q->head, e1, e2, dl, dn);
+    pair_layout_kernel<<<blocks_for(n + 1, 256), 256, 0, c->stream>>>(dl, dn, nullptr, nullptr, n, c->rawOff.as<int64_t>(), c->seqRead.as<uint32_t>(), nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    if ((rc = pair_gather(a.bases.as<uint8_t>(), b.bases.as<uint8_t>(), dl, n, nBases, c->bases.as<uint8_t>(), c->stream))) return rc;
+    c->basesPtr = c->bases.as<uint8_t>();
+    c->haveSeqRead = true;
+    if ((rc = upload_tail(c, nSeq, nullptr, (int64_t)n, nBases))) return rc;
+    p->head += n; p->headBase = e1[1]; p->headName = e1[3];
+    q->head += n; q->headBase = e2[1]; q->headName = e2[3];
+    return KASA_OK;
+}
+
 }  // namespace kasa_parse_impl
 
 extern "C" int kasa_parse_tile_bytes(void) { return kasa_parse_impl::TILE_BYTES; }
@@ -685,6 +864,14 @@ extern "C" int kasa_parse_fetch(kasa_parser *p, uint64_t first, uint64_t n, uint
 }
 
 extern "C" int kasa_parse_take(kasa_parser *p, kasa_ctx *ctx, uint64_t nReads) { KASA_GUARDED(kasa_parse_impl::take_impl(p, ctx, nReads)) }
+
+extern "C" int kasa_pair_take(kasa_parser *first, kasa_parser *second, kasa_ctx *ctx, uint64_t nPairs) { KASA_GUARDED(kasa_parse_impl::pair_take_impl(first, second, ctx, nPairs)) }
+
+extern "C" int kasa_pair_fetch(kasa_parser *first, kasa_parser *second, uint64_t firstPair, uint64_t nPairs, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off,
+                               uint8_t *bases)
+{
+    KASA_GUARDED(kasa_parse_impl::pair_fetch_impl(first, second, firstPair, nPairs, lengths, nameOff, names, off, bases))
+}
 
 extern "C" int kasa_parse_stage_ms(kasa_parser *p, double *uploadMs, double *parseMs)
 {

@@ -742,6 +742,7 @@ struct Params {
     bool bgzf = false;                             // --bgzf: the per-read file is a BGZF stream (blocked gzip), compressed where its text is made
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
     bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
+    bool devicePairs = false;                      // --device-pairs (implies --device-parse): paired-end input is parsed into two pools and paired on the device (kasa_pair_*)
 };
 
 struct IndexFiles {                               // what Compare::ReadIndex loads (Compare.hpp:49-363), shared by every worker
@@ -1097,10 +1098,11 @@ struct SplitCarry;
 // batcher still holds as `pending` behind them.
 struct DevicePool {
     kasa_parser *ps = nullptr;
+    kasa_parser *ps2 = nullptr;                   // --device-pairs: the pool of the second file; `outstanding` counts pairs, which kasa_pair_take takes from both
     std::mutex mu;
     uint64_t outstanding = 0;
     PcieBuf<char> stage;                          // KASA_PARSE_STAGE=pinned: the chunk's text copied to page-locked memory first (default: straight from the reader's buffer, which measured faster)
-    ~DevicePool() { kasa_parse_destroy(ps); }
+    ~DevicePool() { kasa_parse_destroy(ps); kasa_parse_destroy(ps2); }
 };
 struct Batch {
     uint64_t id = 0, firstRead = 0;
@@ -1173,6 +1175,22 @@ static Pieces readerPieces(const ReadSet::LongRec &lr, bool fasta, bool protein,
     return pc;
 }
 
+// paired-end (Read.hpp:834-1049): mate r of both files forms read r; the two sequences stay separate (no k-mer spans the
+// junction) but score into one row; specifier = both names, length = the sum.  The pairs go behind those `out` holds.
+static void appendPairs(ReadSet &out, const ReadSet &r1, const ReadSet &r2)
+{
+    if (r2.size() != r1.size()) throw std::runtime_error("The paired-end files hold different numbers of reads");
+    for (size_t r = 0; r < r1.size(); ++r) {
+        for (const ReadSet *x : {&r1, &r2}) {
+            out.bases.append(x->bases.data() + x->off[r], (size_t)(x->off[r + 1] - x->off[r]));
+            out.off.push_back((int64_t)out.bases.size());
+            out.nameBlob.append(x->nameBlob.data() + x->nameOff[r], x->nameLen(r));
+        }
+        out.nameOff.push_back(out.nameBlob.size());
+        out.lengths.push_back(r1.lengths[r] + r2.lengths[r]);
+    }
+}
+
 // Cuts the reads of one input into batches.  With per-read output the batches are the reference's own: per-read scores
 // are float sums whose order depends on the reads sharing a batch, so the input is cut exactly where `kASA identify -m`
 // cuts it (kasa_refbatch_*: Compare.hpp:2803-2818,3129-3132; Read.hpp:612-630,1147,1165-1195).  A profile-only run
@@ -1182,7 +1200,7 @@ struct Batcher {
     bool wantRows, paired;
     std::unique_ptr<ChunkReader> reader;          // single-end input is streamed
     ReadSet pending; size_t pendPos = 0;          // parsed reads not yet handed out
-    vector<uint32_t> pendSeg;                     // paired-end: the whole (merged) input sits in `pending`
+    std::unique_ptr<ChunkReader> reader2;         // --device-pairs: the second file, streamed like the first (the host path holds both files whole in `pending`)
     uint64_t nextRead = 0, nextId = 0;
     int64_t refBudget = 0; bool useRef = false, firstBatch = true, warned = false;
     uint64_t maxKmersPerBatch;
@@ -1197,27 +1215,22 @@ struct Batcher {
     Batcher(const Params &pp, const IndexFiles &f, bool rows, uint64_t maxKmers, int poolDevice = -1) : p(pp), ixf(f), wantRows(rows), paired(!pp.input2.empty()), maxKmersPerBatch(maxKmers)
     {
         const auto t0 = std::chrono::steady_clock::now();
-        if (poolDevice >= 0 && !paired) {
+        if (poolDevice >= 0) {                     // (paired input comes with a pool only under --device-pairs)
             pool.reset(new DevicePool());
             if (kasa_parse_create(poolDevice, (uint64_t)kLongSequence, &pool->ps)) throwLast();
+            if (paired && kasa_parse_create(poolDevice, (uint64_t)kLongSequence, &pool->ps2)) throwLast();
             devParse = true;
         }
-        if (paired) {
-            // paired-end (Read.hpp:834-1049): mate r of both files forms read r; the two sequences stay separate (no k-mer
-            // spans the junction) but score into one row; specifier = both names, length = the sum
+        if (paired && devParse) {
+            reader.reset(new ChunkReader(p.input, p.deviceInflate));
+            reader2.reset(new ChunkReader(p.input2, p.deviceInflate));
+            if (p.verbose) for (const ChunkReader *cr : {reader.get(), reader2.get()})
+                if (cr->bgzfWhy) std::cout << "OUT: --device-inflate: the host path is used for file " << (cr == reader.get() ? 1 : 2) << " (" << cr->bgzfWhy << ")" << std::endl;
+            refill();
+        } else if (paired) {
             ReadSet r1 = readInput(p.input, p.verbose, p.threads), r2 = readInput(p.input2, false, p.threads);
-            if (r2.size() != r1.size()) throw std::runtime_error("The paired-end files hold different numbers of reads");
             pending.protein = r1.protein;
-            for (size_t r = 0; r < r1.size(); ++r) {
-                for (const ReadSet *x : {&r1, &r2}) {
-                    pending.bases.append(x->bases.data() + x->off[r], (size_t)(x->off[r + 1] - x->off[r]));
-                    pending.off.push_back((int64_t)pending.bases.size());
-                    pendSeg.push_back((uint32_t)r);
-                    pending.nameBlob.append(x->nameBlob.data() + x->nameOff[r], x->nameLen(r));
-                }
-                pending.nameOff.push_back(pending.nameBlob.size());
-                pending.lengths.push_back(r1.lengths[r] + r2.lengths[r]);
-            }
+            appendPairs(pending, r1, r2);
             protein = pending.protein;
         } else {
             reader.reset(new ChunkReader(p.input, devParse && p.deviceInflate));
@@ -1240,6 +1253,7 @@ struct Batcher {
     {
         if (!reader) return;
         ++pendingGen;
+        if (reader2) { refillPairs(); return; }
         if (pendPos > 0 && pendPos == pending.size()) { pending.clear(); pendPos = 0; }
         const char *chunk = nullptr; size_t chunkBytes = 0;
         if (devParse && reader->bgzf) {             // --device-inflate: spans of members until one adds reads, the file ends or the host takes over
@@ -1353,6 +1367,119 @@ struct Batcher {
         pending.nameBlob.resize(n0 + nameBytes);
         if (nameBytes && kasa_parse_fetch(ps, before, added, nullptr, nullptr, pending.nameBlob.data() + n0, nullptr, nullptr)) throwLast();
         return true;
+    }
+    // --- --device-pairs: two files, two pools -------------------------------------------------------------------------
+    // The pool that holds fewer reads gets the next chunk of its file (both when they hold the same), until pairs are
+    // complete in both that `pending` does not know yet: those come through kasa_pair_fetch -- lengths, names and the
+    // offsets of the 2n sequences; the letters stay.  The surplus of the pool that is ahead stays pooled, so the pools
+    // drift apart by one chunk at the most however the mates' lengths differ.
+    uint64_t textParsed2 = 0;
+    void dropHandedOut() { if (pendPos > 0) { ReadSet rest = pending.slice(pendPos, pending.size(), seqPerRead(), p.threads); pending = std::move(rest); pendPos = 0; } }
+    void refillPairs()
+    {
+        if (pendPos > 0 && pendPos == pending.size()) { pending.clear(); pendPos = 0; }
+        for (;;) {
+            uint64_t have[2] = {0, 0};
+            { std::lock_guard<std::mutex> lk(pool->mu); if (kasa_parse_sizes(pool->ps, &have[0], nullptr, nullptr) || kasa_parse_sizes(pool->ps2, &have[1], nullptr, nullptr)) throwLast(); }
+            int appended = 0;
+            for (int w = 0; w < 2; ++w) {
+                if (have[w] > have[w ^ 1]) continue;
+                const int rc = appendMate(w);
+                if (rc < 0) return;                                  // the host parser has taken over: `pending` holds the rest of the input
+                appended += rc;
+            }
+            if (!appended) {                                        // the file(s) whose turn it was have ended
+                if (have[0] != have[1]) throw std::runtime_error("The paired-end files hold different numbers of reads");
+                return;
+            }
+            std::lock_guard<std::mutex> lk(pool->mu);
+            if (kasa_parse_sizes(pool->ps, &have[0], nullptr, nullptr) || kasa_parse_sizes(pool->ps2, &have[1], nullptr, nullptr)) throwLast();
+            const uint64_t known = pool->outstanding + (pending.size() - pendPos), pairs = std::min(have[0], have[1]);
+            if (pairs < known) throw std::runtime_error("--device-pairs: the pools and the pending reads disagree");
+            if (pairs == known) continue;
+            ScopedTimer tm(g_ht.deviceParse);
+            dropHandedOut();
+            const size_t r0 = pending.size(), added = (size_t)(pairs - known);
+            pending.devBases = true; pending.fasta = reader->fasta;
+            const size_t n0 = pending.nameBlob.size(); const int64_t b0 = pending.off[2 * r0];
+            pending.lengths.resize(r0 + added); pending.nameOff.resize(r0 + added + 1); pending.off.resize(2 * (r0 + added) + 1);
+            if (kasa_pair_fetch(pool->ps, pool->ps2, known, added, pending.lengths.data() + r0, pending.nameOff.data() + r0, nullptr, pending.off.data() + 2 * r0, nullptr)) throwLast();
+            const uint64_t nameBytes = pending.nameOff[r0 + added];
+            for (size_t i = 0; i <= added; ++i) pending.nameOff[r0 + i] += n0;
+            for (size_t i = 0; i <= 2 * added; ++i) pending.off[2 * r0 + i] += b0;
+            pending.nameBlob.resize(n0 + nameBytes);
+            if (nameBytes && kasa_pair_fetch(pool->ps, pool->ps2, known, added, nullptr, nullptr, pending.nameBlob.data() + n0, nullptr, nullptr)) throwLast();
+            return;
+        }
+    }
+    // the next chunk (BGZF under --device-inflate: span of members) of file w + 1 goes to its pool.  1: done, 0: the file has
+    // ended, -1: the chunk is not in the form the device takes and the host parser has taken over (pairsToHost)
+    int appendMate(int w)
+    {
+        ChunkReader &cr = w ? *reader2 : *reader;
+        kasa_parser *ps = w ? pool->ps2 : pool->ps;
+        uint64_t &parsedText = w ? textParsed2 : textParsed;
+        const char *chunk = nullptr; size_t chunkBytes = 0; bool final = false;
+        if (cr.bgzf ? !cr.nextSpan(chunk, chunkBytes, final, p.verbose && w == 0) : !cr.next(chunk, chunkBytes, p.verbose && w == 0)) return 0;
+        if (w == 0) protein = pending.protein = cr.protein;          // (the first file's alphabet, as on the host path)
+        uint64_t added = 0, nText = 0, carry = 0, textStart = cr.chunkStart; int parsable = 0;
+        {
+            std::lock_guard<std::mutex> lk(pool->mu);
+            double up0 = 0, ps0 = 0, z0 = 0, up1 = 0, ps1 = 0, z1 = 0;
+            if (kasa_parse_stage_ms(ps, &up0, &ps0) || kasa_bgzf_parse_ms(ps, &z0)) throwLast();
+            if (cr.bgzf) {
+                textStart = parsedText;
+                if (kasa_bgzf_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &carry)) throwLast();
+                if (parsable) parsedText += nText;
+            } else if (kasa_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, &added, &parsable)) throwLast();
+            if (kasa_parse_stage_ms(ps, &up1, &ps1) || kasa_bgzf_parse_ms(ps, &z1)) throwLast();
+            g_ht.uploadText += (up1 - up0) * 1e-3; g_ht.deviceParse += (ps1 - ps0) * 1e-3; g_ht.inflate += (z1 - z0) * 1e-3;
+        }
+        if (parsable) return 1;
+        int code = 0; uint64_t at = 0;
+        (void)kasa_parse_status(ps, &code, &at);
+        if (code == KASA_PARSE_INFLATE) {
+            int zc = 0; uint64_t member = 0;
+            (void)kasa_bgzf_parse_status(ps, &zc, &member);
+            throw std::runtime_error(string(kasa_inflate_status_text(zc)) + " in BGZF member " + std::to_string(cr.membersOut - membersIn(chunk, chunkBytes) + member));
+        }
+        if (p.verbose) std::cout << "OUT: --device-pairs: the host parser takes over from byte " << textStart + at << " of file " << w + 1 << " (" << kasa_parse_status_text(code) << ")" << std::endl;
+        pairsToHost(w, chunk, chunkBytes);
+        return -1;
+    }
+    // Takeover: the pending pairs get their letters, the unpaired surplus of either pool comes back whole, the host parses the
+    // rest of both files behind it (file w + 1 from the chunk the device refused) and pairs it up behind the pending ones.
+    void pairsToHost(int w, const char *chunk, size_t chunkBytes)
+    {
+        ReadSet rest[2];
+        {
+            std::lock_guard<std::mutex> lk(pool->mu);
+            dropHandedOut();
+            const size_t n = pending.size();
+            pending.bases.resize((size_t)pending.off[2 * n]);
+            if (n && kasa_pair_fetch(pool->ps, pool->ps2, pool->outstanding, n, nullptr, nullptr, nullptr, nullptr, pending.bases.data())) throwLast();
+            pending.devBases = false;
+            for (int x = 0; x < 2; ++x) {
+                kasa_parser *ps = x ? pool->ps2 : pool->ps;
+                uint64_t have = 0;
+                if (kasa_parse_sizes(ps, &have, nullptr, nullptr)) throwLast();
+                const uint64_t first = pool->outstanding + n, m = have - first;
+                ReadSet &q = rest[x];
+                q.lengths.resize(m); q.nameOff.resize(m + 1); q.off.resize(m + 1);
+                if (kasa_parse_fetch(ps, first, m, q.lengths.data(), q.nameOff.data(), nullptr, q.off.data(), nullptr)) throwLast();
+                q.nameBlob.resize((size_t)q.nameOff[m]); q.bases.resize((size_t)q.off[m]);
+                if (m && kasa_parse_fetch(ps, first, m, nullptr, nullptr, q.nameBlob.data(), nullptr, q.bases.data())) throwLast();
+            }
+        }
+        for (int x = 0; x < 2; ++x) {
+            ChunkReader &cr = x ? *reader2 : *reader;
+            const char *c = nullptr; size_t cb = 0;
+            if (cr.bgzf) cr.toGzread(x ? textParsed2 : textParsed);   // (the reader is a gzread reader now and stands at the first byte the device has not parsed)
+            else if (x == w) parsePiece(chunk, chunkBytes, cr.fasta, p.threads, 1u << 20, rest[x], parts, cr.chunkStart);
+            while (cr.next(c, cb, false)) parsePiece(c, cb, cr.fasta, p.threads, 1u << 20, rest[x], parts, cr.chunkStart);
+        }
+        appendPairs(pending, rest[0], rest[1]);
+        devParse = false; reader.reset(); reader2.reset();
     }
     // a batch whose letters lie in the pool: its reads are the next ones there that no batch has claimed
     void claim(Batch &b) { if (!b.rs.devBases || b.rs.size() == 0) return; std::lock_guard<std::mutex> lk(pool->mu); b.pool = pool.get(); pool->outstanding += b.rs.size(); }
@@ -1787,7 +1914,7 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
     const uint64_t nr = b.rs.size();
     {
         ScopedTimerMt tm(g_ht.upload, g_ht.mu);
-        if (b.pool) { std::lock_guard<std::mutex> lk(b.pool->mu); if (kasa_parse_take(b.pool->ps, ctx, nr)) throwLast(); b.pool->outstanding -= nr; }
+        if (b.pool) { std::lock_guard<std::mutex> lk(b.pool->mu); if (b.pool->ps2 ? kasa_pair_take(b.pool->ps, b.pool->ps2, ctx, nr) : kasa_parse_take(b.pool->ps, ctx, nr)) throwLast(); b.pool->outstanding -= nr; }
         else if (b.segRead.empty()) { if (kasa_batch_upload(ctx, b.rs.bases.data(), b.rs.off.data(), (int64_t)nr)) throwLast(); }
         else if (kasa_batch_upload_segments(ctx, b.rs.bases.data(), b.rs.off.data(), (int64_t)b.segRead.size(), b.segRead.data(), (int64_t)nr)) throwLast();
     }
@@ -2081,13 +2208,15 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     std::thread textPrep;
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joinTextPrep{textPrep};
     if (!p.rtt.empty() && !p.hostRank && !p.hostText) textPrep = std::thread([&wbs, &p] { try { for (size_t i = 0; i < wbs.size(); ++i) { (void)kasa_thread_device(p.devices[i]); wbs[i].prepareText(); } } catch (...) {} });   // (a fresh thread stands on device 0: the buffers are page-locked for the worker's device)   // (what is missing is made, or fails, when a worker needs it)
-    // --device-parse: single-end input on one device slot; the other combinations keep the host parser and give the same bytes
+    // --device-parse: single-end input on one device slot; the other combinations keep the host parser and give the same bytes.
+    // --device-pairs: the same, and paired-end input goes through two pools (kasa_pair_*)
     int poolDevice = -1;
     if (p.deviceParse) {
-        const char *why = !p.input2.empty() ? "paired-end input" : p.filter ? "--filter writes the reads back from host memory" : p.coherence ? "--coherence"
+        const bool pairs = p.devicePairs && !p.input2.empty();
+        const char *why = (!p.input2.empty() && !pairs) ? "paired-end input" : p.filter ? "--filter writes the reads back from host memory" : p.coherence ? "--coherence"
                           : (nDev > 1 || !ixf.spread.empty()) ? "more than one device slot" : nullptr;
         if (!why) poolDevice = p.devices[(size_t)devSlots[0]];
-        else if (p.verbose) std::cout << "OUT: --device-parse: the host parser is used (" << why << ")" << std::endl;
+        else if (p.verbose) std::cout << "OUT: " << (pairs ? "--device-pairs" : "--device-parse") << ": the host parser is used (" << why << ")" << std::endl;
         if (why && p.deviceInflate && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << why << ")" << std::endl;
     }
     Batcher batcher(p, ixf, wantRows, maxKmersPerBatch, poolDevice);
@@ -2359,6 +2488,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "Gzip") flag("--gzip", val);
         else if (key == "Bgzf") flag("--bgzf", val);                                 // ours: the reference never compresses the per-read file
         else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
+        else if (key == "DevicePairs") flag("--device-pairs", val);
         else if (key == "DeviceInflate") flag("--device-inflate", val);
     }
     vector<string> out = {exe, mode};
@@ -3057,6 +3187,27 @@ static int run(int argc, char **argv)
                        << " cut " << g_ht.cut << " parse " << g_ht.parse << " merge " << g_ht.merge << "\n";
         return 0;
     }
+    if (argc >= 5 && (a[1] == "pair-dump" || a[1] == "pair-dump-device")) {   // test taps: what the host merge / the two device pools make of two files of mates
+        Params pp;
+        pp.input = a[2]; pp.input2 = a[3]; pp.threads = (unsigned)std::stoul(a[4]);
+        const bool onDevice = a[1] == "pair-dump-device";
+        pp.devicePairs = pp.deviceParse = onDevice;
+        IndexFiles none;
+        Batcher bt(pp, none, false, ~0ull, onDevice ? 0 : -1);
+        for (;;) { const size_t before = bt.pending.size(); bt.refill(); if (bt.pending.size() == before) break; }   // (the host path holds everything at once)
+        ReadSet &rs = bt.pending;
+        if (rs.devBases) {
+            rs.bases.resize((size_t)rs.off[2 * rs.size()]);
+            if (rs.size() && kasa_pair_fetch(bt.pool->ps, bt.pool->ps2, 0, rs.size(), nullptr, nullptr, nullptr, nullptr, rs.bases.data())) throwLast();
+        }
+        std::cout << "protein=" << bt.protein << "\n";
+        for (size_t r = 0; r < rs.size(); ++r) {
+            std::cout << rs.name(r) << "\t" << rs.lengths[r];
+            for (size_t q = 0; q < 2; ++q) { std::cout << "\t"; std::cout.write((const char *)rs.bases.data() + rs.off[2 * r + q], rs.off[2 * r + q + 1] - rs.off[2 * r + q]); }
+            std::cout << "\n";
+        }
+        return 0;
+    }
     if (argc >= 4 && a[1] == "bgzf-dump") {                      // test tap: the host's BGZF form of a file + the EOF block (no device involved)
         std::ifstream in(a[2], std::ios::binary);
         if (!in) throw std::runtime_error("Input file not found");
@@ -3182,6 +3333,7 @@ static int run(int argc, char **argv)
         else if (s == "--host-text") p.hostText = true;
         else if (s == "--device-parse") p.deviceParse = true;
         else if (s == "--device-inflate") p.deviceInflate = p.deviceParse = true;
+        else if (s == "--device-pairs") p.devicePairs = p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());

@@ -246,19 +246,8 @@ def parse_reads(path: str) -> ReadBatch:
     return ReadBatch(bases, off, names, np.asarray(lens, dtype=np.uint32), detect_protein(data), layout=layout, fasta=first == b">")
 
 
-def parse_reads_device(path: str, device: int = 0, chunk_bytes: int = 0) -> ReadBatch:
-    """`parse_reads` with the parsing done on the device (capi.Parser) and the reads fetched back: for tests and small hosts.
-    chunk_bytes > 0 hands the text over in chunks of about that size, cut at record starts.  Input the device parser does
-    not take (malformed records, sequences long enough to be read in pieces) raises RuntimeError: `parse_reads` handles it."""
-    from . import capi
-    with _open(path) as f:
-        data = f.read()
-    if not data:
-        return ReadBatch(np.zeros(0, np.uint8), np.zeros(1, np.int64), [], np.zeros(0, np.uint32))
-    first = data[:1]
-    if first not in (b">", b"@"):
-        raise RuntimeError("Input does not start with @ or >.")
-    fasta = first == b">"
+def _record_cuts(data: bytes, fasta: bool, chunk_bytes: int) -> list:
+    """Where a text is cut into chunks of about chunk_bytes (0: one chunk), each starting at a record."""
     cuts = [0]
     if chunk_bytes > 0:
         lines = data.split(b"\n")
@@ -272,19 +261,72 @@ def parse_reads_device(path: str, device: int = 0, chunk_bytes: int = 0) -> Read
             if s - cuts[-1] >= chunk_bytes:
                 cuts.append(s)
     cuts.append(len(data))
+    return cuts
+
+
+def _read_text(path: str):
+    """(text, fasta) of a read file; fasta None: the file is empty."""
+    with _open(path) as f:
+        data = f.read()
+    if not data:
+        return data, None
+    first = data[:1]
+    if first not in (b">", b"@"):
+        raise RuntimeError("Input does not start with @ or >.")
+    return data, first == b">"
+
+
+def _append_chunks(parser, data: bytes, fasta: bool, chunk_bytes: int):
+    cuts = _record_cuts(data, fasta, chunk_bytes)
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        _, ok = parser.append(data[a:b], fasta)
+        if not ok:
+            code, text, at = parser.status()
+            raise RuntimeError(f"not device-parsable: {text} (line at byte {a + at})")
+
+
+def _name_list(names: np.ndarray, name_off: np.ndarray, n: int) -> list:
+    blob = names.tobytes().decode("latin-1")
+    return [blob[int(name_off[r]):int(name_off[r + 1])] for r in range(n)]
+
+
+def parse_reads_device(path: str, device: int = 0, chunk_bytes: int = 0) -> ReadBatch:
+    """`parse_reads` with the parsing done on the device (capi.Parser) and the reads fetched back: for tests and small hosts.
+    chunk_bytes > 0 hands the text over in chunks of about that size, cut at record starts.  Input the device parser does
+    not take (malformed records, sequences long enough to be read in pieces) raises RuntimeError: `parse_reads` handles it."""
+    from . import capi
+    data, fasta = _read_text(path)
+    if fasta is None:
+        return ReadBatch(np.zeros(0, np.uint8), np.zeros(1, np.int64), [], np.zeros(0, np.uint32))
     parser = capi.Parser(device, LONG_SEQUENCE)
     try:
-        for a, b in zip(cuts[:-1], cuts[1:]):
-            _, ok = parser.append(data[a:b], fasta)
-            if not ok:
-                code, text, at = parser.status()
-                raise RuntimeError(f"not device-parsable: {text} (line at byte {a + at})")
+        _append_chunks(parser, data, fasta, chunk_bytes)
         lengths, name_off, names, off, bases = parser.fetch()
     finally:
         parser.close()
-    blob = names.tobytes().decode("latin-1")
-    name_list = [blob[int(name_off[r]):int(name_off[r + 1])] for r in range(lengths.shape[0])]
-    return ReadBatch(bases, off, name_list, lengths, detect_protein(data), fasta=fasta)
+    return ReadBatch(bases, off, _name_list(names, name_off, lengths.shape[0]), lengths, detect_protein(data), fasta=fasta)
+
+
+def parse_pairs_device(path1: str, path2: str, device: int = 0, chunk_bytes: int = 0) -> ReadBatch:
+    """`parse_pairs` with both files parsed into pools on the device and the pairs formed there (capi.pair_fetch): field by
+    field what `parse_pairs` returns.  Raises RuntimeError like `parse_reads_device`, and like `parse_pairs` when the files
+    hold different numbers of reads."""
+    from . import capi
+    (d1, f1), (d2, f2) = _read_text(path1), _read_text(path2)
+    pools = []
+    try:
+        for data, fasta in ((d1, f1), (d2, f2)):
+            pools.append(capi.Parser(device, LONG_SEQUENCE))
+            if fasta is not None:
+                _append_chunks(pools[-1], data, fasta, chunk_bytes)
+        if pools[0].sizes()[0] != pools[1].sizes()[0]:
+            raise RuntimeError("paired-end files hold different numbers of reads")
+        lengths, name_off, names, off, bases = capi.pair_fetch(pools[0], pools[1])
+    finally:
+        for p in pools:
+            p.close()
+    n = lengths.shape[0]
+    return ReadBatch(bases, off, _name_list(names, name_off, n), lengths, detect_protein(d1) if d1 else False, np.repeat(np.arange(n, dtype=np.uint32), 2))
 
 
 def parse_pairs(path1: str, path2: str) -> ReadBatch:
