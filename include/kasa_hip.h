@@ -340,6 +340,18 @@ int kasa_batch_bgzf(kasa_ctx *ctx, uint64_t *nBytes, uint64_t *nBlocks);
 int kasa_batch_bgzf_fetch_range(kasa_ctx *ctx, void *dst, uint64_t offset, uint64_t nBytes);
 /* Test tap (like kasa_text_dtoa): n host bytes through the same kernels; *nOut = stream length, KASA_E_LIMIT when dstCap is too small. */
 int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut);
+/* The code of the members' deflate streams.  KASA_BGZF_DYNAMIC: ONE Huffman table per stream (per kasa_batch_bgzf call), made
+ * on the device from the symbols of a sample of the text's blocks (all of them up to 64, else blocks floor(j nBlocks / 64),
+ * j = 0..63; every symbol keeps a code, of 15 bits at most), and written into every member: BTYPE = 10, HLIT = 29, HDIST = 29,
+ * a complete fixed code-length code without run-length symbols.  The matcher and the tokens are the fixed code's; a member is
+ * still written stored when its coded form is not smaller, and a block of fewer than 2048 bytes keeps the fixed code (a table's
+ * header costs what it saves there).  Bytes are as reproducible as before.
+ *   kasa_ctx_set_bgzf_code    what the context's following kasa_batch_bgzf calls use; a context starts with KASA_BGZF_FIXED.
+ *                             KASA_E_ARG for any other value (the context keeps its code).
+ *   kasa_bgzf_deflate_coded   kasa_bgzf_deflate with a code; kasa_bgzf_deflate is KASA_BGZF_FIXED. */
+enum { KASA_BGZF_FIXED = 0, KASA_BGZF_DYNAMIC = 1 };
+int kasa_ctx_set_bgzf_code(kasa_ctx *ctx, int code);
+int kasa_bgzf_deflate_coded(int device, int code, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut);
 
 /* ---- BGZF in: members inflated on the device (ours: the reference reads .gz through zlib on one thread) -----------------
  * A BGZF file is tens of thousands of deflate streams (RFC 1951: stored, fixed and dynamic blocks, any number per member)

@@ -40,7 +40,7 @@ EXPORTS = [
     "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
     "kasa_pair_take", "kasa_pair_fetch",
-    "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate",
+    "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate", "kasa_ctx_set_bgzf_code", "kasa_bgzf_deflate_coded",
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
     "kasa_ctx_row_classes", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
 ]
@@ -353,14 +353,18 @@ def device_dtoa(values, device: int = 0):
     return [bytes(out[i * 32:(i + 1) * 32]).split(b"\0", 1)[0].decode("ascii") for i in range(v.shape[0])]
 
 
-def bgzf_deflate(device: int, data) -> bytes:
-    """`data` as a BGZF stream made by the DEVICE (kasa_bgzf_deflate, the kernels of kasa_batch_bgzf); no EOF block."""
+BGZF_FIXED, BGZF_DYNAMIC = 0, 1                                   # KASA_BGZF_*: the code of the members' deflate streams
+
+
+def bgzf_deflate(device: int, data, code: int = BGZF_FIXED) -> bytes:
+    """`data` as a BGZF stream made by the DEVICE (kasa_bgzf_deflate_coded, the kernels of kasa_batch_bgzf); no EOF block.
+    code: BGZF_FIXED (RFC 1951's fixed Huffman code) or BGZF_DYNAMIC (one table per stream, counted from a sample of its blocks)."""
     src = np.frombuffer(bytes(data), dtype=np.uint8)
     n = int(src.shape[0])
     cap = n + 31 * ((n + 65279) // 65280)                        # every block stored: 18 + 5 + 8 bytes around it
     out = np.empty(max(1, cap), dtype=np.uint8)
     got = C.c_uint64(0)
-    _check(lib().kasa_bgzf_deflate(C.c_int(device), _p(src) if n else None, C.c_uint64(n), _p(out), C.c_uint64(cap), C.byref(got)))
+    _check(lib().kasa_bgzf_deflate_coded(C.c_int(device), C.c_int(code), _p(src) if n else None, C.c_uint64(n), _p(out), C.c_uint64(cap), C.byref(got)))
     return out[:got.value].tobytes()
 
 
@@ -979,9 +983,13 @@ class Context:
                 _check(lib().kasa_batch_text_fetch_range(self.h, C.c_void_p(buf.ctypes.data + a), C.c_uint64(a), C.c_uint64(k)))
         return buf[:n.value].tobytes(), offs, flags[:self.n_reads]
 
+    def set_bgzf_code(self, code: int):
+        """kasa_ctx_set_bgzf_code: BGZF_FIXED or BGZF_DYNAMIC for the batch_bgzf calls that follow; another value raises (KASA_E_ARG)."""
+        _check(lib().kasa_ctx_set_bgzf_code(self.h, C.c_int(code)))
+
     def batch_bgzf(self, piece: int = 0) -> bytes:
-        """kasa_batch_bgzf + fetch: the text of the last text() as a BGZF stream (no EOF block).  piece > 0: fetched in ranges
-        of that many bytes (kasa_batch_bgzf_fetch_range takes any offset and length)."""
+        """kasa_batch_bgzf + fetch: the text of the last text() as a BGZF stream (no EOF block) in the context's code
+        (set_bgzf_code).  piece > 0: fetched in ranges of that many bytes (kasa_batch_bgzf_fetch_range takes any offset and length)."""
         n, nb = C.c_uint64(0), C.c_uint64(0)
         _check(lib().kasa_batch_bgzf(self.h, C.byref(n), C.byref(nb)))
         buf = np.empty(max(1, n.value), dtype=np.uint8)

@@ -700,6 +700,7 @@ struct kasa_ctx {
     DevBuf txtNames, txtNameOff, txtLen, txtBest, txtBytes, txtOff, txtOut, txtFlags;   // kasa_batch_text
     uint64_t txtTotal = 0; bool txtValid = false;
     DevBuf bgzMembers, bgzSize, bgzOff, bgzOut;                // kasa_batch_bgzf: members at their stride (a chunk of blocks), u64 sizes and offsets, the stream
+    DevBuf bgzCode; int bgzCodeKind = KASA_BGZF_FIXED;         // ... the stream's histogram, table and block header (kasa_bgzf::Code) with KASA_BGZF_DYNAMIC; kasa_ctx_set_bgzf_code
     uint64_t bgzTotal = 0; bool bgzValid = false;              // ... of the text that is valid now (kasa_batch_text forgets it)
     const float *cohScores = nullptr;                          // device: the scores of the last kasa_batch_coherence of this batch
     const void *cohKey = nullptr; bool cohBegun = false;       // kasa_batch_coherence_begin handed this batch's k-mers (cohKey) and depth bytes out; _finish not yet
@@ -778,7 +779,7 @@ struct kasa_ctx {
                 &gwin, &touched, &fbList, &fastScratch, &profKeys, &profSorted, &profSorted2, &rowPos, &rowLen, &rowKey, &rowOff, &st, &cntAllMid, &outTax,
                 &outScore, &cntUnique, &cntTotal, &cntAllHi, &cntAllLo, &rawOff, &cohLen, &cohState, &sortBig, &rankDen, &rankClass, &rankMeta, &rankOut,
                 &rankList, &rankScratch, &scanTmp, &taxText, &taxTextOff, &taxTextIds, &txtNames, &txtNameOff, &txtLen, &txtBest, &txtBytes, &txtOff, &txtOut,
-                &txtFlags, &bgzMembers, &bgzSize, &bgzOff, &bgzOut, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
+                &txtFlags, &bgzMembers, &bgzSize, &bgzOff, &bgzOut, &bgzCode, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
                 &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn, &clsList};
     }
 };
@@ -7916,8 +7917,11 @@ extern "C" int kasa_text_dtoa(int device, const double *values, uint32_t n, char
 // n bytes at `text` (device, 16-byte aligned) -> *total bytes in `out`.  The members of a chunk of blocks are made at their
 // stride, their sizes are scanned behind the chunks before, and they are packed: the scratch is one chunk's whatever the
 // text's length, the stream's buffer is sized for the worst case (every block stored) before the first kernel runs.
+// kind = KASA_BGZF_DYNAMIC: before the chunks count_kernel counts the symbols of a sample of ALL the blocks and build_kernel makes
+// the one table and block header every chunk codes with (`code`, a kasa_bgzf::Code); both are queued on the stream like the rest,
+// nothing of them comes back.  A text of one block below DYN_MIN bytes has no block that would use a table: it goes the fixed way.
 static constexpr uint64_t BGZF_CHUNK_BLOCKS = 4096;              // 256 MiB of members at a time
-static int bgzf_stream(const char *who, const uint8_t *text, uint64_t n, DevBuf &members, DevBuf &size, DevBuf &off, DevBuf &scanTmp, DevBuf &out, hipStream_t stream, uint64_t *total, uint64_t *nBlocks)
+static int bgzf_stream(const char *who, int kind, const uint8_t *text, uint64_t n, DevBuf &members, DevBuf &size, DevBuf &off, DevBuf &scanTmp, DevBuf &out, DevBuf &code, hipStream_t stream, uint64_t *total, uint64_t *nBlocks)
 {
     using namespace kasa_bgzf;
     *total = 0;
@@ -7930,11 +7934,21 @@ static int bgzf_stream(const char *who, const uint8_t *text, uint64_t n, DevBuf 
     if ((rc = members.reserve((size_t)chunk * STRIDE + 64)) || (rc = size.reserve((size_t)(chunk + 1) * 8)) || (rc = off.reserve((size_t)(chunk + 1) * 8)) ||
         (rc = out.reserve((size_t)n + (size_t)nBlk * (HEADER + 5 + TRAILER) + 64)))
         return rc;
+    const bool dynamic = kind == KASA_BGZF_DYNAMIC && n >= DYN_MIN;
+    if (dynamic) {
+        if ((rc = code.reserve(sizeof(Code)))) return rc;
+        HIPCHK(hipMemsetAsync(code.p, 0, sizeof(Code), stream));
+        count_kernel<<<(uint32_t)std::min<uint64_t>(nBlk, SAMPLE_BLOCKS), THREADS, 0, stream>>>(text, n, (uint32_t)nBlk, code.as<Code>());
+        HIPCHK(hipGetLastError());
+        build_kernel<<<1, 320, 0, stream>>>(code.as<Code>());
+        HIPCHK(hipGetLastError());
+    }
     uint64_t at = 0;                                              // bytes of the stream so far
     for (uint64_t b0 = 0; b0 < nBlk; b0 += chunk) {
         const uint64_t cnt = std::min<uint64_t>(chunk, nBlk - b0);
         HIPCHK(hipMemsetAsync(size.p, 0, (size_t)(cnt + 1) * 8, stream));
-        deflate_kernel<<<(uint32_t)cnt, THREADS, 0, stream>>>(text + b0 * BLOCK_IN, n - b0 * BLOCK_IN, members.as<uint8_t>(), size.as<uint64_t>());
+        if (dynamic) deflate_dynamic_kernel<<<(uint32_t)cnt, THREADS, 0, stream>>>(text + b0 * BLOCK_IN, n - b0 * BLOCK_IN, members.as<uint8_t>(), size.as<uint64_t>(), code.as<Code>());
+        else deflate_kernel<<<(uint32_t)cnt, THREADS, 0, stream>>>(text + b0 * BLOCK_IN, n - b0 * BLOCK_IN, members.as<uint8_t>(), size.as<uint64_t>());
         HIPCHK(hipGetLastError());
         // (the first chunk is the longest: it reserves the scan's room for all of them)
         if ((rc = dev_exclusive_scan(scanTmp, stream, size.as<uint64_t>(), off.as<uint64_t>(), at, (size_t)cnt + 1, rocprim::plus<uint64_t>()))) return rc;
@@ -7953,8 +7967,16 @@ extern "C" int kasa_batch_bgzf(kasa_ctx *c, uint64_t *nBytes, uint64_t *nBlocks)
     HIPCHK(hipSetDevice(c->ix->device));
     *nBytes = 0; *nBlocks = 0; c->bgzValid = false; c->bgzTotal = 0;
     int rc;
-    if ((rc = bgzf_stream("kasa_batch_bgzf", c->txtOut.as<uint8_t>(), c->txtTotal, c->bgzMembers, c->bgzSize, c->bgzOff, c->scanTmp, c->bgzOut, c->stream, &c->bgzTotal, nBlocks))) return rc;
+    if ((rc = bgzf_stream("kasa_batch_bgzf", c->bgzCodeKind, c->txtOut.as<uint8_t>(), c->txtTotal, c->bgzMembers, c->bgzSize, c->bgzOff, c->scanTmp, c->bgzOut, c->bgzCode, c->stream, &c->bgzTotal, nBlocks))) return rc;
     c->bgzValid = true; *nBytes = c->bgzTotal;
+    return KASA_OK;
+}
+
+extern "C" int kasa_ctx_set_bgzf_code(kasa_ctx *c, int code)
+{
+    if (!c) return fail(KASA_E_ARG, "kasa_ctx_set_bgzf_code: NULL argument");
+    if (code != KASA_BGZF_FIXED && code != KASA_BGZF_DYNAMIC) return fail(KASA_E_ARG, "kasa_ctx_set_bgzf_code: %d is no code (KASA_BGZF_FIXED, KASA_BGZF_DYNAMIC)", code);
+    c->bgzCodeKind = code;
     return KASA_OK;
 }
 
@@ -7971,23 +7993,29 @@ extern "C" int kasa_batch_bgzf_fetch_range(kasa_ctx *c, void *dst, uint64_t offs
 }
 
 // test tap: n host bytes through the same kernels
-extern "C" int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut)
+extern "C" int kasa_bgzf_deflate_coded(int device, int code, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut)
 {
     if (!nOut || (n && !src)) return fail(KASA_E_ARG, "kasa_bgzf_deflate: NULL argument");
+    if (code != KASA_BGZF_FIXED && code != KASA_BGZF_DYNAMIC) return fail(KASA_E_ARG, "kasa_bgzf_deflate: %d is no code (KASA_BGZF_FIXED, KASA_BGZF_DYNAMIC)", code);
     *nOut = 0;
     HIPCHK(hipSetDevice(device));
     if (n == 0) return KASA_OK;
-    ScopedBuf text, members, size, off, scanTmp, out;
+    ScopedBuf text, members, size, off, scanTmp, out, table;
     int rc;
     if ((rc = text.reserve((size_t)n + 64))) return rc;
     HIPCHK(hipMemcpy(text.p, src, n, hipMemcpyHostToDevice));
     uint64_t total = 0, nBlocks = 0;
-    if ((rc = bgzf_stream("kasa_bgzf_deflate", text.as<uint8_t>(), n, members, size, off, scanTmp, out, nullptr, &total, &nBlocks))) return rc;
+    if ((rc = bgzf_stream("kasa_bgzf_deflate", code, text.as<uint8_t>(), n, members, size, off, scanTmp, out, table, nullptr, &total, &nBlocks))) return rc;
     *nOut = total;
     if (total > dstCap) return fail(KASA_E_LIMIT, "kasa_bgzf_deflate: the stream has %llu bytes, the destination takes %llu", (unsigned long long)total, (unsigned long long)dstCap);
     if (!dst) return fail(KASA_E_ARG, "kasa_bgzf_deflate: NULL destination");
     HIPCHK(hipMemcpy(dst, out.p, total, hipMemcpyDeviceToHost));
     return KASA_OK;
+}
+
+extern "C" int kasa_bgzf_deflate(int device, const void *src, uint64_t n, void *dst, uint64_t dstCap, uint64_t *nOut)
+{
+    return kasa_bgzf_deflate_coded(device, KASA_BGZF_FIXED, src, n, dst, dstCap, nOut);
 }
 
 // ------------------------------------------------------------------------------------------------

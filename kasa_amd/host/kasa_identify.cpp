@@ -740,6 +740,7 @@ struct Params {
     bool gzipOut = false;                        // --gzip: the --filter files are written through zlib (Compare.hpp:2455,3713-3731)
     bool coherence = false; float coherenceThreshold = 11.0f;   // --coherence, --coherenceThreshold (MetaHeader.h:159)
     bool bgzf = false;                             // --bgzf: the per-read file is a BGZF stream (blocked gzip), compressed where its text is made
+    bool bgzfDynamic = false;                      // --bgzf-dynamic (implies --bgzf): device batches get a Huffman table of their own (KASA_BGZF_DYNAMIC); what the host writes stays zlib level 1
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
     bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
     bool devicePairs = false;                      // --device-pairs (implies --device-parse): paired-end input is parsed into two pools and paired on the device (kasa_pair_*)
@@ -2042,7 +2043,8 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
                 if (p.filter && kasa_batch_text_fetch(ctx, nullptr, nullptr, wb.flags.data())) throwLast();
                 if (p.bgzf) {                                      // the pieces below are the stream's then: cut at any byte
                     uint64_t zBytes = 0, zBlocks = 0;
-                    ScopedTimerMt tm(g_ht.deflate, g_ht.mu);
+                    ScopedTimerMt tm(g_ht.deflate, g_ht.mu);           // (with --bgzf-dynamic: the count pass and the table's build are in it)
+                    if (p.bgzfDynamic && kasa_ctx_set_bgzf_code(ctx, KASA_BGZF_DYNAMIC)) throwLast();
                     if (kasa_batch_bgzf(ctx, &zBytes, &zBlocks)) throwLast();
                     nBytes = zBytes;
                 }
@@ -2487,6 +2489,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "ErrorThreshold") opt("--errorThreshold", val);
         else if (key == "Gzip") flag("--gzip", val);
         else if (key == "Bgzf") flag("--bgzf", val);                                 // ours: the reference never compresses the per-read file
+        else if (key == "BgzfDynamic") flag("--bgzf-dynamic", val);
         else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
         else if (key == "DevicePairs") flag("--device-pairs", val);
         else if (key == "DeviceInflate") flag("--device-inflate", val);
@@ -3339,6 +3342,7 @@ static int run(int argc, char **argv)
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());
         else if (s == "--gzip") p.gzipOut = true;                                                  // main.cpp:570-572
         else if (s == "--bgzf") p.bgzf = true;
+        else if (s == "--bgzf-dynamic") p.bgzf = p.bgzfDynamic = true;
         else if (s == "-a" || s == "--alphabet") { p.codonFile = next(); p.codonId = next(); }
         else if (s == "--coherence") p.coherence = true;                                        // main.cpp:576-581
         else if (s == "--coherenceThreshold") p.coherenceThreshold = std::stof(next());

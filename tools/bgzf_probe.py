@@ -5,12 +5,13 @@
     python tools/bgzf_probe.py --table-from profiles/bgzf_probe.json      # only rewrite DESIGN.md's table from a result
 
 Every run is a fresh process of the driver (-m 1024 -n 16 --jsonl -v, KASA_HOST_TIMING=1).  Legs, taking turns: `other`
-(--other-exe: the driver of the parent commit, for "nothing changes without the flag"), `plain` (this driver) and `bgzf`
-(this driver with --bgzf).  Per leg: "Time file" of every run, min / median / max, and the median host breakdown (`output
+(--other-exe: the driver of the parent commit, for "nothing changes without the flag"), `plain` (this driver), `bgzf`
+(this driver with --bgzf) and `dynamic` (this driver with --bgzf-dynamic: a Huffman table per batch).  Per leg: "Time file" of every run, min / median / max, and the median host breakdown (`output
 write`, `text fetch`, `text`, `deflate`, ...).  The sizes: plain bytes, compressed bytes, their ratio -- and what zlib level 1
 makes of the same text block by block on the CPU with the fixed Huffman code (Z_FIXED: the gap to ours is the matcher's
 cost) and with its own tables (what a Huffman table per batch would buy), on a sample of blocks spread over the file.
---kernel-trace: one more `bgzf` run under `rocprofv3 --kernel-trace --stats` for the new kernels (total ms, GB/s of text).
+--kernel-trace: one more `bgzf` and one more `dynamic` run under `rocprofv3 --kernel-trace --stats` for the kernels of each
+(total ms, GB/s of text; `dynamic`: the count pass, the table's build and the coded pass apart).
 Only `kasa_bgzf::` kernels are counted there: the rocPRIM scan of the member sizes (4097 values per 256 MiB of text) and the
 memset of as many bytes carry the names the other stages' scans and memsets carry, so the statistics cannot tell them apart;
 the result says so in `kernels_left_out`.
@@ -70,22 +71,25 @@ BEGIN, END = "<!-- bgzf_probe: table begin (tools/bgzf_probe.py writes it) -->",
 
 def table(res):
     """the result as the markdown table of DESIGN.md section 8e"""
-    names = {"other": "parent commit's driver", "plain": "this driver", "bgzf": "this driver, `--bgzf`"}
+    names = {"other": "parent commit's driver", "plain": "this driver", "bgzf": "this driver, `--bgzf`", "dynamic": "this driver, `--bgzf-dynamic`"}
     host = ("output write", "text fetch", "text", "deflate")
     rows = ["%d reads of %d bases, `--jsonl`, %d runs a leg, fresh processes taking turns; seconds, host entries are medians:" % (res["reads"], res["read_length"], res["runs"]), "",
             "| leg | Time file min / median / max | " + " | ".join("`%s`" % h for h in host) + " | file bytes |", "|---|---|" + "---|" * (len(host) + 1)]
-    for leg in ("other", "plain", "bgzf"):
+    for leg in ("other", "plain", "bgzf", "dynamic"):
         if leg in res["legs"]:
             r = res["legs"][leg]
             cells = ["%.3f" % r["host_median_s"][h] if h in r["host_median_s"] else "-" for h in host]
             rows.append("| %s | %.3f / %.3f / %.3f | %s | %d |" % (names[leg], r["min_s"], r["median_s"], r["max_s"], " | ".join(cells), r["file_bytes"]))
     z = res.get("zlib_on_the_cpu", {})
-    rows += ["", "Ratio (compressed / plain bytes): %.3f on the device; zlib level 1 block by block on %s sampled blocks of the same text: %s with the fixed code, %s with its own tables." %
-             (res["ratio"], z.get("blocks_sampled", "no"), "%.3f" % z["zlib1_fixed_ratio"] if z else "-", "%.3f" % z["zlib1_dynamic_ratio"] if z else "-")]
-    if "bgzf_file" in res:
-        rows.append("The `--bgzf` file decompresses to the plain file: %s; it ends with the EOF block: %s." % (res["bgzf_file"]["decompresses_to_the_plain_file"], res["bgzf_file"]["ends_with_eof_block"]))
-    for k, v in sorted(res.get("kernels", {}).items()):
-        rows.append("`%s`: %d calls, %.1f ms in all, %.1f GB/s of text." % (k, v["calls"], v["total_ms"], v["text_gb_per_s"] or 0.0))
+    rows += ["", "Ratio (compressed / plain bytes): %.3f on the device with the fixed code%s; zlib level 1 block by block on %s sampled blocks of the same text: %s with the fixed code, %s with its own tables." %
+             (res["ratio"], ", %.3f with a table per batch (%.3f of the fixed code's file)" % (res["dynamic_ratio"], res["dynamic_bytes"] / res["bgzf_bytes"]) if "dynamic_ratio" in res else "",
+              z.get("blocks_sampled", "no"), "%.3f" % z["zlib1_fixed_ratio"] if z else "-", "%.3f" % z["zlib1_dynamic_ratio"] if z else "-")]
+    for key, flag in (("bgzf_file", "--bgzf"), ("dynamic_file", "--bgzf-dynamic")):
+        if key in res:
+            rows.append("The `%s` file decompresses to the plain file: %s; it ends with the EOF block: %s." % (flag, res[key]["decompresses_to_the_plain_file"], res[key]["ends_with_eof_block"]))
+    for leg, flag in (("kernels", "--bgzf"), ("kernels_dynamic", "--bgzf-dynamic")):
+        for k, v in sorted(res.get(leg, {}).items()):
+            rows.append("`%s`, `%s`: %d calls, %.1f ms in all, %.1f GB/s of text." % (flag, k, v["calls"], v["total_ms"], v["text_gb_per_s"] or 0.0))
     if "kernels_left_out" in res:
         rows.append("Left out of the kernels' total: " + res["kernels_left_out"])
     return "\n".join(rows)
@@ -129,7 +133,7 @@ def main():
         del ix, reads, g
         print("input made:", res["fastq_bytes"], "bytes of FASTQ", flush=True)
         exe = build.build_host()
-        legs = ([("other", a.other_exe, [])] if a.other_exe else []) + [("plain", exe, []), ("bgzf", exe, ["--bgzf"])]
+        legs = ([("other", a.other_exe, [])] if a.other_exe else []) + [("plain", exe, []), ("bgzf", exe, ["--bgzf"]), ("dynamic", exe, ["--bgzf-dynamic"])]
         runs = {name: [] for name, *_ in legs}
         out = os.path.join(d, "out.jsonl")
         for i in range(a.runs):                                  # the legs take turns, so that drift hits all of them alike
@@ -141,12 +145,12 @@ def main():
                     res["zlib_on_the_cpu"] = zlib_blockwise(out, a.sample_blocks)
                     with open(out, "rb") as f:
                         plain_digest = digest(f)
-                if name == "bgzf" and i == 0:                    # the file rule, at full size: the same bytes, the EOF block at the end
+                if name in ("bgzf", "dynamic") and i == 0:       # the file rule, at full size: the same bytes, the EOF block at the end
                     with gzip.open(out, "rb") as z:
                         same = digest(z) == plain_digest
                     with open(out, "rb") as f:
                         f.seek(-28, os.SEEK_END)
-                        res["bgzf_file"] = {"decompresses_to_the_plain_file": same, "ends_with_eof_block": f.read() == formats.BGZF_EOF}
+                        res[name + "_file"] = {"decompresses_to_the_plain_file": same, "ends_with_eof_block": f.read() == formats.BGZF_EOF}
         for name, rs in runs.items():
             t = [r["time_file_s"] for r in rs]
             keys = sorted({k for r in rs for k in r.get("host", {})})
@@ -156,18 +160,21 @@ def main():
         res["plain_bytes"] = res["legs"]["plain"]["file_bytes"]
         res["bgzf_bytes"] = res["legs"]["bgzf"]["file_bytes"]
         res["ratio"] = res["bgzf_bytes"] / res["plain_bytes"]
-        if a.kernel_trace:
+        res["dynamic_bytes"] = res["legs"]["dynamic"]["file_bytes"]
+        res["dynamic_ratio"] = res["dynamic_bytes"] / res["plain_bytes"]
+        for key, flag in (("kernels", "--bgzf"), ("kernels_dynamic", "--bgzf-dynamic")) if a.kernel_trace else ():
             td = tempfile.mkdtemp(prefix="kasa_bgz_trace_")
-            run_once(exe, d, ["--bgzf"], {}, wrap=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", td, "--"])
+            run_once(exe, d, [flag], {}, wrap=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", td, "--"])
             kern = {}
             for f in glob.glob(os.path.join(td, "**", "*kernel_stats.csv"), recursive=True):
                 for row in csv.DictReader(open(f)):
                     if "kasa_bgzf" in row.get("Name", ""):
                         ns = int(row["TotalDurationNs"])          # text_gb_per_s: the rate at which the kernel gets through the plain text
                         kern[row["Name"].split("(")[0]] = {"calls": int(row["Calls"]), "total_ms": ns * 1e-6, "text_gb_per_s": res["plain_bytes"] / ns if ns else None}
-            res["kernels"] = kern
-            res["kernels_left_out"] = "the rocPRIM scan of the member sizes and the memset before it (4097 values per 256 MiB of text): the statistics list them under names the other stages share"
+            res[key] = kern
             shutil.rmtree(td, ignore_errors=True)
+        if a.kernel_trace:
+            res["kernels_left_out"] = "the rocPRIM scan of the member sizes and the memset before it (4097 values per 256 MiB of text): the statistics list them under names the other stages share"
     finally:
         shutil.rmtree(d, ignore_errors=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
