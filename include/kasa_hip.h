@@ -752,6 +752,41 @@ int kasa_bgzf_parse_ms(kasa_parser *p, double *inflateMs);
 int kasa_pair_take(kasa_parser *first, kasa_parser *second, kasa_ctx *ctx, uint64_t nPairs);
 int kasa_pair_fetch(kasa_parser *first, kasa_parser *second, uint64_t firstPair, uint64_t nPairs, uint32_t *lengths, uint64_t *nameOff, char *names,
                     int64_t *off, uint8_t *bases);
+/* --filter on the device (--device-filter): every read is written back to one of two files, so the pool can keep the reads'
+ * RECORD TEXT: every non-empty line of the record (from its header line up to the next header or the chunk's end), each followed
+ * by one line feed -- what the host driver's filterReads writes for the read.  A '\r' stays part of its line (a line that is only
+ * "\r" is not empty), a last line without a line feed gets one; FASTQ records are their four lines, FASTA drops the empty ones.
+ * (The two pool calls are named kasa_pool_*: kasa_parse_* stays the parser's surface as it was.)
+ *   kasa_pool_keep_records   keep != 0: from now on every append (kasa_parse_append, kasa_bgzf_parse_append) also writes the
+ *                             records and running 64-bit recOff[nReads + 1] behind the pool's end, under the same rule as the
+ *                             other arrays (a refused chunk leaves them as they were); they are compacted with the pool, and
+ *                             kasa_parse_take gives the context its own device-to-device copy of the taken reads' records with
+ *                             offsets from 0, valid until the batch's last call.  keep = 0 (how a pool starts): no extra kernel
+ *                             runs and no extra memory is taken.  KASA_E_STATE unless the pool is empty and nothing is carried.
+ *                             kasa_pair_take / kasa_pair_fetch do not hand records on.
+ *   kasa_pool_fetch_records  test tap: records and recOff of reads [first, first + n), rebased to `first`; either pointer may be
+ *                             NULL; KASA_E_STATE when the pool keeps no records.
+ *   kasa_batch_filter         after kasa_parse_take from such a pool: the batch's records split by flag, in the reads' order.
+ *                             side 0: clean (flag 0), side 1: contaminants.  contaminated: nReads host bytes, or NULL for the
+ *                             flags kasa_batch_text left on the device (a host array is what a driver has when kasa_batch_rank
+ *                             left reads to the host, or when it wrote the rows itself).  sides: bit mask of the sides wanted (bit
+ *                             0 clean, bit 1 contaminants); a side that is not wanted costs nothing and gives 0 and 0.
+ *                             gzip != 0: each wanted side's text becomes a BGZF stream by the kernels of kasa_batch_bgzf in the
+ *                             context's code (kasa_ctx_set_bgzf_code), without end-of-file block; nBytes is then the stream's
+ *                             length.  nReads[side]: reads of that side.  An empty batch or side gives 0 and 0.  KASA_E_STATE:
+ *                             the batch has no records (kasa_batch_upload*, kasa_pair_take), or contaminated is NULL and there
+ *                             is no text of this batch.  One lane per read for the sizes, two running sums (flagged reads and
+ *                             flagged bytes: the clean side's follow from recOff), one lane per read for the sides' lists, and
+ *                             the 64-bit gather of kasa_pair_take split by output bytes; no atomics.
+ *   kasa_batch_filter_fetch_range  dst[nBytes] = side's text (or stream) [offset, offset + nBytes).
+ *   kasa_filter_split         test tap, host to host, the same kernels: one side of nReads records as plain text.  *nOut is the
+ *                             side's size even when it exceeds cap (then KASA_E_LIMIT and nothing is written). */
+int kasa_pool_keep_records(kasa_parser *p, int keep);
+int kasa_pool_fetch_records(kasa_parser *p, uint64_t first, uint64_t n, uint64_t *recOff, char *records);
+int kasa_batch_filter(kasa_ctx *ctx, const uint8_t *contaminated, unsigned sides, int gzip, uint64_t nBytes[2], uint64_t nReads[2]);
+int kasa_batch_filter_fetch_range(kasa_ctx *ctx, int side, void *dst, uint64_t offset, uint64_t nBytes);
+int kasa_filter_split(int device, const char *records, const uint64_t *recOff, uint64_t nReads, const uint8_t *flags, int side, char *out, uint64_t cap,
+                      uint64_t *nOut, uint64_t *nReadsOut);
 void kasa_parse_destroy(kasa_parser *p);
 
 #ifdef __cplusplus

@@ -43,6 +43,7 @@ EXPORTS = [
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate", "kasa_ctx_set_bgzf_code", "kasa_bgzf_deflate_coded",
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
     "kasa_ctx_row_classes", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
+    "kasa_pool_keep_records", "kasa_pool_fetch_records", "kasa_batch_filter", "kasa_batch_filter_fetch_range", "kasa_filter_split",
 ]
 
 
@@ -209,6 +210,11 @@ def lib():
         L.kasa_bgzf_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_bgzf_parse_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_parse_destroy.restype = None
+        L.kasa_pool_keep_records.argtypes = [C.c_void_p, C.c_int]
+        L.kasa_pool_fetch_records.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kasa_batch_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+        L.kasa_batch_filter_fetch_range.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.kasa_filter_split.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _check_runtime(L)
         _lib = L
     return _lib
@@ -699,6 +705,22 @@ class Parser:
         _check(L.kasa_parse_fetch(self.h, C.c_uint64(first), C.c_uint64(n), None, None, _p(names), None, _p(bases)))
         return lengths, name_off, names, off, bases
 
+    def keep_records(self, keep: bool = True):
+        """kasa_pool_keep_records: the appends that follow also keep every read's record text (what --filter writes back) and
+        `take` hands it to the context.  Only on an empty pool (KASA_E_STATE otherwise)."""
+        _check(lib().kasa_pool_keep_records(self.h, C.c_int(1 if keep else 0)))
+
+    def fetch_records(self, first: int = 0, n: int = None):
+        """Record text of reads [first, first + n) of the pool: (rec_off u64[n+1] rebased to `first`, records bytes)."""
+        pooled = self.sizes()[0]
+        n = pooled - first if n is None else n
+        rec_off = np.zeros(n + 1, dtype=np.uint64)
+        L = lib()
+        _check(L.kasa_pool_fetch_records(self.h, C.c_uint64(first), C.c_uint64(n), _p(rec_off), None))
+        records = np.zeros(max(1, int(rec_off[-1])), dtype=np.uint8)
+        _check(L.kasa_pool_fetch_records(self.h, C.c_uint64(first), C.c_uint64(n), None, _p(records)))
+        return rec_off, records[:int(rec_off[-1])].tobytes()
+
     def take(self, ctx: "Context", n_reads: int):
         """The first n_reads pooled reads become ctx's batch (as Context.upload does) and leave the pool."""
         _check(lib().kasa_parse_take(self.h, ctx.h, C.c_uint64(n_reads)))
@@ -720,6 +742,23 @@ class Parser:
             self.close()
         except Exception:
             pass
+
+
+def filter_split(device: int, records: bytes, rec_off, flags, side: int, cap: int = None):
+    """kasa_filter_split: one side (0 clean, 1 contaminants) of the records under the flags, through the split's kernels.
+    -> (bytes of the side, its reads).  cap: room of the destination (None: all the records); too small raises (KASA_E_LIMIT)."""
+    rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    n = int(flags.shape[0])
+    if rec_off.shape[0] != n + 1:
+        raise ValueError("filter_split: rec_off has one entry more than there are flags")
+    rec = np.frombuffer(records, dtype=np.uint8)
+    cap = int(rec.shape[0]) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    n_out, n_reads = C.c_uint64(0), C.c_uint64(0)
+    _check(lib().kasa_filter_split(C.c_int(device), _p(rec) if rec.shape[0] else None, _p(rec_off), C.c_uint64(n), _p(flags) if n else None, C.c_int(side),
+                                   _p(out), C.c_uint64(cap), C.byref(n_out), C.byref(n_reads)))
+    return out[:n_out.value].tobytes(), int(n_reads.value)
 
 
 def _pool_handle(p):
@@ -998,6 +1037,25 @@ class Context:
             k = min(step, n.value - a)
             _check(lib().kasa_batch_bgzf_fetch_range(self.h, C.c_void_p(buf.ctypes.data + a), C.c_uint64(a), C.c_uint64(k)))
         return buf[:n.value].tobytes()
+
+    def filter(self, flags=None, sides: int = 3, gzip: bool = False):
+        """kasa_batch_filter + fetch: the batch's records (Parser.keep_records, Parser.take) split by flag.  flags: uint8[n_reads],
+        or None for those the last text() left on the device.  sides: bit 0 clean, bit 1 contaminants.  gzip: each side as a
+        BGZF stream (no EOF block) in the context's code.  -> (clean bytes, contaminant bytes, clean reads, contaminant reads)"""
+        fl = None
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8)
+            if fl.shape[0] != self.n_reads:
+                raise ValueError("filter: one flag per read")
+        nb, nr = (C.c_uint64 * 2)(0, 0), (C.c_uint64 * 2)(0, 0)
+        _check(lib().kasa_batch_filter(self.h, _p(fl) if fl is not None and fl.shape[0] else None, C.c_uint(sides), C.c_int(1 if gzip else 0), nb, nr))
+        out = []
+        for side in (0, 1):
+            buf = np.empty(max(1, nb[side]), dtype=np.uint8)
+            if nb[side]:
+                _check(lib().kasa_batch_filter_fetch_range(self.h, C.c_int(side), _p(buf), C.c_uint64(0), C.c_uint64(nb[side])))
+            out.append(buf[:nb[side]].tobytes())
+        return out[0], out[1], int(nr[0]), int(nr[1])
 
     def coherence(self) -> np.ndarray:
         """--coherence scores of the batch (Compare::postProcess): float32[n_reads].  Raises where the reference throws."""

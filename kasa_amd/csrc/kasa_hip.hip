@@ -702,6 +702,10 @@ struct kasa_ctx {
     DevBuf bgzMembers, bgzSize, bgzOff, bgzOut;                // kasa_batch_bgzf: members at their stride (a chunk of blocks), u64 sizes and offsets, the stream
     DevBuf bgzCode; int bgzCodeKind = KASA_BGZF_FIXED;         // ... the stream's histogram, table and block header (kasa_bgzf::Code) with KASA_BGZF_DYNAMIC; kasa_ctx_set_bgzf_code
     uint64_t bgzTotal = 0; bool bgzValid = false;              // ... of the text that is valid now (kasa_batch_text forgets it)
+    // kasa_parse_take from a pool that keeps records: the batch's record text and u64[nReads + 1] offsets from 0 (kasa_filter.h)
+    DevBuf fltRecords, fltRecOff; bool fltHaveRecords = false; uint64_t fltRecBytes = 0;
+    DevBuf fltFlags, fltCnt, fltByt, fltSrc[2], fltDst[2], fltOut[2], fltZ[2];   // kasa_batch_filter: flags, their two running sums, per side the entries, the text, its stream
+    uint64_t fltBytes[2] = {0, 0}; bool fltValid = false, fltGzip = false;      // ... what kasa_batch_filter_fetch_range delivers
     const float *cohScores = nullptr;                          // device: the scores of the last kasa_batch_coherence of this batch
     const void *cohKey = nullptr; bool cohBegun = false;       // kasa_batch_coherence_begin handed this batch's k-mers (cohKey) and depth bytes out; _finish not yet
     bool grouped = false; uint32_t poolUsed = 1; // event records + pool of this batch are in place (group stage or import)
@@ -780,7 +784,8 @@ struct kasa_ctx {
                 &outScore, &cntUnique, &cntTotal, &cntAllHi, &cntAllLo, &rawOff, &cohLen, &cohState, &sortBig, &rankDen, &rankClass, &rankMeta, &rankOut,
                 &rankList, &rankScratch, &scanTmp, &taxText, &taxTextOff, &taxTextIds, &txtNames, &txtNameOff, &txtLen, &txtBest, &txtBytes, &txtOff, &txtOut,
                 &txtFlags, &bgzMembers, &bgzSize, &bgzOff, &bgzOut, &bgzCode, &encLong, &wireOff, &esrLong, &esrShort, &esrIota, &esrQOff, &esrReadEv, &esrEvCnt, &esrEvOff, &esrKeyA, &esrKeyB, &esrValA, &esrValB, &esrChain,
-                &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn, &clsList};
+                &esrChainScore, &esrBig, &cohKmIn, &cohPart, &cohIn, &absorbIn, &clsList,
+                &fltRecords, &fltRecOff, &fltFlags, &fltCnt, &fltByt, &fltSrc[0], &fltSrc[1], &fltDst[0], &fltDst[1], &fltOut[0], &fltOut[1], &fltZ[0], &fltZ[1]};
     }
 };
 
@@ -1029,7 +1034,7 @@ static int upload_reset(kasa_ctx *c, int64_t nSeq, int64_t nReads)
 {
     if ((uint64_t)nReads >= 0xFFFFFFF0ull || (uint64_t)nSeq >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_upload: more than 2^32 reads in one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->fltHaveRecords = false; c->fltValid = false; coh_forget(c); c->nReads = nReads; c->nSeq = nSeq; c->nQ = 0;
     c->recOut = nullptr; c->recSorted = false;
     return KASA_OK;
 }
@@ -7091,7 +7096,7 @@ extern "C" int kasa_batch_set_sorted_device(kasa_ctx *c, const void *kmersDev, u
     if (!c || (n && !kmersDev)) return fail(KASA_E_ARG, "kasa_batch_set_sorted_device: bad arguments");
     if (n >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_set_sorted_device: too many queries for one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c);
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->fltHaveRecords = false; c->fltValid = false; coh_forget(c);
     c->recOut = nullptr; c->recSorted = false;                       // the last batch's exported records (the caller's buffer) are not this batch's
     int rc;
     if ((rc = c->qKmerB.reserve(n * c->keyBytes() + 64))) return rc;
@@ -8902,7 +8907,7 @@ static int batch_set_queries_impl(kasa_ctx *c, const void *kmers, const uint32_t
     if (nReads < 0 || (n && (!kmers || !reads))) return fail(KASA_E_ARG, "kasa_batch_set_queries: bad arguments");
     if (n >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_set_queries: too many queries for one batch");
     HIPCHK(hipSetDevice(c->ix->device));
-    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; coh_forget(c); c->readsUploaded = false; c->recOut = nullptr; c->recSorted = false;
+    c->state = 0; c->haveScores = false; c->grouped = false; c->slotOf = nullptr; c->payloadIsSlot = false; c->rankValid = false; c->txtValid = false; c->fltHaveRecords = false; c->fltValid = false; coh_forget(c); c->readsUploaded = false; c->recOut = nullptr; c->recSorted = false;
     std::vector<uint64_t> koff((size_t)nReads + 1, 0);
     uint32_t maxCnt = 0;
     for (uint64_t i = 0; i < n; ++i) {
@@ -9109,3 +9114,4 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
 // parse: FASTA / FASTQ text -> the reads of a batch on the device (kasa_parse_*)
 // ------------------------------------------------------------------------------------------------
 #include "kasa_parse.h"
+#include "kasa_filter.h"

@@ -18,6 +18,9 @@
 //                output bytes between those two, reads them with unaligned dword loads + v_alignbyte (or byte by byte where
 //                the 16 bytes span lines) and stores one aligned 16-byte vector.  The same sweep checks the sequence bytes
 //                for ' ' and '\t'.  No atomics except the one that reports the first offence; no lane walks a record.
+// kasa_pool_keep_records: the pool also keeps every read's RECORD TEXT (what --filter writes back: every non-empty line of the
+// record and one line feed each) with running recOff: prs_recsize_kernel, one running sum over the lines, prs_recindex_kernel
+// and prs_recoff_kernel list the non-empty lines, and the gather's third flavour copies them behind the pool's end.
 // A chunk that is not in the form the device takes (KASA_PARSE_* codes) leaves the pool as it was: everything is written
 // behind the pool's end and the sizes move only when the status word is clean.
 #pragma once
@@ -157,14 +160,19 @@ __device__ __forceinline__ uint32_t prs_find(const uint32_t *__restrict__ dst, u
     return lo;
 }
 
-// Entry j = text[src[j] ...) goes to output bytes [dst[j], dst[j + 1]); NAMES: its last byte is a space instead.  n >= 1 entries
+// Entry j = text[src[j] ...) goes to output bytes [dst[j], dst[j + 1]); GATHER_NAMES: its last byte is a space instead,
+// GATHER_RECORDS: a line feed (the text has one there, or nothing: a last line without one).  n >= 1 entries
 // of at least one byte, dst[n] = total.  `out` is the 16-byte aligned address at or below the pool's end and `lead` what lies
 // between the two, so that every store of a whole vector is aligned whatever the pool holds.
-template <bool NAMES>
+enum { GATHER_BASES = 0, GATHER_NAMES = 1, GATHER_RECORDS = 2 };
+template <int KIND>
 __global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *__restrict__ text, const uint32_t *__restrict__ src, const uint32_t *__restrict__ dst,
                                                                 uint32_t n, uint32_t total, uint8_t *__restrict__ out, uint32_t lead,
                                                                 unsigned long long *__restrict__ status)
 {
+    constexpr bool NAMES = KIND != GATHER_BASES;                                 // the entry's last byte is not the text's
+    constexpr uint32_t LAST = KIND == GATHER_NAMES ? (uint32_t)' ' : (uint32_t)'\n';
+    constexpr bool BLANKS = KIND == GATHER_BASES;                                // only the letters are checked for ' ' and '\t'
     const uint32_t tile = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const uint64_t vEnd = (uint64_t)lead + total, v0 = (uint64_t)tile * TILE_BYTES;
     if (v0 >= vEnd) return;
@@ -188,7 +196,7 @@ __global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *_
             const uint32_t sh = a & 3u, x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3], x4 = q[4];
             w[0] = __builtin_amdgcn_alignbyte(x1, x0, sh); w[1] = __builtin_amdgcn_alignbyte(x2, x1, sh);
             w[2] = __builtin_amdgcn_alignbyte(x3, x2, sh); w[3] = __builtin_amdgcn_alignbyte(x4, x3, sh);
-            if (!NAMES && (eq_bytes(w[0], 0x20202020u) | eq_bytes(w[1], 0x20202020u) | eq_bytes(w[2], 0x20202020u) | eq_bytes(w[3], 0x20202020u) |
+            if (BLANKS && (eq_bytes(w[0], 0x20202020u) | eq_bytes(w[1], 0x20202020u) | eq_bytes(w[2], 0x20202020u) | eq_bytes(w[3], 0x20202020u) |
                            eq_bytes(w[0], 0x09090909u) | eq_bytes(w[1], 0x09090909u) | eq_bytes(w[2], 0x09090909u) | eq_bytes(w[3], 0x09090909u)) != 0)
                 for (int q = 15; q >= 0; --q) { const uint32_t c = (w[q >> 2] >> (8 * (q & 3))) & 0xFFu; if (c == ' ' || c == '\t') blankAt = a + q; }
         } else {
@@ -198,8 +206,8 @@ __global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *_
                 if (v < vs || v >= vb) continue;
                 const uint32_t k = (uint32_t)(v - lead);
                 while (k >= d1) { ++j; d0 = d1; d1 = dst[j + 1]; s0 = src[j]; }       // (every entry has a byte: at most 16 steps per lane)
-                const uint32_t c = (NAMES && k == d1 - 1) ? (uint32_t)' ' : (uint32_t)text[s0 + (k - d0)];
-                if (!NAMES && (c == ' ' || c == '\t') && blankAt == ~0u) blankAt = s0 + (k - d0);
+                const uint32_t c = (NAMES && k == d1 - 1) ? LAST : (uint32_t)text[s0 + (k - d0)];
+                if (BLANKS && (c == ' ' || c == '\t') && blankAt == ~0u) blankAt = s0 + (k - d0);
                 w[q >> 2] |= c << (8 * (q & 3));
             }
         }
@@ -208,6 +216,31 @@ __global__ __launch_bounds__(64 * WAVES) void prs_gather_kernel(const uint8_t *_
         else
             for (int q = 0; q < 16; ++q) { const uint64_t v = va + q; if (v >= vs && v < vb) out[v] = (uint8_t)(w[q >> 2] >> (8 * (q & 3))); }
     }
+}
+
+// ---- the records (kasa_pool_keep_records).  k3 = non-empty lines << 32 | their bytes with one line feed each (a chunk and
+// one added line feed stay below 2^32); entry nLines = 0: the running sum's totals land there.
+__global__ void prs_recsize_kernel(const uint32_t *__restrict__ lineStart, uint32_t nLines, uint64_t *__restrict__ k3)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nLines) return;
+    const uint32_t len = i < nLines ? lineStart[i + 1] - 1 - lineStart[i] : 0;
+    k3[i] = len ? (1ull << 32) | (uint64_t)(len + 1) : 0;
+}
+// after the running sum: the non-empty lines in order with their place in the records' text
+__global__ void prs_recindex_kernel(const uint32_t *__restrict__ lineStart, const uint64_t *__restrict__ k3, uint32_t nLines, uint32_t *__restrict__ recSrc, uint32_t *__restrict__ recDst)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > nLines) return;
+    const uint64_t a = k3[i];
+    if (i == nLines) { recDst[(uint32_t)(a >> 32)] = (uint32_t)a; return; }
+    if ((k3[i + 1] >> 32) != (a >> 32)) { recSrc[(uint32_t)(a >> 32)] = lineStart[i]; recDst[(uint32_t)(a >> 32)] = (uint32_t)a; }
+}
+// one lane per read and one for the end: a record starts with its header line
+__global__ void prs_recoff_kernel(const uint32_t *__restrict__ hdrLine, const uint64_t *__restrict__ k3, uint32_t nReads, uint64_t recBase, uint64_t *__restrict__ recOff)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r <= nReads) recOff[r] = recBase + (uint32_t)k3[hdrLine[r]];
 }
 
 // the FASTA cut of kasa_bgzf_parse_append: the last line that begins with '>' as line << 32 | its start (the key grows with the line)
@@ -244,6 +277,7 @@ struct PairOffsets {
     uint64_t a0, b0;
     __device__ __forceinline__ uint64_t dst(uint64_t j) const { return (a[(j >> 1) + (j & 1)] - a0) + (b[j >> 1] - b0); }
     __device__ __forceinline__ uint64_t src(uint64_t j) const { return (j & 1) ? b[j >> 1] : a[j >> 1]; }
+    __device__ __forceinline__ const uint8_t *base(uint64_t j, const uint8_t *src1, const uint8_t *src2) const { return (j & 1) ? src2 : src1; }
     // largest j in [lo, hi] with D(j) <= o; for o < D(hi + 1) that entry holds byte o: the empty ones before it are stepped over
     __device__ __forceinline__ uint64_t find(uint64_t lo, uint64_t hi, uint64_t o) const
     {
@@ -272,8 +306,11 @@ __global__ void pair_layout_kernel(PairOffsets lo, PairOffsets na, const uint32_
 // The copy, split by OUTPUT bytes like prs_gather_kernel: a wavefront owns TILE_BYTES of `out` (16-byte aligned), finds the
 // entries of its tile by bisection in D, every lane the entry of its 16 bytes.  16 bytes of one entry: five dwords from the
 // 4-byte aligned address below (both sources are padded behind their end, pool_room), shifted into place, one aligned store.
-// Lanes whose 16 bytes cross a junction, and the tail, go byte by byte.  n >= 1, total >= 1; positions are 64-bit.
-__global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *__restrict__ src1, const uint8_t *__restrict__ src2, PairOffsets d, uint64_t n,
+// Lanes whose 16 bytes cross a junction, and the tail, go byte by byte.  nEntries >= 1, total >= 1; positions are 64-bit.
+// Offsets names the entries: dst(j) (ascending, dst(nEntries) = total), src(j), base(j, src1, src2), find -- PairOffsets above
+// (2 n entries of two pools), kasa_filter's FilterOffsets (the reads of one side of --filter, one source).
+template <class Offsets>
+__global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *__restrict__ src1, const uint8_t *__restrict__ src2, Offsets d, uint64_t nEntries,
                                                                  uint64_t total, uint8_t *__restrict__ out)
 {
     const uint64_t tile = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
@@ -281,14 +318,14 @@ __global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *
     const uint64_t v0 = tile * TILE_BYTES;
     if (v0 >= total) return;
     const uint64_t v1 = v0 + TILE_BYTES < total ? v0 + TILE_BYTES : total;
-    const uint64_t jLo = d.find(0, 2 * n - 1, v0), jHi = d.find(jLo, 2 * n - 1, v1 - 1);
+    const uint64_t jLo = d.find(0, nEntries - 1, v0), jHi = d.find(jLo, nEntries - 1, v1 - 1);
     for (int s = 0; s < STEPS; ++s) {
         const uint64_t va = v0 + (uint64_t)s * STEP_BYTES + lane * 16;
         if (va >= total) continue;
         const uint64_t vb = va + 16 < total ? va + 16 : total;
         uint64_t j = d.find(jLo, jHi, va);
         uint64_t d0 = d.dst(j), d1 = d.dst(j + 1);
-        const uint8_t *sp = ((j & 1) ? src2 : src1) + d.src(j);
+        const uint8_t *sp = d.base(j, src1, src2) + d.src(j);
         uint32_t w[4] = {0, 0, 0, 0};
         const bool whole = vb - va == 16;
         if (whole && va + 16 <= d1) {
@@ -303,7 +340,7 @@ __global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *
             for (int q = 0; q < 16; ++q) {
                 const uint64_t k = va + q;
                 if (k >= vb) continue;
-                while (k >= d1) { ++j; d0 = d1; d1 = d.dst(j + 1); sp = ((j & 1) ? src2 : src1) + d.src(j); }   // (k < total = D(2n): it ends; empty entries fall through)
+                while (k >= d1) { ++j; d0 = d1; d1 = d.dst(j + 1); sp = d.base(j, src1, src2) + d.src(j); }   // (k < total = dst(nEntries): it ends; empty entries fall through)
                 w[q >> 2] |= (uint32_t)sp[k - d0] << (8 * (q & 3));
             }
         }
@@ -314,7 +351,7 @@ __global__ __launch_bounds__(64 * WAVES) void pair_gather_kernel(const uint8_t *
     }
 }
 
-struct PoolArrays { DevBuf bases, off, names, nameOff, lengths; };
+struct PoolArrays { DevBuf bases, off, names, nameOff, lengths, records, recOff; };   // the last two with kasa_pool_keep_records only
 
 }  // namespace kasa_parse_impl
 
@@ -338,6 +375,10 @@ struct kasa_parser {
     double msInflate = 0;
     // kasa_pair_fetch (this pool as the first of the two): the interleaved arrays before they cross to the host
     DevBuf pairOff, pairNameOff, pairLengths, pairNames, pairBases;
+    // kasa_pool_keep_records: records / recOff of the pool's arrays are kept like names / nameOff
+    bool keepRecords = false;
+    uint64_t headRec = 0, endRec = 0;
+    DevBuf k3, recSrc, recDst;
 };
 
 namespace kasa_parse_impl {
@@ -365,6 +406,15 @@ static int pool_room(kasa_parser *p, PoolArrays &a, uint64_t reads, uint64_t bas
         return rc;
     return KASA_OK;
 }
+// ... and of `addRecs` bytes of record text behind `recs` (the 64 bytes of slack: the gathers' five-dword reads end behind a record)
+static int pool_room_records(kasa_parser *p, PoolArrays &a, uint64_t reads, uint64_t recs, uint64_t addReads, uint64_t addRecs, bool fresh)
+{
+    int rc;
+    if ((rc = grow_keep(a.records, recs + addRecs + 64, fresh ? 0 : recs, p->stream)) ||
+        (rc = grow_keep(a.recOff, (reads + addReads + 1) * 8, fresh ? 0 : (reads + 1) * 8, p->stream)))
+        return rc;
+    return KASA_OK;
+}
 
 // The reads already taken leave the arrays.  An empty pool starts over where it is (off[0] = nameOff[0] = 0 again, nothing
 // copied); a remainder moves to the front of the other set once the taken letters outweigh it, so that the copies stay
@@ -376,13 +426,20 @@ static int pool_compact(kasa_parser *p)
     if (n == 0) {
         HIPCHK(hipMemsetAsync(p->arrays[p->cur].off.p, 0, 8, p->stream));
         HIPCHK(hipMemsetAsync(p->arrays[p->cur].nameOff.p, 0, 8, p->stream));
-        p->head = p->nReads = 0; p->headBase = p->endBase = 0; p->headName = p->endName = 0;
+        if (p->keepRecords) HIPCHK(hipMemsetAsync(p->arrays[p->cur].recOff.p, 0, 8, p->stream));
+        p->head = p->nReads = 0; p->headBase = p->endBase = 0; p->headName = p->endName = 0; p->headRec = p->endRec = 0;
         return KASA_OK;
     }
     if (p->headBase <= nb) return KASA_OK;
     PoolArrays &from = p->arrays[p->cur], &to = p->arrays[p->cur ^ 1];
+    const uint64_t nr = p->endRec - p->headRec;
     int rc = pool_room(p, to, 0, 0, 0, n, nb, nn, true);
     if (rc) return rc;
+    if (p->keepRecords) {
+        if ((rc = pool_room_records(p, to, 0, 0, n, nr, true))) return rc;
+        if (nr) HIPCHK(hipMemcpyAsync(to.records.p, from.records.as<char>() + p->headRec, nr, hipMemcpyDeviceToDevice, p->stream));
+        prs_rebase_kernel<uint64_t><<<blocks_for(n + 1, 256), 256, 0, p->stream>>>(from.recOff.as<uint64_t>() + p->head, to.recOff.as<uint64_t>(), n + 1, p->headRec);
+    }
     if (nb) HIPCHK(hipMemcpyAsync(to.bases.p, from.bases.as<uint8_t>() + p->headBase, nb, hipMemcpyDeviceToDevice, p->stream));
     if (nn) HIPCHK(hipMemcpyAsync(to.names.p, from.names.as<char>() + p->headName, nn, hipMemcpyDeviceToDevice, p->stream));
     if (n) HIPCHK(hipMemcpyAsync(to.lengths.p, from.lengths.as<uint32_t>() + p->head, n * 4, hipMemcpyDeviceToDevice, p->stream));
@@ -390,7 +447,7 @@ static int pool_compact(kasa_parser *p)
     prs_rebase_kernel<uint64_t><<<blocks_for(n + 1, 256), 256, 0, p->stream>>>(from.nameOff.as<uint64_t>() + p->head, to.nameOff.as<uint64_t>(), n + 1, p->headName);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(p->stream));
-    p->cur ^= 1; p->head = 0; p->nReads = n; p->headBase = 0; p->endBase = nb; p->headName = 0; p->endName = nn;
+    p->cur ^= 1; p->head = 0; p->nReads = n; p->headBase = 0; p->endBase = nb; p->headName = 0; p->endName = nn; p->headRec = 0; p->endRec = nr;
     return KASA_OK;
 }
 
@@ -489,8 +546,18 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
         (rc = dev_exclusive_scan(p->scanTmp, p->stream, k2, k2, (uint64_t)0, (size_t)nLines + 1, rocprim::plus<uint64_t>()))) return rc;
     prs_index_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(lineStart, k1, k2, nLines, p->hdrLine.as<uint32_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    uint64_t tot[2] = {0, 0};
+    uint64_t tot[2] = {0, 0}, totRec = 0;
     unsigned long long st = ~0ull;
+    if (p->keepRecords) {                                                          // ---- the records' sizes: one more running sum over the lines
+        if ((rc = p->k3.reserve(nl * 8)) || (rc = p->recSrc.reserve(nl * 4)) || (rc = p->recDst.reserve(nl * 4))) return rc;
+        uint64_t *k3 = p->k3.as<uint64_t>();
+        prs_recsize_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(lineStart, nLines, k3);
+        HIPCHK(hipGetLastError());
+        if ((rc = dev_exclusive_scan(p->scanTmp, p->stream, k3, k3, (uint64_t)0, (size_t)nLines + 1, rocprim::plus<uint64_t>()))) return rc;
+        prs_recindex_kernel<<<blocks_for((uint64_t)nLines + 1, 256), 256, 0, p->stream>>>(lineStart, k3, nLines, p->recSrc.as<uint32_t>(), p->recDst.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        if ((rc = fetch_async(p->stream, totRec, k3 + nLines))) return rc;
+    }
     if ((rc = fetch_async(p->stream, tot[0], k1 + nLines)) || (rc = fetch_async(p->stream, tot[1], k2 + nLines)) || (rc = fetch(p->stream, st, status))) return rc;
     if (st != ~0ull) {                                                             // (the text went up all the same: it counts)
         float up = 0.0f;
@@ -504,6 +571,9 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
     if ((rc = pool_room(p, a, p->nReads, p->endBase, p->endName, addReads, addBases, addNames, false)) ||
         (rc = p->nameSrc.reserve((addReads + 2) * 4)) || (rc = p->nameDst.reserve((addReads + 2) * 4)))
         return rc;
+    const uint32_t nRecLines = (uint32_t)(totRec >> 32);
+    const uint64_t addRecs = totRec & 0xFFFFFFFFull;
+    if (p->keepRecords && (rc = pool_room_records(p, a, p->nReads, p->endRec, addReads, addRecs, false))) return rc;
     // ---- per read, then the two gathers behind the pool's end
     prs_reads_kernel<<<blocks_for(addReads + 1, 256), 256, 0, p->stream>>>(lineStart, p->hdrLine.as<uint32_t>(), k1, k2, (uint32_t)addReads, p->longSeq,
         (int64_t)p->endBase, p->endName, a.off.as<int64_t>() + p->nReads, a.nameOff.as<uint64_t>() + p->nReads, a.lengths.as<uint32_t>() + p->nReads,
@@ -512,16 +582,28 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
     if (addBases && nSeqLines) {
         const uint32_t lead = (uint32_t)(p->endBase & 15);
         const uint64_t tiles = (lead + addBases + TILE_BYTES - 1) / TILE_BYTES;
-        prs_gather_kernel<false><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>(),
+        prs_gather_kernel<GATHER_BASES><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->seqSrc.as<uint32_t>(), p->seqDst.as<uint32_t>(),
             nSeqLines, (uint32_t)addBases, a.bases.as<uint8_t>() + (p->endBase - lead), lead, status);
         HIPCHK(hipGetLastError());
     }
     if (addNames && addReads) {
         const uint32_t lead = (uint32_t)(p->endName & 15);
         const uint64_t tiles = (lead + addNames + TILE_BYTES - 1) / TILE_BYTES;
-        prs_gather_kernel<true><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->nameSrc.as<uint32_t>(), p->nameDst.as<uint32_t>(),
+        prs_gather_kernel<GATHER_NAMES><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->nameSrc.as<uint32_t>(), p->nameDst.as<uint32_t>(),
             (uint32_t)addReads, (uint32_t)addNames, a.names.as<uint8_t>() + (p->endName - lead), lead, status);
         HIPCHK(hipGetLastError());
+    }
+    if (p->keepRecords) {
+        prs_recoff_kernel<<<blocks_for(addReads + 1, 256), 256, 0, p->stream>>>(p->hdrLine.as<uint32_t>(), p->k3.as<uint64_t>(), (uint32_t)addReads, p->endRec,
+            a.recOff.as<uint64_t>() + p->nReads);
+        HIPCHK(hipGetLastError());
+        if (addRecs && nRecLines) {
+            const uint32_t lead = (uint32_t)(p->endRec & 15);
+            const uint64_t tiles = (lead + addRecs + TILE_BYTES - 1) / TILE_BYTES;
+            prs_gather_kernel<GATHER_RECORDS><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, p->stream>>>(p->text.as<uint8_t>(), p->recSrc.as<uint32_t>(), p->recDst.as<uint32_t>(),
+                nRecLines, (uint32_t)addRecs, a.records.as<uint8_t>() + (p->endRec - lead), lead, status);
+            HIPCHK(hipGetLastError());
+        }
     }
     HIPCHK(hipEventRecord(p->ev[2], p->stream));
     if ((rc = fetch(p->stream, st, status))) return rc;
@@ -529,7 +611,7 @@ static int append_device(kasa_parser *p, uint64_t nBytes, int firstByte, int las
     if (!cut && hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess) p->msUpload += ms;       // (a span's upload and inflate are counted where they happen)
     if (hipEventElapsedTime(&ms, cut ? p->evz[1] : p->ev[1], p->ev[2]) == hipSuccess) p->msParse += ms;
     if (st != ~0ull) return refuse(p, (int)(st & 0xFF), st >> 8, parsable);         // (what was written lies behind the pool's end)
-    p->nReads += addReads; p->endBase += addBases; p->endName += addNames;
+    p->nReads += addReads; p->endBase += addBases; p->endName += addNames; p->endRec += addRecs;
     if (nReadsAdded) *nReadsAdded = addReads;
     return KASA_OK;
 }
@@ -655,7 +737,54 @@ static int take_impl(kasa_parser *p, kasa_ctx *c, uint64_t n)
     // the context copies the bases (the pool's memory is reused by the next append) and returns with its stream idle
     const int rc = upload_impl(c, a.bases.as<uint8_t>(), a.off.as<int64_t>() + p->head, (int64_t)n, nullptr, (int64_t)n, true, true);
     if (rc) return rc;
-    p->head += n; p->headBase = end; p->headName = nameEnd;
+    uint64_t recEnd = p->headRec;
+    if (p->keepRecords) {
+        // ... and the records with their offsets, rebased, on the context's stream (the pool's is idle)
+        if ((rc0 = fetch(p->stream, recEnd, a.recOff.as<uint64_t>() + p->head + n))) return rc0;
+        const uint64_t nr = recEnd - p->headRec;
+        if ((rc0 = c->fltRecords.reserve(nr + 64)) || (rc0 = c->fltRecOff.reserve((n + 1) * 8))) return rc0;
+        if (nr) HIPCHK(hipMemcpyAsync(c->fltRecords.p, a.records.as<char>() + p->headRec, nr, hipMemcpyDeviceToDevice, c->stream));
+        prs_rebase_kernel<uint64_t><<<blocks_for(n + 1, 256), 256, 0, c->stream>>>(a.recOff.as<uint64_t>() + p->head, c->fltRecOff.as<uint64_t>(), n + 1, p->headRec);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->fltHaveRecords = true; c->fltRecBytes = nr;
+    }
+    p->head += n; p->headBase = end; p->headName = nameEnd; p->headRec = recEnd;
+    return KASA_OK;
+}
+
+static int keep_records_impl(kasa_parser *p, int keep)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (p->nReads != p->head || p->carry)
+        return fail(KASA_E_STATE, "kasa_pool_keep_records: %llu reads are pooled and %llu bytes carried; the pool must be empty", (unsigned long long)(p->nReads - p->head), (unsigned long long)p->carry);
+    HIPCHK(hipSetDevice(p->device));
+    if (keep)
+        for (PoolArrays &a : p->arrays) {                                          // recOff[0] = 0
+            int rc = a.recOff.reserve(8);
+            if (rc) return rc;
+            HIPCHK(hipMemsetAsync(a.recOff.p, 0, 8, p->stream));
+        }
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->keepRecords = keep != 0; p->headRec = p->endRec = 0;
+    return KASA_OK;
+}
+
+static int fetch_records_impl(kasa_parser *p, uint64_t first, uint64_t n, uint64_t *recOff, char *records)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (!p->keepRecords) return fail(KASA_E_STATE, "kasa_pool_fetch_records: the pool keeps no records (kasa_pool_keep_records)");
+    const uint64_t pooled = p->nReads - p->head;
+    if (first > pooled || n > pooled - first)
+        return fail(KASA_E_ARG, "kasa_pool_fetch_records: reads [%llu, +%llu) outside the %llu pooled", (unsigned long long)first, (unsigned long long)n, (unsigned long long)pooled);
+    HIPCHK(hipSetDevice(p->device));
+    const PoolArrays &a = p->arrays[p->cur];
+    const uint64_t r0 = p->head + first;
+    uint64_t e[2] = {0, 0};
+    int rc;
+    if ((rc = fetch_async(p->stream, e[0], a.recOff.as<uint64_t>() + r0)) || (rc = fetch(p->stream, e[1], a.recOff.as<uint64_t>() + r0 + n))) return rc;
+    if (recOff) { HIPCHK(hipMemcpy(recOff, a.recOff.as<uint64_t>() + r0, (n + 1) * 8, hipMemcpyDeviceToHost)); for (uint64_t i = 0; i <= n; ++i) recOff[i] -= e[0]; }
+    if (records && e[1] > e[0]) HIPCHK(hipMemcpy(records, a.records.as<char>() + e[0], e[1] - e[0], hipMemcpyDeviceToHost));
     return KASA_OK;
 }
 
@@ -677,14 +806,19 @@ static void pair_offsets(const kasa_parser *p, const kasa_parser *q, uint64_t r1
     names = PairOffsets{a.nameOff.as<uint64_t>() + r1, b.nameOff.as<uint64_t>() + r2, e1[2], e2[2]};
 }
 
-static int pair_gather(const uint8_t *src1, const uint8_t *src2, const PairOffsets &d, uint64_t n, uint64_t total, uint8_t *out, hipStream_t stream)
+template <class Offsets>
+static int gather64(const uint8_t *src1, const uint8_t *src2, const Offsets &d, uint64_t nEntries, uint64_t total, uint8_t *out, hipStream_t stream)
 {
-    if (n == 0 || total == 0) return KASA_OK;
+    if (nEntries == 0 || total == 0) return KASA_OK;
     const uint64_t tiles = (total + TILE_BYTES - 1) / TILE_BYTES;
     if (tiles / WAVES >= 0x7FFFFFFFull) return fail(KASA_E_LIMIT, "kasa_pair: %llu bytes in one call", (unsigned long long)total);
-    pair_gather_kernel<<<blocks_for(tiles, WAVES), 64 * WAVES, 0, stream>>>(src1, src2, d, n, total, out);
+    pair_gather_kernel<Offsets><<<blocks_for(tiles, WAVES), 64 * WAVES, 0, stream>>>(src1, src2, d, nEntries, total, out);
     HIPCHK(hipGetLastError());
     return KASA_OK;
+}
+static int pair_gather(const uint8_t *src1, const uint8_t *src2, const PairOffsets &d, uint64_t n, uint64_t total, uint8_t *out, hipStream_t stream)
+{
+    return gather64(src1, src2, d, 2 * n, total, out, stream);
 }
 
 static int pair_fetch_impl(kasa_parser *p, kasa_parser *q, uint64_t first, uint64_t n, uint32_t *lengths, uint64_t *nameOff, char *names, int64_t *off, uint8_t *bases)
@@ -864,6 +998,13 @@ extern "C" int kasa_parse_fetch(kasa_parser *p, uint64_t first, uint64_t n, uint
 }
 
 extern "C" int kasa_parse_take(kasa_parser *p, kasa_ctx *ctx, uint64_t nReads) { KASA_GUARDED(kasa_parse_impl::take_impl(p, ctx, nReads)) }
+
+extern "C" int kasa_pool_keep_records(kasa_parser *p, int keep) { KASA_GUARDED(kasa_parse_impl::keep_records_impl(p, keep)) }
+
+extern "C" int kasa_pool_fetch_records(kasa_parser *p, uint64_t first, uint64_t n, uint64_t *recOff, char *records)
+{
+    KASA_GUARDED(kasa_parse_impl::fetch_records_impl(p, first, n, recOff, records))
+}
 
 extern "C" int kasa_pair_take(kasa_parser *first, kasa_parser *second, kasa_ctx *ctx, uint64_t nPairs) { KASA_GUARDED(kasa_parse_impl::pair_take_impl(first, second, ctx, nPairs)) }
 

@@ -217,7 +217,7 @@ static vector<uint64_t> loadFreq(const string &prefix, size_t nTaxa, int kHigh, 
 }
 
 // KASA_HOST_TIMING=1: where the host spends the time of "Time fastq" (seconds, summed over the file)
-struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, inflate = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, deflate = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
+struct HostTimers { double read = 0, cut = 0, parse = 0, merge = 0, uploadText = 0, inflate = 0, deviceParse = 0, form = 0, write = 0, upload = 0, compute = 0, rank = 0, text = 0, fetch = 0, deflate = 0, encode = 0, sort = 0, score = 0, coherence = 0, cohBegin = 0, cohDepth = 0, cohFinish = 0, filterSplit = 0, filterFetch = 0, filterWrite = 0; std::mutex mu; bool on = getenv("KASA_HOST_TIMING") != nullptr; };
 static HostTimers g_ht;
 static std::chrono::steady_clock::time_point g_t0 = std::chrono::steady_clock::now();
 static void mark(const char *what, uint64_t id = ~0ull)          // KASA_HOST_TIMING: a time line of the file's pipeline
@@ -743,6 +743,8 @@ struct Params {
     bool bgzfDynamic = false;                      // --bgzf-dynamic (implies --bgzf): device batches get a Huffman table of their own (KASA_BGZF_DYNAMIC); what the host writes stays zlib level 1
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
     bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
+    bool deviceFilter = false;                     // --device-filter (implies --device-parse, needs --filter): the two files of --filter are split on the device batch by batch (kasa_batch_filter)
+    bool deviceFilterOn = false;                   // ... and this file's input takes that path (identifyFile decides)
     bool devicePairs = false;                      // --device-pairs (implies --device-parse): paired-end input is parsed into two pools and paired on the device (kasa_pair_*)
 };
 
@@ -1220,6 +1222,7 @@ struct Batcher {
             pool.reset(new DevicePool());
             if (kasa_parse_create(poolDevice, (uint64_t)kLongSequence, &pool->ps)) throwLast();
             if (paired && kasa_parse_create(poolDevice, (uint64_t)kLongSequence, &pool->ps2)) throwLast();
+            if (p.deviceFilterOn && kasa_pool_keep_records(pool->ps, 1)) throwLast();      // --device-filter: the records stay with the reads
             devParse = true;
         }
         if (paired && devParse) {
@@ -1765,6 +1768,7 @@ struct OrderedOut {
     std::thread writer; std::mutex wmu; std::condition_variable wcv; std::deque<std::pair<off_t, Item>> wq; bool wStop = false; size_t wBusy = 0;
     std::exception_ptr wErr;
     bool abandoned = false;                                     // a batch failed: nothing more is placed, nobody waits for a place
+    double *writeTimer = &g_ht.write;                           // KASA_HOST_TIMING: where the writer's seconds go (--device-filter's files have their own entry)
     ~OrderedOut() { stopWriter(); if (fd >= 0) ::close(fd); }
     static void writeAt(int fd, const char *d, size_t n, off_t at)
     {
@@ -1800,7 +1804,7 @@ struct OrderedOut {
                 job = std::move(wq.front()); wq.pop_front(); ++wBusy;
             }
             try {
-                ScopedTimerMt tm(g_ht.write, g_ht.mu);
+                ScopedTimerMt tm(*writeTimer, g_ht.mu);
                 writeAt(fd, job.second.view, job.second.n, job.first);
                 job.second.done->set_value();
             } catch (...) { job.second.done->set_exception(std::current_exception()); std::lock_guard<std::mutex> lk(wmu); if (!wErr) wErr = std::current_exception(); }
@@ -1883,10 +1887,10 @@ struct WorkerBuffers {
     // writer; they are made when the worker starts, while the input is still being parsed (page-locking takes 0.2 s per GB)
     static constexpr unsigned TEXT_SLOTS = 10;
     PcieBuf<char> text[TEXT_SLOTS]; std::future<void> written[TEXT_SLOTS]; unsigned turn = 0;
-    size_t pieceBytes = (size_t)64 << 20;
+    static size_t pieceFromEnv() { const char *e = getenv("KASA_TEXT_PIECE"); return e ? std::max<size_t>(1, (size_t)atoll(e)) : (size_t)64 << 20; }   // tests force small pieces
+    size_t pieceBytes = pieceFromEnv();
     void prepareText()
     {
-        if (const char *e = getenv("KASA_TEXT_PIECE")) pieceBytes = std::max<size_t>(1, (size_t)atoll(e));   // tests force small pieces
         for (auto &t : text) if (t.capacity < pieceBytes) t.resize(pieceBytes);
     }
     PcieBuf<uint8_t> flags;
@@ -1908,11 +1912,72 @@ static void overPartitions(const IndexFiles &ixf, size_t nP, const std::function
     for (size_t j = 0; j < nP; ++j) if (rcs[j]) throw std::runtime_error(msgs[j]);
 }
 
-static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int ownerDev, const vector<kasa_ctx *> &partCtx, Batch &b, bool wantRows, double &tDevice, double &tText, WorkerBuffers &wb, OrderedOut &out)
+// --device-filter: the two files of --filter as two more ordered outputs.  Every batch's records are split on the device
+// (kasa_batch_filter) and each side's text -- BGZF members under --gzip -- leaves through the worker's page-locked pieces in
+// batch order, as the -q file does.  A batch whose reads did not come out of the pool (the host parser took over) cannot be
+// split: `rewrite` is set and filterReads writes both files anew when the input has ended.
+struct FilterOut {
+    OrderedOut side[2];                                         // 0: clean, 1: contaminants
+    bool on[2] = {false, false};
+    string name[2];
+    std::atomic<bool> rewrite{false};
+    unsigned sides() const { return (on[0] ? 1u : 0u) | (on[1] ? 2u : 0u); }
+    void open(const Params &p, bool fasta)                      // the names are filterReads' (Compare.hpp:2454-2455)
+    {
+        const string ext = string(fasta ? ".fasta" : ".fastq") + (p.gzipOut ? ".gz" : "");
+        const string *prefix[2] = {&p.filterClean, &p.filterCont};
+        for (int s = 0; s < 2; ++s) {
+            if (*prefix[s] == "_") continue;
+            name[s] = *prefix[s] + ext;
+            side[s].fd = ::open(name[s].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (side[s].fd < 0) throw std::runtime_error(string(s ? "Contaminants" : "Filtered") + " output files could not be opened for writing, did you use the correct path?");
+            side[s].writeTimer = &g_ht.filterWrite;
+            on[s] = true;
+        }
+    }
+    void skip(uint64_t batch) { for (int s = 0; s < 2; ++s) if (on[s]) side[s].begin(batch, 0); }
+    void abandon() { for (auto &o : side) o.abandon(); }
+    void close(bool gzip)                                       // everything is in the files; --gzip: BGZF's end-of-file block
+    {
+        for (int s = 0; s < 2; ++s) {
+            if (!on[s]) continue;
+            side[s].drainWriter(); side[s].stopWriter();
+            if (gzip) side[s].putEof();
+            ::close(side[s].fd); side[s].fd = -1;
+        }
+    }
+};
+
+static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int ownerDev, const vector<kasa_ctx *> &partCtx, Batch &b, bool wantRows, double &tDevice, double &tText, WorkerBuffers &wb, OrderedOut &out,
+                     FilterOut *flt = nullptr)
 {
     const auto tDev = std::chrono::steady_clock::now();
     auto secondsSince = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     const uint64_t nr = b.rs.size();
+    // --device-filter: this batch's records to the two files.  hostFlags: one byte per read, or NULL for the flags kasa_batch_text left on the device
+    auto filterOut = [&](const uint8_t *hostFlags) {
+        if (!flt) return;
+        if (!b.pool || flt->rewrite.load()) { if (nr) flt->rewrite.store(true); flt->skip(b.id); return; }   // (once the host has to write the files anew, nothing more goes into them)
+        uint64_t nBytes[2] = {0, 0}, nReads[2] = {0, 0};
+        {
+            ScopedTimerMt tm(g_ht.filterSplit, g_ht.mu);
+            if (p.gzipOut && p.bgzfDynamic && kasa_ctx_set_bgzf_code(ctx, KASA_BGZF_DYNAMIC)) throwLast();
+            if (kasa_batch_filter(ctx, hostFlags, flt->sides(), p.gzipOut ? 1 : 0, nBytes, nReads)) throwLast();
+        }
+        for (int s = 0; s < 2; ++s) {
+            if (!flt->on[s]) continue;
+            const size_t nPieces = (size_t)((nBytes[s] + wb.pieceBytes - 1) / wb.pieceBytes);
+            flt->side[s].begin(b.id, nPieces);
+            for (size_t i = 0; i < nPieces; ++i) {
+                const unsigned slot = wb.turn++ % WorkerBuffers::TEXT_SLOTS;
+                if (wb.written[slot].valid()) wb.written[slot].get();         // (the piece that was here is in its file)
+                const uint64_t at = (uint64_t)i * wb.pieceBytes, len = std::min<uint64_t>(wb.pieceBytes, nBytes[s] - at);
+                if (wb.text[slot].capacity < wb.pieceBytes) wb.text[slot].resize(wb.pieceBytes);
+                { ScopedTimerMt tm(g_ht.filterFetch, g_ht.mu); if (kasa_batch_filter_fetch_range(ctx, s, wb.text[slot].data(), at, len)) throwLast(); }
+                wb.written[slot] = flt->side[s].view(b.id, i, wb.text[slot].data(), (size_t)len);
+            }
+        }
+    };
     {
         ScopedTimerMt tm(g_ht.upload, g_ht.mu);
         if (b.pool) { std::lock_guard<std::mutex> lk(b.pool->mu); if (b.pool->ps2 ? kasa_pair_take(b.pool->ps, b.pool->ps2, ctx, nr) : kasa_parse_take(b.pool->ps, ctx, nr)) throwLast(); b.pool->outstanding -= nr; }
@@ -1967,7 +2032,7 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
         }
     }
     b.kmers = nk;
-    if (!wantRows) { tDevice += secondsSince(tDev); out.begin(b.id, 0); return; }
+    if (!wantRows) { tDevice += secondsSince(tDev); out.begin(b.id, 0); if (flt) flt->skip(b.id); return; }
     vector<float> coherence;                                     // --coherence (Compare::postProcess, Compare.hpp:3317-3321)
     if (p.coherence) {
         coherence.assign(nr, 0.f);
@@ -2062,6 +2127,7 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
                     wb.written[slot] = out.view(b.id, i, wb.text[slot].data(), (size_t)len);
                 }
                 if (p.filter) for (uint64_t r = 0; r < nr; ++r) if (wb.flags.data()[r]) b.flagged.push_back(b.firstRead + r);
+                filterOut(nullptr);
                 tDevice += secondsSince(tDev);
                 return;
             }
@@ -2134,6 +2200,11 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
     else { vector<std::thread> pool; for (unsigned t = 0; t < nt; ++t) pool.emplace_back(work, t); for (auto &th : pool) th.join(); }
     for (auto &e : err) if (e) std::rethrow_exception(e);
     for (auto &f : flagged) b.flagged.insert(b.flagged.end(), f.begin(), f.end());
+    if (flt) {                                                     // the rows were the host's: so are the flags
+        vector<uint8_t> hostFlags(nr, 0);
+        for (uint64_t id : b.flagged) hostFlags[(size_t)(id - b.firstRead)] = 1;
+        filterOut(hostFlags.data());
+    }
     tText += secondsSince(tTxt);
 }
 
@@ -2148,6 +2219,8 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     g_t0 = tStart; mark("file begins");
     const bool wantRows = !p.rtt.empty() || p.filter;
     const size_t nDev = devSlots.size();
+    const char *filterWhy = !p.deviceFilter ? nullptr : !p.input2.empty() ? "paired-end input" : p.coherence ? "--coherence" : (nDev > 1 || !ixf.spread.empty()) ? "more than one device slot" : nullptr;
+    p.deviceFilterOn = p.deviceFilter && p.filter && !filterWhy;
     vector<kasa_ctx *> ctx(nDev, nullptr);
     struct CtxGuard { vector<kasa_ctx *> &c; ~CtxGuard() { for (auto *x : c) kasa_ctx_destroy(x); } } guard{ctx};
     for (size_t d = 0; d < nDev; ++d)
@@ -2178,7 +2251,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         // stride of 64 KiB, and the allocator's sixteenth on top: a fixed amount, off the free memory first).  The stream
         // itself is at most the text and 31 bytes a block; like the text it is not counted per query, the fifth kept free is
         // its room, and a batch that outgrows it ends the run with the library's out-of-memory message in an ERROR: line.
-        const uint64_t bgzfScratch = p.bgzf ? (uint64_t)4096 * 65536 / 16 * 17 + (1u << 20) : 0;
+        const uint64_t bgzfScratch = (p.bgzf || (p.deviceFilterOn && p.gzipOut)) ? (uint64_t)4096 * 65536 / 16 * 17 + (1u << 20) : 0;
         auto lessScratch = [bgzfScratch](uint64_t freeBytes, uint64_t slots) { return freeBytes > slots * bgzfScratch ? freeBytes - slots * bgzfScratch : 0; };
         freeB = lessScratch(freeB, (uint64_t)std::count(p.devices.begin(), p.devices.end(), p.devices[(size_t)devSlots[0]]));
         const uint64_t per = kasa_batch_bytes_per_query(ctx[0]);
@@ -2205,6 +2278,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     }
     mark("contexts made");
     OrderedOut out;
+    std::unique_ptr<FilterOut> flt;                                    // --device-filter
     vector<WorkerBuffers> wbs(nDev);                                   // (after `out`: their destructors wait for its writer)
     // the page-locked text buffers are made while the first chunk is parsed
     std::thread textPrep;
@@ -2212,14 +2286,16 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     if (!p.rtt.empty() && !p.hostRank && !p.hostText) textPrep = std::thread([&wbs, &p] { try { for (size_t i = 0; i < wbs.size(); ++i) { (void)kasa_thread_device(p.devices[i]); wbs[i].prepareText(); } } catch (...) {} });   // (a fresh thread stands on device 0: the buffers are page-locked for the worker's device)   // (what is missing is made, or fails, when a worker needs it)
     // --device-parse: single-end input on one device slot; the other combinations keep the host parser and give the same bytes.
     // --device-pairs: the same, and paired-end input goes through two pools (kasa_pair_*)
+    // --device-filter: the same again, and the pool keeps the records; where it does not apply, --filter is the host's as before
     int poolDevice = -1;
     if (p.deviceParse) {
         const bool pairs = p.devicePairs && !p.input2.empty();
-        const char *why = (!p.input2.empty() && !pairs) ? "paired-end input" : p.filter ? "--filter writes the reads back from host memory" : p.coherence ? "--coherence"
+        const char *why = (!p.input2.empty() && !pairs) ? "paired-end input" : (p.filter && !p.deviceFilterOn) ? "--filter writes the reads back from host memory" : p.coherence ? "--coherence"
                           : (nDev > 1 || !ixf.spread.empty()) ? "more than one device slot" : nullptr;
         if (!why) poolDevice = p.devices[(size_t)devSlots[0]];
         else if (p.verbose) std::cout << "OUT: " << (pairs ? "--device-pairs" : "--device-parse") << ": the host parser is used (" << why << ")" << std::endl;
         if (why && p.deviceInflate && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << why << ")" << std::endl;
+        if (filterWhy && p.verbose) std::cout << "OUT: --device-filter: the host path is used (" << filterWhy << ")" << std::endl;
     }
     Batcher batcher(p, ixf, wantRows, maxKmersPerBatch, poolDevice);
     mark("first chunk parsed");
@@ -2250,6 +2326,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         else if (p.fmt == Params::Json) out.put("[\n");
     }
     if (!p.profile.empty() && !std::ofstream(p.profile)) throw std::runtime_error("Profile file couldn't be opened for writing!");
+    if (p.deviceFilterOn) { flt.reset(new FilterOut()); flt->open(p, batcher.reader && batcher.reader->fasta); }
 
     // queue of formed batches (bounded: one waiting per device) and results that leave in batch order
     std::mutex mu;
@@ -2283,7 +2360,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                     if (fair) cvWork.notify_all();
                 }
                 mark("device takes batch", b->id);
-                runBatch(p, ixf, ctx[d], p.devices[(size_t)devSlots[d]], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out);
+                runBatch(p, ixf, ctx[d], p.devices[(size_t)devSlots[d]], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out, flt.get());
                 mark("device done with batch", b->id);
                 totalKmers += b->kmers;
                 b->rs = ReadSet();                                   // the reads are done with
@@ -2294,7 +2371,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         } catch (...) {
             std::lock_guard<std::mutex> lk(mu);
             if (!failure) failure = std::current_exception();       // like Compare.hpp:1060-1067: parked, rethrown by the driver thread
-            out.abandon(); carry.abandon();
+            out.abandon(); carry.abandon(); if (flt) flt->abandon();
             cvDone.notify_all(); cvSpace.notify_all(); cvWork.notify_all();
         }
     };
@@ -2349,7 +2426,18 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     const uint64_t nReads = batcher.nextRead;
     mark("workers joined");
     if (!p.rtt.empty()) { out.drainWriter(); out.stopWriter(); mark("writer drained"); if (p.fmt == Params::Json) out.put("\n]"); if (p.bgzf) out.putEof(); ::close(out.fd); out.fd = -1; }
-    if (p.filter) filterReads(p, contaminants);
+    if (flt) {
+        // The files are complete -- unless the host parser had reads of this input (their records never were on the device), or
+        // no read was flagged: the reference then copies the input as it is, empty lines and a missing last line feed included
+        flt->close(p.gzipOut);
+        const char *rewriteWhy = flt->rewrite.load() ? (batcher.devParse ? "a batch did not come out of the pool" : "the host parser took over")
+                                 : (contaminants.empty() && flt->on[0]) ? "no read was flagged: the input is copied as it is" : nullptr;
+        if (rewriteWhy) {
+            if (p.verbose) std::cout << "OUT: --device-filter: the files are written by the host (" << rewriteWhy << ")" << std::endl;
+            filterReads(p, contaminants);
+        }
+        if (p.verbose && g_ht.on) std::cout << "OUT: host timing: filter split " << g_ht.filterSplit << " s, filter fetch " << g_ht.filterFetch << " s, filter write " << g_ht.filterWrite << " s" << std::endl;
+    } else if (p.filter) filterReads(p, contaminants);
     // profile: one RCCL all-reduce over the devices' tables, then device 0's copy
     if (!ixf.spread.empty()) {
         // --partition-devices: no communicator (ncclCommInitAll refuses a device named twice, and integer tables need no
@@ -2492,6 +2580,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "BgzfDynamic") flag("--bgzf-dynamic", val);
         else if (key == "DeviceParse") flag("--device-parse", val);                  // ours: the reference has no device
         else if (key == "DevicePairs") flag("--device-pairs", val);
+        else if (key == "DeviceFilter") flag("--device-filter", val);
         else if (key == "DeviceInflate") flag("--device-inflate", val);
     }
     vector<string> out = {exe, mode};
@@ -3337,6 +3426,7 @@ static int run(int argc, char **argv)
         else if (s == "--device-parse") p.deviceParse = true;
         else if (s == "--device-inflate") p.deviceInflate = p.deviceParse = true;
         else if (s == "--device-pairs") p.devicePairs = p.deviceParse = true;
+        else if (s == "--device-filter") p.deviceFilter = p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
         else if (s == "--errorThreshold") p.errorThreshold = std::stof(next());
@@ -3352,6 +3442,7 @@ static int run(int argc, char **argv)
     }
     if (p.partitionDevices && p.devicesGiven) throw std::runtime_error("--partition-devices cannot be combined with --device or --devices: its slots are the devices of the run");
     if (p.bgzf && p.rtt.empty()) throw std::runtime_error("--bgzf compresses the per-read file: it needs -q <file>");
+    if (p.deviceFilter && !p.filter) throw std::runtime_error("--device-filter splits the files of --filter: it needs --filter <clean> <contaminants>");
     if (frameFlags >= 2) throw std::runtime_error("You'll have to decide between using one, three, or six frames. Currently, more than one option was chosen. Please check your parameters!"); // main.cpp:618-620
     std::ifstream info(p.index + "_info.txt");
     if (!info) throw std::runtime_error("Info file for this index can not be found!");
