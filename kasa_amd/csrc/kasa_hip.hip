@@ -2080,74 +2080,131 @@ __global__ __launch_bounds__(256) void bucket_rank32_kernel(const uint64_t *__re
     }
 }
 
-// 64-bit keys with up to 40 bits below the bucket's (SORT_TOP = 32: 28): the same with one 64-bit word per query -- those bits
-// above its position in the window -- so that members still compare like (key, position) with ONE compare, two members
-// per step.
+// 64-bit keys whose bits below the bucket's fit a 32-bit word (SORT_TOP = 32: 28 of them): every pair is read from global
+// memory ONCE.  A wavefront owns RANK_TILE / 256 consecutive rows of 64 queries and keeps their keys and payloads in
+// registers from the staging to the stores; LDS holds the low key bits of the window (four members per 16-byte read), one
+// word of "first of its bucket" flags per row, and per row the nearest flag in the rows before and in the rows after it.
+//  - A query's predecessor is its neighbouring lane; a row's first lane takes the last key of the row before (the same
+//    wavefront's registers, or one wavefront-uniform load for the wavefront's first row and for its halo row).
+//  - The bucket's ends come in closed form: the nearest flag below / above the lane in the row's own flag word (the same for
+//    all lanes: scalar registers), else the row's entry in the two tables.  No flag on the left: the bucket began before
+//    the window; none on the right: it leaves the window, unless the window ends with the batch (position n carries a
+//    flag when it is staged).  Both take the scan over global memory, as in the kernels above.
+//  - Members before me count when their low bits are not larger, members after me when they are smaller: whole 16-byte
+//    groups are compared with mine + 1 before my own group and with mine from there on, the two ragged groups at the
+//    bucket's ends with a range check per member, and the ties before me in my own group are added last.
 __global__ __launch_bounds__(256) void bucket_rank64_kernel(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin, uint64_t *__restrict__ kout,
                                                             uint32_t *__restrict__ vout, uint32_t n, int shift, uint32_t *__restrict__ big,
                                                             uint32_t *__restrict__ bigHead)
 {
-    constexpr uint32_t WIN = RANK_TILE + 2 * RANK_HALO, POS_BITS = 12;
-    static_assert(WIN % 256 == 0 && WIN <= (1u << POS_BITS), "window positions fit the low bits of the LDS word; whole wavefronts stage it");
-    __shared__ __attribute__((aligned(16))) uint64_t sW[WIN + 2];
-    __shared__ uint64_t sHead[WIN / 64];
+    constexpr uint32_t WIN = RANK_TILE + 2 * RANK_HALO, ROWS = WIN / 64, PER = RANK_TILE / 256, NONE = ~0u;
+    static_assert(RANK_TILE % 256 == 0 && RANK_HALO == 128, "four wavefronts share the tile's rows and take one of the four halo rows each");
+    __shared__ __attribute__((aligned(16))) uint32_t sLow[WIN];
+    __shared__ uint64_t sHead[ROWS];
+    __shared__ uint32_t sBefore[ROWS], sAfter[ROWS];
     const uint32_t base = blockIdx.x * RANK_TILE;
-    const uint32_t lo = base >= RANK_HALO ? base - RANK_HALO : 0u;
-    const uint32_t hi = (uint64_t)base + RANK_TILE + RANK_HALO < (uint64_t)n ? base + RANK_TILE + RANK_HALO : n;
-    const uint32_t win = hi - lo;
-    const uint64_t lowMask = (1ull << shift) - 1ull;                      // (shift + POS_BITS <= 52: checked by the caller)
-    for (uint32_t x = threadIdx.x; x < WIN; x += 256u) {
-        bool head = false;
-        if (x < win) {
-            const uint32_t q = lo + x;
-            const uint64_t k = kin[q];
-            head = q == 0u || (kin[q - 1u] >> shift) != (k >> shift);
-            sW[x] = ((k & lowMask) << POS_BITS) | x;
-        }
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t origin = (int64_t)base - RANK_HALO, end = (int64_t)n;    // window position x is query origin + x
+    const uint32_t lowMask = (uint32_t)((1ull << shift) - 1ull);           // (shift < 32: checked by the caller)
+    const uint32_t row0 = RANK_HALO / 64u + wave * PER;                    // my wavefront's first row of the tile ...
+    const uint32_t rowH = wave < 2u ? wave : RANK_TILE / 64u + wave;       // ... and its row of the halos
+
+    uint64_t k[PER], kH = 0ull, before0 = 0ull, beforeH = 0ull;
+    uint32_t v[PER];
+#pragma unroll
+    for (uint32_t j = 0; j < PER; ++j) {
+        const int64_t q = origin + (row0 + j) * 64u + lane;
+        const bool in = q < end;
+        k[j] = in ? kin[q] : 0ull;
+        v[j] = in ? vin[q] : 0u;
+    }
+    {
+        const int64_t q = origin + rowH * 64u + lane, b0 = origin + row0 * 64u - 1, bH = origin + rowH * 64u - 1;
+        if (q >= 0 && q < end) kH = kin[q];
+        if (b0 >= 0 && b0 < end) before0 = kin[b0];                        // (the same address in every lane)
+        if (bH >= 0 && bH < end) beforeH = kin[bH];
+    }
+    // one row: low bits to LDS, the row's flags to sHead; returns the row's last key for the row after it
+    auto stage = [&](uint32_t row, uint64_t key, uint64_t before) -> uint64_t {
+        const int64_t q = origin + row * 64u + lane;
+        const bool in = q >= 0 && q < end;
+        const uint32_t pl = (uint32_t)__shfl_up((int)(uint32_t)key, 1), ph = (uint32_t)__shfl_up((int)(uint32_t)(key >> 32), 1);
+        const uint64_t prev = lane == 0u ? before : ((uint64_t)ph << 32) | pl;
+        const bool head = in ? (q == 0 || ((prev ^ key) >> shift) != 0ull) : q == end;
+        if (in) sLow[row * 64u + lane] = (uint32_t)key & lowMask;
         const uint64_t m = __ballot(head);
-        if ((threadIdx.x & 63u) == 0u) sHead[x >> 6] = m;
+        if (lane == 0u) sHead[row] = m;
+        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, 63);
+    };
+    stage(rowH, kH, beforeH);
+#pragma unroll
+    for (uint32_t j = 0; j < PER; ++j) before0 = stage(row0 + j, k[j], before0);
+    __syncthreads();
+    if (wave == 0u) {                                                      // the nearest flag in the rows before a row ...
+        for (uint32_t row = lane; row < ROWS; row += 64u) {
+            uint32_t at = NONE;
+            for (uint32_t m = row; m > 0u && at == NONE;) { const uint64_t w = sHead[--m]; if (w != 0ull) at = m * 64u + 63u - (uint32_t)__clzll((long long)w); }
+            sBefore[row] = at;
+        }
+    } else if (wave == 1u) {                                               // ... and in the rows after it
+        for (uint32_t row = lane; row < ROWS; row += 64u) {
+            uint32_t at = NONE;
+            for (uint32_t m = row + 1u; m < ROWS && at == NONE; ++m) { const uint64_t w = sHead[m]; if (w != 0ull) at = m * 64u + (uint32_t)__ffsll((unsigned long long)w) - 1u; }
+            sAfter[row] = at;
+        }
     }
     __syncthreads();
-    const uint32_t lastWord = (win - 1u) >> 6;
-    for (uint32_t e = threadIdx.x; e < RANK_TILE; e += 256u) {
-        const uint32_t p = base + e;
-        if (p >= n) break;
-        const uint32_t i0 = p - lo, bit = i0 & 63u;
-        const uint64_t my = sW[i0];
-        bool edge = false;
-        uint32_t m = i0 >> 6;
-        uint64_t w = sHead[m] & (~0ull >> (63u - bit));                   // the bucket's first member: the last flag at or before me
-        while (w == 0ull && m > 0u) w = sHead[--m];
-        uint32_t hs = 0;
-        if (w == 0ull) edge = true; else hs = m * 64u + 63u - (uint32_t)__clzll((long long)w);
-        m = i0 >> 6;
-        w = sHead[m] & ((~0ull << bit) << 1);                             // its end: the first flag after me
-        while (w == 0ull && m < lastWord) w = sHead[++m];
-        uint32_t he = win;
-        if (w == 0ull) edge = edge || (hi < n); else he = m * 64u + (uint32_t)__ffsll((unsigned long long)w) - 1u;
+
+    const bool cut = origin + (int64_t)WIN < end;                          // the batch goes on behind the window
+    const uint32_t winEnd = cut ? WIN : (uint32_t)(end - origin);
+    const uint64_t upToMe = ~0ull >> (63u - lane), aboveMe = (~0ull << lane) << 1;
+    const uint4 *sLow4 = reinterpret_cast<const uint4 *>(sLow);
+#pragma unroll
+    for (uint32_t j = 0; j < PER; ++j) {
+        const uint32_t row = row0 + j, i0 = row * 64u + lane;
+        const int64_t q = origin + i0;
+        if (q >= end) break;                                               // (the rows after it are past the batch as well)
+        const uint32_t p = (uint32_t)q;
+        const uint64_t key = k[j], hw = sHead[row];
+        const uint64_t heads = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(hw >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)hw);
+        const uint32_t farBefore = (uint32_t)__builtin_amdgcn_readfirstlane((int)sBefore[row]), farAfter = (uint32_t)__builtin_amdgcn_readfirstlane((int)sAfter[row]);
+        const uint64_t below = heads & upToMe, above = heads & aboveMe;
+        const uint32_t hs = below != 0ull ? row * 64u + 63u - (uint32_t)__clzll((long long)below) : farBefore;          // the bucket's first member: the last flag at or before me
+        const uint32_t he = above != 0ull ? row * 64u + (uint32_t)__ffsll((unsigned long long)above) - 1u : farAfter != NONE ? farAfter : winEnd;   // its end: the first flag after me
+        const bool edge = hs == NONE || (above == 0ull && farAfter == NONE && cut);
         uint32_t L = i0 - hs, members = he - hs, rank = 0;
         if (!edge && members <= SORT_BUCKET_LIMIT) {
-            uint32_t j = hs;
-            if (j & 1u) { rank += sW[j] < my ? 1u : 0u; ++j; }            // (pairs of words are read from even positions: 16-byte LDS reads)
-            for (; j + 1u < he; j += 2u) {
-                const ulonglong2 ab = *reinterpret_cast<const ulonglong2 *>(&sW[j]);
-                rank += (ab.x < my ? 1u : 0u) + (ab.y < my ? 1u : 0u);
+            const uint32_t my = (uint32_t)key & lowMask, up = my + 1u;     // (my + 1 does not wrap: fewer than 32 low bits)
+            const uint32_t qa = hs >> 2, qm = i0 >> 2, qb = (he - 1u) >> 2;
+            auto ragged = [&](uint32_t g, uint32_t limit) -> uint32_t {
+                const uint4 t = sLow4[g];
+                const uint32_t d = g * 4u - hs;
+                return ((d < members && t.x < limit) ? 1u : 0u) + ((d + 1u < members && t.y < limit) ? 1u : 0u) +
+                       ((d + 2u < members && t.z < limit) ? 1u : 0u) + ((d + 3u < members && t.w < limit) ? 1u : 0u);
+            };
+            rank = ragged(qa, qa < qm ? up : my) + ragged(qb, qb != qa ? my : 0u);
+#pragma unroll 1
+            for (uint32_t g = qa + 1u; g < qb; ++g) {                      // (three such groups in the average query's bucket)
+                const uint4 t = sLow4[g];
+                const uint32_t limit = g < qm ? up : my;
+                rank += (t.x < limit ? 1u : 0u) + (t.y < limit ? 1u : 0u) + (t.z < limit ? 1u : 0u) + (t.w < limit ? 1u : 0u);
             }
-            if (j < he) rank += sW[j] < my ? 1u : 0u;
+            const uint4 t = sLow4[qm];                                     // equal members before me in my own group
+            const uint32_t c = i0 & 3u, f = qm * 4u;
+            rank += ((c > 0u && f >= hs && t.x == my) ? 1u : 0u) + ((c > 1u && f + 1u >= hs && t.y == my) ? 1u : 0u) + ((c > 2u && f + 2u >= hs && t.z == my) ? 1u : 0u);
         }
-        const uint64_t k = kin[p];
-        if (edge) {                                                       // the bucket leaves the window: the whole scan again, from global memory
-            const uint64_t top = k >> shift;
+        if (edge) {                                                        // the bucket leaves the window: the whole scan again, from global memory
+            const uint64_t top = key >> shift;
             uint32_t R = 0;
             rank = 0; L = 0;
-            for (uint32_t q = p; q > 0 && L < SORT_BUCKET_LIMIT;) { --q; const uint64_t o = kin[q]; if ((o >> shift) != top) break; ++L; rank += (o <= k) ? 1u : 0u; }
-            for (uint32_t q = p + 1; q < n && R < SORT_BUCKET_LIMIT; ++q) { const uint64_t o = kin[q]; if ((o >> shift) != top) break; ++R; rank += (o < k) ? 1u : 0u; }
+            for (uint32_t o = p; o > 0 && L < SORT_BUCKET_LIMIT;) { --o; const uint64_t other = kin[o]; if ((other >> shift) != top) break; ++L; rank += (other <= key) ? 1u : 0u; }
+            for (uint32_t o = p + 1; o < n && R < SORT_BUCKET_LIMIT; ++o) { const uint64_t other = kin[o]; if ((other >> shift) != top) break; ++R; rank += (other < key) ? 1u : 0u; }
             members = L + R + 1u;
         }
         if (members > SORT_BUCKET_LIMIT) {
-            kout[p] = k; vout[p] = vin[p];
+            kout[p] = key; vout[p] = v[j];
             if (L == 0u) { const uint32_t at = atomicAdd(big, 1u); if (at < SORT_BIG_CAP) bigHead[at] = p; }
-        } else { const uint32_t at = p - L + rank; kout[at] = k; vout[at] = vin[p]; }
+        } else { const uint32_t at = p - L + rank; kout[at] = key; vout[at] = v[j]; }
     }
 }
 
@@ -2208,7 +2265,7 @@ static int sort_and_range_impl(kasa_ctx *c, int unique)
             HIPCHK(hipMemsetAsync(&c->ctr()->sortBig, 0, sizeof(LongBuckets), c->stream));
             Span rank(c, c->kernels[KASA_KERNEL_BUCKET_RANK]); if ((rc = rank.begin())) return rc;
             static_assert(KeyTraits<uint64_t>::BITS - SORT_TOP_OLD + 12 <= 32, "bucket_rank32_kernel: low key bits and window position share a word");
-            static_assert(KeyTraits<uint64_t>::BITS - SORT_TOP + 12 <= 52, "bucket_rank64_kernel: low key bits and window position share a word");
+            static_assert(KeyTraits<uint64_t>::BITS - SORT_TOP < 32, "bucket_rank64_kernel: the low key bits are a 32-bit word, and that word + 1 does not wrap");
             if (sizeof(Key) == 8 && top != SORT_TOP_OLD && !(c->debugFlags & 4194304))   // (test tap 4194304: the kernel for any key width)
                 bucket_rank64_kernel<<<blocks_for(nQ, RANK_TILE), 256, 0, c->stream>>>(c->qKmerB.as<uint64_t>(), c->qReadB.as<uint32_t>(), c->qKmerA.as<uint64_t>(),
                                                                                       c->qReadA.as<uint32_t>(), (uint32_t)nQ, (int)(BITS - top), big, bigHead);
