@@ -445,7 +445,7 @@ enum {
     KASA_KERNEL_LOOKUP = 0,       /* lookup_tile_kernel: the sorted-index lookup */
     KASA_KERNEL_GROUP = 1,        /* group_kernel: flush order + taxon segments, one record per query */
     KASA_KERNEL_SCORE_MAIN = 2,   /* score_main_kernel: the float chains of a read's register taxa */
-    KASA_KERNEL_SCORE_OTHER = 3,  /* score_other_kernel: staging records of all other taxa */
+    KASA_KERNEL_SCORE_OTHER = 3,  /* score_other_flat_kernel / score_other_flat16_kernel (debug bit 5: score_other_kernel): staging records of all other taxa */
     KASA_KERNEL_ROW_MERGE = 4,    /* row_merge_*: staging rows -> final {taxon, score} rows + profile keys */
     KASA_KERNEL_SCORE_GENERAL = 5,/* flush_positions_kernel + score_kernel (all its passes): the reads the fast kernels hand over */
     KASA_KERNEL_PROFILE_TABLES = 6,/* profile_(group_)table_kernel + the sort and reduce of the keys it leaves over */
@@ -565,8 +565,8 @@ int kasa_ctx_record_placement(kasa_ctx *ctx, uint32_t *candidates, float *keptRa
  * score kernel, bit 1 = per-query index search instead of the streamed-tile lookup, bit 2 = sorting row
  * merge instead of the bitmap one, bit 3 = the encoder does not rank the k-mers of a read (slots come from
  * a stable sort by read id, as for long or paired reads), bit 4 = the profile keys are sorted and reduced even
- * when the LDS counting table would fit, bit 5 = score_other_kernel (one lane per query) instead of
- * score_other_flat_kernel (work items = segments) for 32-byte records, bit 6 = the library's radix sort over all
+ * when the LDS counting table would fit, bit 5 = score_other_kernel (one lane per query, either record width) instead of
+ * score_other_flat_kernel / score_other_flat16_kernel (work items = segments), bit 6 = the library's radix sort over all
  * key bits instead of 4 (5) passes + bucket_rank_kernel, bit 7 = long sort buckets are not sorted one by one but by the
  * library over all bits (the path for inputs with too many or too long ones), bit 8 = kasa_batch_rank leaves reads with
  * tied hits to the host instead of ranking them with std::sort's order on the device, bit 9 = the library's radix passes

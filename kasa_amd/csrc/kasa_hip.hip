@@ -396,6 +396,16 @@ __device__ __forceinline__ void wave_seg_incl_sum(uint32_t &v, bool &f)
 #undef KASA_SEG_STEP
     f = fl != 0u;
 }
+// lanes 0 .. lane of a wavefront, as a ballot mask
+__device__ __forceinline__ unsigned long long lanes_up_to(int lane) { return lane == 63 ? ~0ull : ((2ull << lane) - 1ull); }
+
+// the last i < n with off[i] <= x (off ascending, off[0] <= x): the read of a slot or element, from the reads' offsets
+__device__ __forceinline__ uint32_t last_at_or_before(const uint64_t *__restrict__ off, uint32_t n, uint64_t x)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
 
 // ------------------------------------------------------------------------------------------------
 // index
@@ -1920,10 +1930,7 @@ __global__ void slot_to_read_kernel(const uint32_t *__restrict__ slot, uint32_t 
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t s = slot[i];
-    uint32_t lo = 0, hi = nReads;                                  // last r with kmerOff[r] <= s
-    while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (kmerOff[mid] <= s) lo = mid; else hi = mid; }
-    read[i] = lo;
+    read[i] = last_at_or_before(kmerOff, nReads, slot[i]);
 }
 
 template <class Key> static int lookup_part(kasa_ctx *c);
@@ -4664,6 +4671,156 @@ template <int RW> __device__ __forceinline__ uint32_t seg_records(uint32_t level
     return (RW == 8 && pc <= 2u && !saturated) ? (pc ? 1u : 0u) : pc;
 }
 
+// ---- the steps the score_other* kernels (and record_stats_kernel) share: each rule of the stage is stated here, once
+
+// The read of a slot, and that read's first slot: reads are mostly equally long, so the proportional guess is right; else search.
+__device__ __forceinline__ uint32_t read_of_slot(const ScoreArgs &A, uint32_t slot, uint64_t &readStart)
+{
+    uint32_t r = (uint32_t)((double)slot * ((double)A.nReads / (double)A.nQ));
+    if (r >= A.nReads) r = A.nReads - 1u;
+    readStart = A.kmerOff[r];
+    if (!(readStart <= slot && slot < A.kmerOff[r + 1])) {
+        r = last_at_or_before(A.kmerOff, A.nReads, slot);
+        readStart = A.kmerOff[r];
+    }
+    return r;
+}
+
+// What a lane of these kernels knows of its slot: the record's words, the read and what score_main_kernel left for it, and
+// the decoded query -- without depth, segments or split mark when it is dead (no match, no read of the fast path, or one of
+// the slots past nQ that fill the last wavefront for the prefix sums).
+template <int RW> struct OtherSlot {
+    uint4 cur[RW / 4];
+    uint32_t r;
+    uint64_t readStart;
+    MainOut mo;
+    bool inRange, live;
+    QueryRec<RW> Q;
+    // BYQS: the record's cell by shift (ScoreArgs::recQS; wide records fill theirs), else by the words per cell (recCW)
+    template <bool BYQS> __device__ __forceinline__ void load(const ScoreArgs &A, uint32_t slot)
+    {
+        inRange = slot < A.nQ;
+#pragma unroll
+        for (int i = 0; i < RW / 4; ++i) cur[i] = make_uint4(0, 0, 0, 0);
+        r = 0; readStart = 0;
+        uint4 m4 = make_uint4(0, 0, 0, 0);
+        if (inRange) {
+            const size_t at = BYQS ? (size_t)slot << (RW == 16 ? 2u : A.recQS) : (size_t)slot * (A.recCW / 4u);
+#pragma unroll
+            for (int i = 0; i < RW / 4; ++i) cur[i] = reinterpret_cast<const uint4 *>(A.rec)[at + i];
+            r = read_of_slot(A, slot, readStart);
+            m4 = reinterpret_cast<const uint4 *>(A.mainOut)[r];
+        }
+        mo = MainOut{m4.x, m4.y, m4.z, m4.w};
+        live = inRange && mo.nOther != 0u && (cur[0].z & 31u) != 0u;      // a matched query of a read the fast path kept
+        Q.decode_regs(cur, A.pool);
+        if (!live) { Q.d = 0; Q.nInl = 0; Q.nMore = 0; Q.split = 0; Q.nseg = 0; }
+    }
+    __device__ __forceinline__ int events(int kLow) const { return Q.d ? Q.d - kLow + 1 : 0; }   // events of the query's flush order
+    __device__ __forceinline__ bool head(uint32_t slot) const { return inRange && (uint64_t)slot == readStart; }   // its read's first slot
+    // Where the records of this wavefront's part of the read go on: behind `otherAt` when the read starts inside the wavefront
+    // (`started`: at or before this lane), else after the count score_main_kernel left at the wavefront's first slot.
+    __device__ __forceinline__ uint32_t row_at(const ScoreArgs &A, uint32_t slot, bool started) const { return mo.otherAt + (started ? 0u : A.otherOff64[slot >> 6]); }
+};
+
+// narrow records: the levels with |T| > 4 (CNT_FIELDS), one bit per level -- there the register taxa leave profile records
+// instead of counting in LDS (score_main_kernel)
+__device__ __forceinline__ uint32_t big_levels8(uint32_t nlev)
+{
+    const uint32_t f = (nlev >> 2) & ((nlev >> 1) | nlev) & 0x249249u;    // field >= 5, one bit per 3-bit field
+    return (f & 1u) | ((f >> 2) & 2u) | ((f >> 4) & 4u) | ((f >> 6) & 8u) | ((f >> 8) & 16u) | ((f >> 10) & 32u) | ((f >> 12) & 64u) | ((f >> 14) & 128u);
+}
+
+// narrow records: position of level lv in a query's flush order (three bits per event: the field that equals lv, found
+// without a loop; fields past the nEv events are masked out, with eight events there are none)
+__device__ __forceinline__ int order_pos8(uint32_t order, int nEv, int lv)
+{
+    const uint32_t x = (order ^ ((uint32_t)lv * 0x249249u)) | (nEv < 8 ? (0xFFFFFFFFu << (3 * nEv)) : 0u);
+    const uint32_t z = ~(x | (x >> 1) | (x >> 2)) & 0x249249u;             // bit 3 i set iff field i is zero
+    return (__ffs((int)z) - 1) / 3;
+}
+
+// Levels at which a segment leaves records: all of them for another taxon; for a register taxon those with a large |T|
+// (bigLv), and none where the profile is built from the groups (GpOf).
+template <int RW> __device__ __forceinline__ uint32_t emit_mask(uint32_t sq, uint32_t tax0, uint32_t tax1, uint32_t bigLv, int kHigh)
+{
+    const uint32_t t = sq & SEG_TAX_MASK, m = seg_level_mask(sq, kHigh);
+    return (t != tax0 && t != tax1) ? m : (GpOf<RW>::v ? 0u : (m & bigLv));
+}
+
+// The event record of taxon t at level lv, |T| = n.  A register taxon's is a profile record (its score is already in the
+// row), and so is everybody's when no per-read scores are wanted.
+template <bool PERREAD> __device__ __forceinline__ uint2 event_record(uint32_t t, bool isMain, int lv, uint32_t n)
+{
+    return make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | ((isMain || !PERREAD) ? RK_PROFILE : 0u), (n << 16) | 1u);
+}
+
+// A split query (REC_SPLIT): a taxon may own several segments, and its records must follow the query's flush order across
+// them -- so they leave event by event, one per (segment, level).  put(segment, level) takes each in that order.
+template <int RW, class Put>
+__device__ __forceinline__ void split_walk(const QueryRec<RW> &Q, int nEv, uint32_t tax0, uint32_t tax1, uint32_t bigLv, int kHigh, Put put)
+{
+    typedef RecTraits<RW> RT;
+    typename std::conditional<RW == 8, uint32_t, unsigned __int128>::type o = Q.order;
+    for (int ev = 0; ev < nEv; ++ev, o >>= RT::OBITS) {
+        const int lv = (int)((uint32_t)o & ((1u << RT::OBITS) - 1u));
+#pragma unroll
+        for (int q = 0; q < RT::INL; ++q) if ((uint32_t)q < Q.nInl && ((emit_mask<RW>(Q.sg[q], tax0, tax1, bigLv, kHigh) >> lv) & 1u)) put(Q.sg[q], lv);
+        for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = Q.more[q]; if ((emit_mask<RW>(sq, tax0, tax1, bigLv, kHigh) >> lv) & 1u) put(sq, lv); }
+    }
+}
+// How many records split_walk puts, for the flat kernels, which place a query's records before they write them.  Not the
+// walk with a put that only counts: that keeps the masks of all inline segments in registers across the pool loop of every
+// event, six or seven more than score_other_flat_kernel's 64 hold (measured: 28-32 bytes of scratch per lane).
+template <int RW> __device__ __forceinline__ uint32_t split_records(const QueryRec<RW> &Q, uint32_t tax0, uint32_t tax1, uint32_t bigLv, int kHigh)
+{
+    uint32_t n = 0;
+#pragma unroll
+    for (int q = 0; q < RecTraits<RW>::INL; ++q) if ((uint32_t)q < Q.nInl) n += (uint32_t)__popc(emit_mask<RW>(Q.sg[q], tax0, tax1, bigLv, kHigh));
+    for (uint32_t q = 0; q < Q.nMore; ++q) n += (uint32_t)__popc(emit_mask<RW>(Q.more[q], tax0, tax1, bigLv, kHigh));
+    return n;
+}
+
+// ---- the flat kernels' placement: the items of a wavefront's 64 queries, 64 per round
+// exclusive prefix sums of the queries' item counts (incl: the inclusive ones), and their total behind them
+__device__ __forceinline__ void item_bases(uint32_t (&sBase)[65], int lane, uint32_t incl, uint32_t n)
+{
+    sBase[lane] = incl - n;
+    if (lane == 63) sBase[64] = incl;
+}
+// owner of item i: the last query whose items start at or before i
+__device__ __forceinline__ uint32_t item_owner(const uint32_t (&sBase)[65], uint32_t i)
+{
+    uint32_t own = 0;
+#pragma unroll
+    for (int step = 32; step; step >>= 1) if (sBase[own + step] <= i) own += step;
+    return own;
+}
+// An item knows how many records it yields; a segmented prefix sum over the items -- restarting where a new read begins --
+// gives each its place in the read's row.  The count carries over from round to round.
+struct ItemPlacer {
+    unsigned long long H;                                               // the queries (lanes) at which a read begins
+    uint32_t carry;
+    int prevOwnCarry;
+    // returns `started`: a read starts at or before this lane, inside the wavefront
+    __device__ __forceinline__ bool begin(bool head, int lane) { H = __ballot(head); carry = 0; prevOwnCarry = -1; return (H & lanes_up_to(lane)) != 0ull; }
+    // records before this lane's item (c records, of query `own`; an idle lane: act = false, own = 63, c = 0) since its
+    // read's row_at
+    __device__ __forceinline__ uint32_t place(uint32_t own, bool act, uint32_t c)
+    {
+        // does a read begin between the previous item's query and this one's?  Then the count restarts here.
+        const int prevOwn = lane_before((int)own, prevOwnCarry);
+        const unsigned long long toPrev = prevOwn < 0 ? 0ull : lanes_up_to(prevOwn);
+        bool f = act && (H & lanes_up_to((int)own) & ~toPrev) != 0ull;
+        uint32_t v = c;
+        wave_seg_incl_sum(v, f);
+        const uint32_t before = v - c + (f ? 0u : carry);
+        carry = lane_value<63>(v) + ((int)lane_value<63>((uint32_t)f) ? 0u : carry);
+        prevOwnCarry = (int)lane_value<63>((uint32_t)own);
+        return before;
+    }
+};
+
 // FB: bits of a hit counter.  16 by default; 8 when no read of the batch has more than 255 k-mers (narrow records): the LDS
 // counters are what limits the resident wavefronts of this kernel, and it runs faster the more there are (26 ms at 16 per
 // CU, 40 at 8).
@@ -4986,13 +5143,10 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
 {
     typedef RecTraits<RW> RT;
     constexpr int OB = RT::OBITS;
-    constexpr bool GP = GpOf<RW>::v;
     constexpr uint32_t CNT_FIELDS = RW == 8 ? 4u : 2u;
     typedef typename std::conditional<RW == 8, uint32_t, unsigned __int128>::type Order;
     const int lane = threadIdx.x & 63;
-    const uint32_t kindOther = PERREAD ? 0u : RK_PROFILE;
     const uint32_t stride = gridDim.x * 256u;
-    const double readsPerSlot = (double)A.nReads / (double)A.nQ;
     const uint32_t nQup = (A.nQ + 63u) & ~63u;                             // whole wavefronts take part in the prefix sums
     // A wavefront's records leave through LDS: a lane's 8-byte stores would reach the row as ~50 partial-line write requests
     // per wavefront (measured: 4/5 of the kernel); staged, consecutive lanes write consecutive records.
@@ -5002,35 +5156,13 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
     __shared__ uint32_t sLvN[RW == 16 ? (RT::LEVELS + 3) / 2 : 1][256];  // wide records: |T_k| of this thread's query (QueryRec::tab), two levels per word
     const int wv = threadIdx.x >> 6;
     for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < nQup; slot += stride) {
-        const bool inRange = slot < A.nQ;
-        uint4 cur[RW / 4];
-#pragma unroll
-        for (int i = 0; i < RW / 4; ++i) cur[i] = make_uint4(0, 0, 0, 0);
-        uint32_t r = 0;
-        uint64_t readStart = 0;
-        uint4 mo = make_uint4(0, 0, 0, 0);
-        if (inRange) {
-#pragma unroll
-            for (int i = 0; i < RW / 4; ++i) cur[i] = reinterpret_cast<const uint4 *>(A.rec)[(size_t)slot * (A.recCW / 4u) + i];
-            // the read of this slot: reads are mostly equally long, so the proportional guess is right; else search
-            r = (uint32_t)((double)slot * readsPerSlot);
-            if (r >= A.nReads) r = A.nReads - 1u;
-            readStart = A.kmerOff[r];
-            if (!(readStart <= slot && slot < A.kmerOff[r + 1])) {
-                uint32_t lo = 0, hi = A.nReads;                                // last r with kmerOff[r] <= slot
-                while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (A.kmerOff[mid] <= slot) lo = mid; else hi = mid; }
-                r = lo;
-                readStart = A.kmerOff[r];
-            }
-            mo = reinterpret_cast<const uint4 *>(A.mainOut)[r];
-        }
-        const bool live = inRange && mo.w != 0u && (cur[0].z & 31u) != 0u;     // a matched query of a read the fast path kept
-        const uint32_t mTax0 = mo.x, mTax1 = mo.y;
-        QueryRec<RW> Q;
-        Q.decode_regs(cur, A.pool);
-        if (!live) { Q.d = 0; Q.nInl = 0; Q.nMore = 0; Q.split = 0; }
-        const bool sat = RW == 8 && (cur[0].z & REC_SPLIT) != 0u;   // then: one event record per level (seg_records)
-        const int nEv = Q.d ? Q.d - A.kLow + 1 : 0;
+        OtherSlot<RW> S;
+        S.template load<false>(A, slot);
+        QueryRec<RW> &Q = S.Q;
+        const bool live = S.live;
+        const uint32_t mTax0 = S.mo.tax0, mTax1 = S.mo.tax1;
+        const bool sat = RW == 8 && (S.cur[0].z & REC_SPLIT) != 0u;   // then: one event record per level (seg_records)
+        const int nEv = S.events(A.kLow);
         // the pool segments of the query, the first four in registers (their loads go out together)
         uint32_t xs[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -5057,18 +5189,11 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
         }
         // levels with |T| > CNT_FIELDS: there the register taxa leave profile records instead of counting in LDS
         uint32_t bigLv = 0;
-        if constexpr (RW == 8) {
-            const uint32_t x = Q.nlev, f = (x >> 2) & ((x >> 1) | x) & 0x249249u;      // field >= 5, one bit per 3-bit field
-            bigLv = (f & 1u) | ((f >> 2) & 2u) | ((f >> 4) & 4u) | ((f >> 6) & 8u) | ((f >> 8) & 16u) | ((f >> 10) & 32u) | ((f >> 12) & 64u) | ((f >> 14) & 128u);
-        } else {
+        if constexpr (RW == 8) bigLv = big_levels8(Q.nlev);
+        else
             for (int lv = 0; lv < nEv; ++lv) { const int l2 = A.kHigh - A.kLow - lv; if (Q.set_size(l2, A.kHigh) > CNT_FIELDS) bigLv |= 1u << l2; }
-        }
-        // levels at which a segment leaves records (all of them: another taxon; those with a large |T|: register taxon)
-        // and how many records that makes
-        auto emitMask = [&](uint32_t sq, bool valid) -> uint32_t {
-            const uint32_t t = sq & SEG_TAX_MASK, m = valid ? seg_level_mask(sq, A.kHigh) : 0u;
-            return (t != mTax0 && t != mTax1) ? m : (GP ? 0u : (m & bigLv));
-        };
+        // levels at which a segment leaves records, and how many records that makes
+        auto emitMask = [&](uint32_t sq, bool valid) -> uint32_t { return valid ? emit_mask<RW>(sq, mTax0, mTax1, bigLv, A.kHigh) : 0u; };
         auto records = [&](uint32_t sq, uint32_t m) -> uint32_t {
             const uint32_t t = sq & SEG_TAX_MASK;
             return (t != mTax0 && t != mTax1) ? seg_records<RW>(m, sat) : (uint32_t)__popc(m);
@@ -5079,9 +5204,8 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
         for (int q = 0; q < RT::INL; ++q) { em[q] = emitMask(Q.sg[q], (uint32_t)q < Q.nInl); mine += records(Q.sg[q], em[q]); }
         for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = extra(q); mine += records(sq, emitMask(sq, true)); }
         // segmented inclusive prefix sum over the wavefront: a segment starts at every read's first slot
-        const bool head = inRange && (uint64_t)slot == readStart;
         uint32_t incl = mine;
-        bool started = head;                                                   // a read starts at or before this lane, inside the wavefront
+        bool started = S.head(slot);                                           // a read starts at or before this lane, inside the wavefront
         wave_seg_incl_sum(incl, started);
         // place in the wavefront's staging area: a plain prefix sum
         uint32_t lincl = mine;
@@ -5090,29 +5214,14 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
         if (total == 0u) continue;                                           // uniform
         const bool staged = total <= STAGE;
         uint32_t lp = lincl - mine;
-        // reads that began before the wavefront continue from the count score_main_kernel left at the wavefront's first slot
-        uint32_t w = mine ? mo.z + incl - mine + (started ? 0u : A.otherOff64[slot >> 6]) : 0u;
+        uint32_t w = mine ? S.row_at(A, slot, started) + incl - mine : 0u;
         auto emit = [&](uint2 rec) {
             if (staged) { sRec[wv][lp] = rec; sAt[wv][lp] = w; ++lp; ++w; }
             else A.st[w++] = rec;
         };
-        // position of level lv in the query's flush order (three bits per event: the field that equals lv, found without a loop)
-        auto posOf = [&](int lv) -> int {
-            if constexpr (RW == 8) {
-                const uint32_t x = ((uint32_t)Q.order ^ ((uint32_t)lv * 0x249249u)) | (nEv < 8 ? (0xFFFFFFFFu << (3 * nEv)) : 0u);
-                const uint32_t z = ~(x | (x >> 1) | (x >> 2)) & 0x249249u;       // bit 3 i set iff field i is zero
-                return (__ffs((int)z) - 1) / 3;
-            } else {
-                Order o = (Order)Q.order;
-                int pos = 0;
-                for (int ev = 0; ev < nEv; ++ev, o >>= OB) if ((int)((uint32_t)o & ((1u << OB) - 1u)) == lv) pos = ev;
-                return pos;
-            }
-        };
         auto putEvent = [&](uint32_t sq, int lv) {
             const uint32_t t = sq & SEG_TAX_MASK;
-            const uint32_t kind = (t == mTax0 || t == mTax1) ? RK_PROFILE : kindOther;
-            emit(make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (Q.set_size(lv, A.kHigh) << 16) | 1u));
+            emit(event_record<PERREAD>(t, t == mTax0 || t == mTax1, lv, Q.set_size(lv, A.kHigh)));
         };
         auto putSeg = [&](uint32_t sq, uint32_t m) {
             if (m == 0u) return;
@@ -5121,7 +5230,7 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
             if (pc == 1u && (RW != 8 || t == mTax0 || t == mTax1 || sat)) { putEvent(sq, __ffs((int)m) - 1); return; }   // one event, one record
             if (RW == 8 && t != mTax0 && t != mTax1 && pc <= 2u && !sat) {   // one segment record (seg_records)
                 const int lvLo = __ffs((int)m) - 1, lvHi = 31 - __clz((int)m);   // lvLo = the deeper level (larger k)
-                const bool desc = pc == 2u && posOf(lvLo) < posOf(lvHi);          // the larger k flushes first
+                const bool desc = pc == 2u && order_pos8((uint32_t)Q.order, nEv, lvLo) < order_pos8((uint32_t)Q.order, nEv, lvHi);   // the larger k flushes first
                 emit(make_uint2(t | ((uint32_t)(A.kHigh - lvHi) << 20) | (desc ? RK_SEG_DESC : 0u) | RK_SEG,
                                 (uint32_t)(A.kHigh - lvLo) | (Q.set_size(lvHi, A.kHigh) << 5) | (Q.set_size(lvLo, A.kHigh) << 18)));
                 return;
@@ -5133,16 +5242,8 @@ __global__ __launch_bounds__(256) void score_other_kernel(ScoreArgs A)
             }
         };
         if (mine == 0u) {}
-        else if (Q.split) {
-            // a taxon may own several segments: its records must follow the query's flush order across them -- event by event
-            Order o = (Order)Q.order;
-            for (int ev = 0; ev < nEv; ++ev, o >>= OB) {
-                const int lv = (int)((uint32_t)o & ((1u << OB) - 1u));
-#pragma unroll
-                for (int q = 0; q < RT::INL; ++q) if ((em[q] >> lv) & 1u) putEvent(Q.sg[q], lv);
-                for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = extra(q); if ((emitMask(sq, true) >> lv) & 1u) putEvent(sq, lv); }
-            }
-        } else {
+        else if (Q.split) split_walk<RW>(Q, nEv, mTax0, mTax1, bigLv, A.kHigh, putEvent);
+        else {
 #pragma unroll
             for (int q = 0; q < RT::INL; ++q) putSeg(Q.sg[q], em[q]);
             for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = extra(q); putSeg(sq, emitMask(sq, true)); }
@@ -5166,88 +5267,47 @@ template <bool PERREAD>
 __global__ __launch_bounds__(256, 8) void score_other_flat_kernel(ScoreArgs A)
 {
     constexpr int WV = 4;
-    constexpr bool GP = GpOf<8>::v;
     __shared__ uint32_t sBase[WV][65];                                    // exclusive prefix sums of the queries' item counts
     __shared__ uint32_t sSg[WV][4][64];                                    // the inline segments that leave records, compacted
     __shared__ uint32_t sW2[WV][64], sW3[WV][64], sT0[WV][64], sT1[WV][64], sRow[WV][64], sBig[WV][64], sSplit[WV][64], sPool[WV][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t kindOther = PERREAD ? 0u : RK_PROFILE;
     const uint32_t stride = gridDim.x * 256u;
-    const double readsPerSlot = (double)A.nReads / (double)A.nQ;
     const uint32_t nQup = (A.nQ + 63u) & ~63u;
-    const unsigned long long upTo = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);   // lanes 0..lane
     for (uint32_t slot = blockIdx.x * 256u + threadIdx.x; slot < nQup; slot += stride) {
-        const bool inRange = slot < A.nQ;
-        uint4 cur[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-        uint32_t r = 0;
-        uint64_t readStart = 0;
-        uint4 mo = make_uint4(0, 0, 0, 0);
-        if (inRange) {
-            cur[0] = reinterpret_cast<const uint4 *>(A.rec)[(size_t)slot << A.recQS];
-            cur[1] = reinterpret_cast<const uint4 *>(A.rec)[((size_t)slot << A.recQS) + 1];
-            r = (uint32_t)((double)slot * readsPerSlot);                       // reads are mostly equally long: the guess is right, else search
-            if (r >= A.nReads) r = A.nReads - 1u;
-            readStart = A.kmerOff[r];
-            if (!(readStart <= slot && slot < A.kmerOff[r + 1])) {
-                uint32_t lo = 0, hi = A.nReads;
-                while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (A.kmerOff[mid] <= slot) lo = mid; else hi = mid; }
-                r = lo;
-                readStart = A.kmerOff[r];
-            }
-            mo = reinterpret_cast<const uint4 *>(A.mainOut)[r];
-        }
-        const bool live = inRange && mo.w != 0u && (cur[0].z & 31u) != 0u;     // a matched query of a read the fast path kept
-        const uint32_t mTax0 = mo.x, mTax1 = mo.y;
-        QueryRec<8> Q;
-        Q.decode_regs(cur, A.pool);
-        if (!live) { Q.d = 0; Q.nInl = 0; Q.nMore = 0; Q.split = 0; Q.nseg = 0; }
+        OtherSlot<8> Sl;
+        Sl.template load<true>(A, slot);
+        const QueryRec<8> &Q = Sl.Q;
+        const uint32_t mTax0 = Sl.mo.tax0, mTax1 = Sl.mo.tax1;
         const bool split = Q.split != 0u;
-        const int nEvMine = Q.d ? Q.d - A.kLow + 1 : 0;
-        // levels with |T| > 4: there the register taxa leave profile records instead of counting in LDS (score_main_kernel)
-        const uint32_t xl = Q.nlev, fl = (xl >> 2) & ((xl >> 1) | xl) & 0x249249u;   // field >= 5, one bit per 3-bit field
-        const uint32_t bigLv = (fl & 1u) | ((fl >> 2) & 2u) | ((fl >> 4) & 4u) | ((fl >> 6) & 8u) | ((fl >> 8) & 16u) | ((fl >> 10) & 32u) | ((fl >> 12) & 64u) | ((fl >> 14) & 128u);
-        auto emitMask = [&](uint32_t sq) -> uint32_t {
-            const uint32_t t = sq & SEG_TAX_MASK, m = seg_level_mask(sq, A.kHigh);
-            return (t != mTax0 && t != mTax1) ? m : (GP ? 0u : (m & bigLv));
-        };
-        uint32_t mineSplit = 0;                                                // a split query's records: one per (segment, level)
-        if (__ballot(split) != 0ull && split) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) if ((uint32_t)q < Q.nInl) mineSplit += (uint32_t)__popc(emitMask(Q.sg[q]));
-            for (uint32_t q = 0; q < Q.nMore; ++q) mineSplit += (uint32_t)__popc(emitMask(Q.more[q]));
-        }
+        const int nEvMine = Sl.events(A.kLow);
+        const uint32_t bigLv = big_levels8(Q.nlev);
+        uint32_t mineSplit = 0;                                                // a split query's records
+        if (__ballot(split) != 0ull && split) mineSplit = split_records<8>(Q, mTax0, mTax1, bigLv, A.kHigh);
         // items: the inline segments that leave records (most belong to the register taxa and do not) and all pool segments
         uint32_t emInl = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) if ((uint32_t)q < Q.nInl && emitMask(Q.sg[q]) != 0u) emInl |= 1u << q;
+        for (int q = 0; q < 4; ++q) if ((uint32_t)q < Q.nInl && emit_mask<8>(Q.sg[q], mTax0, mTax1, bigLv, A.kHigh) != 0u) emInl |= 1u << q;
         const uint32_t nEmInl = (uint32_t)__popc(emInl);
         const uint32_t nFlat = split ? (mineSplit ? 1u : 0u) : nEmInl + Q.nMore;
         uint32_t incl = nFlat;
         incl = wave_incl_sum(incl);
         const uint32_t S = lane_value<63>(incl);
         if (S == 0u) continue;                                                 // uniform
-        const bool head = inRange && (uint64_t)slot == readStart;
-        const unsigned long long H = __ballot(head);
-        const bool started = (H & upTo) != 0ull;                               // a read starts at or before this lane, inside the wavefront
-        sBase[wv][lane] = incl - nFlat;
-        if (lane == 63) sBase[wv][64] = S;
+        ItemPlacer P;
+        const bool started = P.begin(Sl.head(slot), lane);
+        item_bases(sBase[wv], lane, incl, nFlat);
 #pragma unroll
         for (int q = 0; q < 4; ++q) if ((emInl >> q) & 1u) sSg[wv][__popc(emInl & ((1u << q) - 1u))][lane] = Q.sg[q];
         sPool[wv][lane] = Q.sg[3];                                             // pool block of the query (when it has one)
-        sW2[wv][lane] = cur[0].z; sW3[wv][lane] = (cur[0].w & ~255u) | (nEmInl << 4) | (Q.nMore ? 1u : 0u);   // low byte: items in LDS; has a pool block
+        sW2[wv][lane] = Sl.cur[0].z; sW3[wv][lane] = (Sl.cur[0].w & ~255u) | (nEmInl << 4) | (Q.nMore ? 1u : 0u);   // low byte: items in LDS; has a pool block
         sT0[wv][lane] = mTax0; sT1[wv][lane] = mTax1; sBig[wv][lane] = bigLv;
-        // reads that began before the wavefront continue from the count score_main_kernel left at the wavefront's first slot
-        sRow[wv][lane] = live ? mo.z + (started ? 0u : A.otherOff64[slot >> 6]) : 0u;
+        sRow[wv][lane] = Sl.live ? Sl.row_at(A, slot, started) : 0u;
         sSplit[wv][lane] = mineSplit;
         LDS_WAVE_SYNC();
-        uint32_t carry = 0;
-        int prevOwnCarry = -1;
         for (uint32_t b0 = 0; b0 < S; b0 += 64) {
             const uint32_t i = b0 + lane;
             const bool act = i < S;
-            uint32_t own = 0;                                                  // the last query whose items start at or before i
-#pragma unroll
-            for (int step = 32; step; step >>= 1) if (sBase[wv][own + step] <= i) own += step;
+            uint32_t own = item_owner(sBase[wv], i);
             if (!act) own = 63u;
             const uint32_t idx = i - sBase[wv][own];
             const uint32_t w2 = sW2[wv][own], w3 = sW3[wv][own], poolAt = sPool[wv][own];
@@ -5259,24 +5319,14 @@ __global__ __launch_bounds__(256, 8) void score_other_flat_kernel(ScoreArgs A)
                 if (idx < nInl) sq = sSg[wv][idx][own];
                 else sq = A.pool[poolAt + 1u + ((w2 & REC_SAT) ? POOL_SIZES : 0u) + idx - nInl];
             }
-            const uint32_t t = sq & SEG_TAX_MASK;
-            const bool isMain = t == sT0[wv][own] || t == sT1[wv][own];
-            const uint32_t m = seg ? seg_level_mask(sq, A.kHigh) : 0u;
-            const uint32_t em = isMain ? (GP ? 0u : (m & sBig[wv][own])) : m;
+            const uint32_t t = sq & SEG_TAX_MASK, tax0 = sT0[wv][own], tax1 = sT1[wv][own];
+            const bool isMain = t == tax0 || t == tax1;
+            const uint32_t em = seg ? emit_mask<8>(sq, tax0, tax1, sBig[wv][own], A.kHigh) : 0u;
             const uint32_t pc = (uint32_t)__popc(em);
             const bool segRec = !isMain && pc <= 2u;                           // one segment record (seg_records)
             uint32_t c = segRec ? (pc ? 1u : 0u) : pc;
             if (act && isSplit) c = sSplit[wv][own];
-            // does a read begin between the previous item's query and this one's?  Then the count restarts here.
-            const int prevOwn = lane_before((int)own, prevOwnCarry);
-            const unsigned long long toOwn = own == 63u ? ~0ull : ((2ull << own) - 1ull);
-            const unsigned long long toPrev = prevOwn < 0 ? 0ull : (prevOwn == 63 ? ~0ull : ((2ull << prevOwn) - 1ull));
-            bool f = act && (H & toOwn & ~toPrev) != 0ull;
-            uint32_t v = c;
-            wave_seg_incl_sum(v, f);
-            uint32_t w = sRow[wv][own] + v - c + (f ? 0u : carry);
-            carry = lane_value<63>(v) + ((int)lane_value<63>((uint32_t)f) ? 0u : carry);
-            prevOwnCarry = (int)lane_value<63>((uint32_t)own);
+            uint32_t w = sRow[wv][own] + P.place(own, act, c);
             const int nEv = (int)(w2 & 31u) - A.kLow + 1;
             const uint32_t order = (w2 >> 5) & 0xFFFFFFu;
             auto sizeOf = [&](int lv) -> uint32_t {
@@ -5287,44 +5337,28 @@ __global__ __launch_bounds__(256, 8) void score_other_flat_kernel(ScoreArgs A)
                 if (isSplit) sSplit[wv][own] = w;                             // its owner writes them below
                 else if (segRec) {
                     const int lvLo = __ffs((int)em) - 1, lvHi = 31 - __clz((int)em);   // lvLo = the deeper level (larger k)
-                    // position of a level in the query's flush order (three bits per event): the field that equals lv
-                    auto posOf = [&](int lv) -> int {
-                        const uint32_t x = (order ^ ((uint32_t)lv * 0x249249u)) | (nEv < 8 ? (0xFFFFFFFFu << (3 * nEv)) : 0u);
-                        const uint32_t z = ~(x | (x >> 1) | (x >> 2)) & 0x249249u;
-                        return (__ffs((int)z) - 1) / 3;
-                    };
-                    const bool desc = pc == 2u && posOf(lvLo) < posOf(lvHi);   // the larger k flushes first
+                    const bool desc = pc == 2u && order_pos8(order, nEv, lvLo) < order_pos8(order, nEv, lvHi);   // the larger k flushes first
                     A.st[w] = make_uint2(t | ((uint32_t)(A.kHigh - lvHi) << 20) | (desc ? RK_SEG_DESC : 0u) | RK_SEG,
                                          (uint32_t)(A.kHigh - lvLo) | (sizeOf(lvHi) << 5) | (sizeOf(lvLo) << 18));
                 }
             }
             const bool multi = act && c != 0u && !isSplit && !segRec;          // one event record per level, in flush order
             if (__ballot(multi) != 0ull && multi) {
-                const uint32_t kind = isMain ? RK_PROFILE : kindOther;
                 uint32_t o = order;
                 for (int ev = 0; ev < nEv; ++ev, o >>= 3) {
                     const int lv = (int)(o & 7u);
-                    if ((em >> lv) & 1u) A.st[w++] = make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (sizeOf(lv) << 16) | 1u);
+                    if ((em >> lv) & 1u) A.st[w++] = event_record<PERREAD>(t, isMain, lv, sizeOf(lv));
                 }
             }
         }
         if (__ballot(split && mineSplit) != 0ull) {
             LDS_WAVE_SYNC();
             if (split && mineSplit) {
-                // a taxon may own several segments: its records must follow the query's flush order across them -- event by event
                 uint32_t w = sSplit[wv][lane];
-                uint32_t o = (uint32_t)Q.order;
-                auto putEvent = [&](uint32_t sq, int lv) {
+                split_walk<8>(Q, nEvMine, mTax0, mTax1, bigLv, A.kHigh, [&](uint32_t sq, int lv) {
                     const uint32_t t = sq & SEG_TAX_MASK;
-                    const uint32_t kind = (t == mTax0 || t == mTax1) ? RK_PROFILE : kindOther;
-                    A.st[w++] = make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (Q.set_size(lv, A.kHigh) << 16) | 1u);
-                };
-                for (int ev = 0; ev < nEvMine; ++ev, o >>= 3) {
-                    const int lv = (int)(o & 7u);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) if ((uint32_t)q < Q.nInl && ((emitMask(Q.sg[q]) >> lv) & 1u)) putEvent(Q.sg[q], lv);
-                    for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = Q.more[q]; if ((emitMask(sq) >> lv) & 1u) putEvent(sq, lv); }
-                }
+                    A.st[w++] = event_record<PERREAD>(t, t == mTax0 || t == mTax1, lv, Q.set_size(lv, A.kHigh));
+                });
             }
         }
         LDS_WAVE_SYNC();
@@ -5341,7 +5375,6 @@ __global__ __launch_bounds__(128) void score_other_flat16_kernel(ScoreArgs A)
 {
     typedef RecTraits<16> RT;
     constexpr int WV = 2, INL = RT::INL;
-    constexpr bool GP = GpOf<16>::v;
     constexpr uint32_t CNT_FIELDS = 2u;
     __shared__ uint32_t sBase[WV][65];
     __shared__ uint32_t sSg[WV][INL][64];                                  // inline segments (sweep 1: all; sweep 2: those that leave records)
@@ -5349,49 +5382,23 @@ __global__ __launch_bounds__(128) void score_other_flat16_kernel(ScoreArgs A)
     __shared__ uint32_t sW2[WV][64], sT0[WV][64], sT1[WV][64], sRow[WV][64], sBig[WV][64], sSplit[WV][64], sPool[WV][64], sNInl[WV][64];
     __shared__ uint32_t sLvN[WV][(NLW + 3) / 2][64];                       // |T_k| of every lane's query (QueryRec::tab), two levels per word
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t kindOther = PERREAD ? 0u : RK_PROFILE;
     const uint32_t stride = gridDim.x * 128u;
-    const double readsPerSlot = (double)A.nReads / (double)A.nQ;
     const uint32_t nQup = (A.nQ + 63u) & ~63u;
-    const unsigned long long upTo = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
     const int nK = A.kHigh - A.kLow + 1;
     for (uint32_t slot = blockIdx.x * 128u + threadIdx.x; slot < nQup; slot += stride) {
-        const bool inRange = slot < A.nQ;
-        uint4 cur[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) cur[i] = make_uint4(0, 0, 0, 0);
-        uint32_t r = 0;
-        uint64_t readStart = 0;
-        uint4 mo = make_uint4(0, 0, 0, 0);
-        if (inRange) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) cur[i] = reinterpret_cast<const uint4 *>(A.rec)[(size_t)slot * 4 + i];
-            r = (uint32_t)((double)slot * readsPerSlot);
-            if (r >= A.nReads) r = A.nReads - 1u;
-            readStart = A.kmerOff[r];
-            if (!(readStart <= slot && slot < A.kmerOff[r + 1])) {
-                uint32_t lo = 0, hi = A.nReads;
-                while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (A.kmerOff[mid] <= slot) lo = mid; else hi = mid; }
-                r = lo;
-                readStart = A.kmerOff[r];
-            }
-            mo = reinterpret_cast<const uint4 *>(A.mainOut)[r];
-        }
-        const bool live = inRange && mo.w != 0u && (cur[0].z & 31u) != 0u;
-        const uint32_t mTax0 = mo.x, mTax1 = mo.y;
-        QueryRec<16> Q;
-        Q.decode_regs(cur, A.pool);
-        if (!live) { Q.d = 0; Q.nInl = 0; Q.nMore = 0; Q.split = 0; Q.nseg = 0; }
+        OtherSlot<16> Sl;
+        Sl.template load<true>(A, slot);
+        QueryRec<16> &Q = Sl.Q;
+        const uint32_t mTax0 = Sl.mo.tax0, mTax1 = Sl.mo.tax1;
         const bool split = Q.split != 0u;
-        const int nEvMine = Q.d ? Q.d - A.kLow + 1 : 0;
+        const int nEvMine = Sl.events(A.kLow);
         // ---- sweep 1: |T_k| of every query
         for (uint32_t w = 0; w < lvp_rows(nK); ++w) sLvN[wv][w][lane] = 0u;
         uint32_t incl = Q.nseg;
         incl = wave_incl_sum(incl);
         const uint32_t S1 = lane_value<63>(incl);
         if (S1 == 0u) continue;                                                // uniform: no live query
-        sBase[wv][lane] = incl - Q.nseg;
-        if (lane == 63) sBase[wv][64] = S1;
+        item_bases(sBase[wv], lane, incl, Q.nseg);
 #pragma unroll
         for (int q = 0; q < INL; ++q) sSg[wv][q][lane] = Q.sg[q];
         sNInl[wv][lane] = Q.nInl;
@@ -5400,9 +5407,7 @@ __global__ __launch_bounds__(128) void score_other_flat16_kernel(ScoreArgs A)
         for (uint32_t b0 = 0; b0 < S1; b0 += 64) {
             const uint32_t i = b0 + lane;
             if (i < S1) {
-                uint32_t own = 0;
-#pragma unroll
-                for (int step = 32; step; step >>= 1) if (sBase[wv][own + step] <= i) own += step;
+                const uint32_t own = item_owner(sBase[wv], i);
                 const uint32_t idx = i - sBase[wv][own], nInl = sNInl[wv][own];
                 const uint32_t sq = idx < nInl ? sSg[wv][idx][own] : A.pool[sPool[wv][own] + 1u + idx - nInl];
                 const int la = A.kHigh - (int)(sq >> 27), lb = A.kHigh - (int)((sq >> 22) & 31u) + 1;
@@ -5414,48 +5419,34 @@ __global__ __launch_bounds__(128) void score_other_flat16_kernel(ScoreArgs A)
         uint32_t bigLv = 0;                                                    // levels where the register taxa leave profile records
         lvp_running(&sLvN[wv][0][lane], 64, nK, [&](int lv, uint32_t n) { if (n > CNT_FIELDS) bigLv |= 1u << lv; });
         Q.tab = &sLvN[wv][0][lane]; Q.tabStride = 64;
-        auto emitMask = [&](uint32_t sq) -> uint32_t {
-            const uint32_t t = sq & SEG_TAX_MASK, m = seg_level_mask(sq, A.kHigh);
-            return (t != mTax0 && t != mTax1) ? m : (GP ? 0u : (m & bigLv));
-        };
         // ---- sweep 2: the records
         uint32_t mineSplit = 0;
-        if (__ballot(split) != 0ull && split) {
-#pragma unroll
-            for (int q = 0; q < INL; ++q) if ((uint32_t)q < Q.nInl) mineSplit += (uint32_t)__popc(emitMask(Q.sg[q]));
-            for (uint32_t q = 0; q < Q.nMore; ++q) mineSplit += (uint32_t)__popc(emitMask(Q.more[q]));
-        }
+        if (__ballot(split) != 0ull && split) mineSplit = split_records<16>(Q, mTax0, mTax1, bigLv, A.kHigh);
         uint32_t emInl = 0;
 #pragma unroll
-        for (int q = 0; q < INL; ++q) if ((uint32_t)q < Q.nInl && emitMask(Q.sg[q]) != 0u) emInl |= 1u << q;
+        for (int q = 0; q < INL; ++q) if ((uint32_t)q < Q.nInl && emit_mask<16>(Q.sg[q], mTax0, mTax1, bigLv, A.kHigh) != 0u) emInl |= 1u << q;
         const uint32_t nEmInl = (uint32_t)__popc(emInl);
         const uint32_t nFlat = split ? (mineSplit ? 1u : 0u) : nEmInl + Q.nMore;
         incl = nFlat;
         incl = wave_incl_sum(incl);
         const uint32_t S = lane_value<63>(incl);
         if (S == 0u) { LDS_WAVE_SYNC(); continue; }                            // uniform
-        const bool head = inRange && (uint64_t)slot == readStart;
-        const unsigned long long H = __ballot(head);
-        const bool started = (H & upTo) != 0ull;
+        ItemPlacer P;
+        const bool started = P.begin(Sl.head(slot), lane);
         LDS_WAVE_SYNC();                                                       // sweep 1's readers are done with sBase / sSg
-        sBase[wv][lane] = incl - nFlat;
-        if (lane == 63) sBase[wv][64] = S;
+        item_bases(sBase[wv], lane, incl, nFlat);
 #pragma unroll
         for (int q = 0; q < INL; ++q) if ((emInl >> q) & 1u) sSg[wv][__popc(emInl & ((1u << q) - 1u))][lane] = Q.sg[q];
         sNInl[wv][lane] = nEmInl;
-        sOrd[wv][0][lane] = cur[1].x; sOrd[wv][1][lane] = cur[1].y; sOrd[wv][2][lane] = cur[1].z; sOrd[wv][3][lane] = cur[1].w;
-        sW2[wv][lane] = cur[0].z; sT0[wv][lane] = mTax0; sT1[wv][lane] = mTax1; sBig[wv][lane] = bigLv;
-        sRow[wv][lane] = live ? mo.z + (started ? 0u : A.otherOff64[slot >> 6]) : 0u;
+        sOrd[wv][0][lane] = Sl.cur[1].x; sOrd[wv][1][lane] = Sl.cur[1].y; sOrd[wv][2][lane] = Sl.cur[1].z; sOrd[wv][3][lane] = Sl.cur[1].w;
+        sW2[wv][lane] = Sl.cur[0].z; sT0[wv][lane] = mTax0; sT1[wv][lane] = mTax1; sBig[wv][lane] = bigLv;
+        sRow[wv][lane] = Sl.live ? Sl.row_at(A, slot, started) : 0u;
         sSplit[wv][lane] = mineSplit;
         LDS_WAVE_SYNC();
-        uint32_t carry = 0;
-        int prevOwnCarry = -1;
         for (uint32_t b0 = 0; b0 < S; b0 += 64) {
             const uint32_t i = b0 + lane;
             const bool act = i < S;
-            uint32_t own = 0;
-#pragma unroll
-            for (int step = 32; step; step >>= 1) if (sBase[wv][own + step] <= i) own += step;
+            uint32_t own = item_owner(sBase[wv], i);
             if (!act) own = 63u;
             const uint32_t idx = i - sBase[wv][own];
             const uint32_t w2 = sW2[wv][own];
@@ -5464,56 +5455,38 @@ __global__ __launch_bounds__(128) void score_other_flat16_kernel(ScoreArgs A)
             const bool seg = act && !isSplit;
             if (seg) {
                 const uint32_t nInl = sNInl[wv][own];
-                sq = idx < nInl ? sSg[wv][idx][own] : A.pool[sPool[wv][own] + 1u + (INL - 1) + (idx - nInl) - (INL - 1)];
+                sq = idx < nInl ? sSg[wv][idx][own] : A.pool[sPool[wv][own] + 1u + idx - nInl];
             }
-            const uint32_t t = sq & SEG_TAX_MASK;
-            const bool isMain = t == sT0[wv][own] || t == sT1[wv][own];
-            const uint32_t m = seg ? seg_level_mask(sq, A.kHigh) : 0u;
-            const uint32_t em = isMain ? (GP ? 0u : (m & sBig[wv][own])) : m;
+            const uint32_t t = sq & SEG_TAX_MASK, tax0 = sT0[wv][own], tax1 = sT1[wv][own];
+            const bool isMain = t == tax0 || t == tax1;
+            const uint32_t em = seg ? emit_mask<16>(sq, tax0, tax1, sBig[wv][own], A.kHigh) : 0u;
             uint32_t c = (uint32_t)__popc(em);
             if (act && isSplit) c = sSplit[wv][own];
-            const int prevOwn = lane_before((int)own, prevOwnCarry);
-            const unsigned long long toOwn = own == 63u ? ~0ull : ((2ull << own) - 1ull);
-            const unsigned long long toPrev = prevOwn < 0 ? 0ull : (prevOwn == 63 ? ~0ull : ((2ull << prevOwn) - 1ull));
-            bool f = act && (H & toOwn & ~toPrev) != 0ull;
-            uint32_t v = c;
-            wave_seg_incl_sum(v, f);
-            uint32_t w = sRow[wv][own] + v - c + (f ? 0u : carry);
-            carry = lane_value<63>(v) + ((int)lane_value<63>((uint32_t)f) ? 0u : carry);
-            prevOwnCarry = (int)lane_value<63>((uint32_t)own);
+            uint32_t w = sRow[wv][own] + P.place(own, act, c);
             if (act && c) {
-                const uint32_t kind = isMain ? RK_PROFILE : kindOther;
                 if (isSplit) sSplit[wv][own] = w;
                 else if (c == 1u) {
                     const int lv = __ffs((int)em) - 1;
-                    A.st[w] = make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (lvp_get(&sLvN[wv][0][own], 64, lv) << 16) | 1u);
+                    A.st[w] = event_record<PERREAD>(t, isMain, lv, lvp_get(&sLvN[wv][0][own], 64, lv));
                 } else {                                                       // its levels in the query's flush order
                     const int nEv = (int)(w2 & 31u) - A.kLow + 1;
                     unsigned __int128 o = ((unsigned __int128)sOrd[wv][3][own] << 96) | ((unsigned __int128)sOrd[wv][2][own] << 64) |
                                           ((unsigned __int128)sOrd[wv][1][own] << 32) | sOrd[wv][0][own];
                     for (int ev = 0; ev < nEv; ++ev, o >>= 5) {
                         const int lv = (int)((uint32_t)o & 31u);
-                        if ((em >> lv) & 1u) A.st[w++] = make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (lvp_get(&sLvN[wv][0][own], 64, lv) << 16) | 1u);
+                        if ((em >> lv) & 1u) A.st[w++] = event_record<PERREAD>(t, isMain, lv, lvp_get(&sLvN[wv][0][own], 64, lv));
                     }
                 }
             }
         }
         if (__ballot(split && mineSplit) != 0ull) {
             LDS_WAVE_SYNC();
-            if (split && mineSplit) {                                          // a taxon may own several segments: event by event
+            if (split && mineSplit) {
                 uint32_t w = sSplit[wv][lane];
-                unsigned __int128 o = Q.order;
-                auto putEvent = [&](uint32_t sq, int lv) {
+                split_walk<16>(Q, nEvMine, mTax0, mTax1, bigLv, A.kHigh, [&](uint32_t sq, int lv) {
                     const uint32_t t = sq & SEG_TAX_MASK;
-                    const uint32_t kind = (t == mTax0 || t == mTax1) ? RK_PROFILE : kindOther;
-                    A.st[w++] = make_uint2(t | ((uint32_t)lv << RK_LV_SHIFT) | kind, (Q.set_size(lv, A.kHigh) << 16) | 1u);
-                };
-                for (int ev = 0; ev < nEvMine; ++ev, o >>= 5) {
-                    const int lv = (int)((uint32_t)o & 31u);
-#pragma unroll
-                    for (int q = 0; q < INL; ++q) if ((uint32_t)q < Q.nInl && ((emitMask(Q.sg[q]) >> lv) & 1u)) putEvent(Q.sg[q], lv);
-                    for (uint32_t q = 0; q < Q.nMore; ++q) { const uint32_t sq = Q.more[q]; if ((emitMask(sq) >> lv) & 1u) putEvent(sq, lv); }
-                }
+                    A.st[w++] = event_record<PERREAD>(t, t == mTax0 || t == mTax1, lv, Q.set_size(lv, A.kHigh));
+                });
             }
         }
         LDS_WAVE_SYNC();
@@ -8219,9 +8192,8 @@ struct CohCursor {
     {
         idx = at;
         if (at >= n) return;
-        uint32_t lo = 0, hi = nReads;                                 // last read whose elements start at or before `at`
-        while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (off[mid] <= at) lo = mid; else hi = mid; }
-        er = lo; eStart = off[er]; eEnd = off[er + 1]; per = (uint32_t)((eEnd - eStart) / strands);
+        er = last_at_or_before(off, nReads, at);                      // the last read whose elements start at or before `at`
+        eStart = off[er]; eEnd = off[er + 1]; per = (uint32_t)((eEnd - eStart) / strands);
     }
     __device__ void next()
     {
@@ -8850,21 +8822,12 @@ __global__ __launch_bounds__(256) void record_stats_kernel(ScoreArgs A, unsigned
 {
     const int lane = threadIdx.x & 63;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    const bool inRange = slot < A.nQ;
-    uint4 cur[2] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-    uint4 mo = make_uint4(0, 0, 0, 0);
-    if (inRange) {
-        cur[0] = reinterpret_cast<const uint4 *>(A.rec)[(size_t)slot * (A.recCW / 4u)]; cur[1] = reinterpret_cast<const uint4 *>(A.rec)[(size_t)slot * (A.recCW / 4u) + 1];
-        uint32_t lo = 0, hi = A.nReads;
-        while (hi - lo > 1) { const uint32_t mid = lo + ((hi - lo) >> 1); if (A.kmerOff[mid] <= slot) lo = mid; else hi = mid; }
-        mo = reinterpret_cast<const uint4 *>(A.mainOut)[lo];
-    }
-    const bool live = inRange && mo.w != 0u && (cur[0].z & 31u) != 0u;
-    QueryRec<8> Q;
-    Q.decode_regs(cur, A.pool);
-    if (!live) { Q.d = 0; Q.nInl = 0; Q.nMore = 0; Q.split = 0; Q.nseg = 0; }
-    const bool sat = (cur[0].z & REC_SAT) != 0u, split = live && (cur[0].z & REC_SPLIT) != 0u;
-    const int nEv = Q.d ? Q.d - A.kLow + 1 : 0;
+    OtherSlot<8> S;
+    S.load<false>(A, slot);
+    const QueryRec<8> Q = S.Q;                                        // (a copy: the loop below indexes its segments)
+    const MainOut mo = S.mo;
+    const bool live = S.live, sat = (S.cur[0].z & REC_SAT) != 0u, split = live && (S.cur[0].z & REC_SPLIT) != 0u;
+    const int nEv = S.events(A.kLow);
     unsigned long long v[32];
     for (int i = 0; i < 32; ++i) v[i] = 0;
     v[0] = live; v[1] = live && Q.nMore > 0; v[2] = split; v[3] = live && sat; v[4] = Q.nseg;
@@ -8873,7 +8836,7 @@ __global__ __launch_bounds__(256) void record_stats_kernel(ScoreArgs A, unsigned
         const uint32_t sq = q < Q.nInl ? Q.sg[q] : Q.more[q - Q.nInl];
         const uint32_t t = sq & SEG_TAX_MASK, m = seg_level_mask(sq, A.kHigh);
         const uint32_t pc = __popc(m);
-        if (t != mo.x && t != mo.y) {
+        if (t != mo.tax0 && t != mo.tax1) {
             ++nOtherSeg; v[5]++; v[6] += pc == 1; v[7] += pc == 2; v[8] += pc >= 3;
             if (!split && !sat) v[16] += pc >= 3;
             rec += seg_records<8>(m, split);
