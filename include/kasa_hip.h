@@ -477,6 +477,14 @@ int kasa_batch_query_count(kasa_ctx *ctx, uint64_t *n);
 int kasa_batch_fetch_queries(kasa_ctx *ctx, void *kmers, uint32_t *reads, uint64_t n);
 /* Test tap: install (k-mer, read id) queries directly instead of upload + encode (any order). */
 int kasa_batch_set_queries(kasa_ctx *ctx, const void *kmers, const uint32_t *reads, uint64_t n, int64_t nReads);
+/* Test tap (like kasa_batch_set_queries and kasa_text_dtoa): replace the per-read score rows of the batch that is loaded
+ * by a CSR of the caller's -- readOffsets[nReads + 1], per read taxIdx strictly ascending (the rank kernels index the
+ * denominators with them) and any float as score, zeros, infinities and NaN included.  kasa_batch_scores_fetch then returns
+ * exactly these arrays, kasa_batch_rank and kasa_batch_text work on them; rank and text results of the batch become invalid,
+ * its coherence scores stay.  Works on any loaded batch, whatever has run on it (right after kasa_batch_upload, too).
+ * KASA_E_STATE: no batch is loaded.  KASA_E_ARG: nReads is not the batch's read count; the offsets do not start at 0 or
+ * descend; a taxon index >= the index's taxon count; taxon indices not strictly ascending within a row. */
+int kasa_batch_set_scores(kasa_ctx *ctx, const uint64_t *readOffsets, const uint32_t *taxIdx, const float *score, uint64_t nReads);
 /* Per sorted query: deepest matched level k (0 = none) and an index position sharing that prefix. */
 int kasa_batch_fetch_lookup(kasa_ctx *ctx, uint8_t *depth, uint32_t *indexPos, uint64_t n);
 int kasa_ctx_device_bytes(kasa_ctx *ctx, uint64_t *bytes);

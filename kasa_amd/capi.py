@@ -25,7 +25,7 @@ EXPORTS = [
     "kasa_batch_records_fetch", "kasa_batch_records_import", "kasa_batch_scores_size", "kasa_batch_scores_fetch",
     "kasa_profile_reset", "kasa_profile_absorb", "kasa_profile_fetch", "kasa_profile_export_limbs", "kasa_profile_import_limbs", "kasa_profile_allreduce",
     "kasa_ctx_stage_ms", "kasa_ctx_stage_reset", "kasa_ctx_kernel_ms", "kasa_ctx_batch_stats", "kasa_batch_query_count", "kasa_batch_fetch_queries",
-    "kasa_batch_fetch_lookup", "kasa_ctx_device_bytes", "kasa_device_memory", "kasa_batch_bytes_per_query", "kasa_ctx_counters", "kasa_ctx_third_pass_reads", "kasa_ctx_synchronize", "kasa_batch_set_queries", "kasa_ctx_debug",
+    "kasa_batch_fetch_lookup", "kasa_ctx_device_bytes", "kasa_device_memory", "kasa_batch_bytes_per_query", "kasa_ctx_counters", "kasa_ctx_third_pass_reads", "kasa_ctx_synchronize", "kasa_batch_set_queries", "kasa_batch_set_scores", "kasa_ctx_debug",
     "kasa_refbatch_budget", "kasa_refbatch_sequence_cost", "kasa_refbatch_read_overhead", "kasa_refbatch_cut",
     "kasa_batch_rank", "kasa_batch_rank_fetch", "kasa_host_alloc", "kasa_host_free", "kasa_thread_device",
     "kasa_batch_queries_device", "kasa_batch_slice_starts", "kasa_batch_set_sorted_device", "kasa_batch_records_device",
@@ -176,6 +176,7 @@ def lib():
         L.kasa_host_free.argtypes = [C.c_void_p]
         L.kasa_batch_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         L.kasa_batch_rank_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_batch_set_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.kasa_runtime_versions.argtypes = [C.c_void_p] * 5
         L.kasa_build_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
         L.kasa_build_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
@@ -1245,6 +1246,16 @@ class Context:
         reads = np.ascontiguousarray(reads, dtype=np.uint32)
         _check(lib().kasa_batch_set_queries(self.h, _p(kmers), _p(reads), C.c_uint64(kmers.shape[0]), C.c_int64(n_reads)))
         self.n_reads, self.n_kmers = int(n_reads), int(kmers.shape[0])
+
+    def set_scores(self, offsets: np.ndarray, tax_idx: np.ndarray, scores: np.ndarray):
+        """kasa_batch_set_scores (test tap): the CSR (offsets u64[nReads + 1], taxIdx u32[nnz] strictly ascending per read,
+        score f32[nnz]) in place of the loaded batch's score rows; scores(), rank() and text() then work on it."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        tax_idx = np.ascontiguousarray(tax_idx, dtype=np.uint32)
+        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        if offsets.shape[0] < 1 or tax_idx.shape[0] != scores.shape[0] or (tax_idx.shape[0] < int(offsets[-1])):
+            raise ValueError("set_scores: offsets[nReads + 1] and one taxon index and score per cell")
+        _check(lib().kasa_batch_set_scores(self.h, _p(offsets), _p(tax_idx), _p(scores), C.c_uint64(offsets.shape[0] - 1)))
 
     def lookup(self):
         d = np.zeros(self.n_kmers, dtype=np.uint8)

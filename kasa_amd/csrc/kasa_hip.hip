@@ -8956,6 +8956,54 @@ extern "C" int kasa_batch_set_queries(kasa_ctx *c, const void *kmers, const uint
     KASA_GUARDED(batch_set_queries_impl(c, kmers, reads, n, nReads))
 }
 
+// test tap: the caller's CSR in place of the rows the score stage left ({taxon, score} pairs in the staging buffer, row r at
+// rowPos[r], rowLen without ROW_MERGE, rowOff their running sum): what kasa_batch_rank and csr_pack read
+static int batch_set_scores_impl(kasa_ctx *c, const uint64_t *readOffsets, const uint32_t *taxIdx, const float *score, uint64_t nReads)
+{
+    if (!c || !readOffsets) return fail(KASA_E_ARG, "kasa_batch_set_scores: NULL argument");
+    if (c->state < 1) return fail(KASA_E_STATE, "kasa_batch_set_scores: no batch is loaded");
+    if (nReads != (uint64_t)c->nReads) return fail(KASA_E_ARG, "kasa_batch_set_scores: %llu reads, the batch has %lld", (unsigned long long)nReads, (long long)c->nReads);
+    if (readOffsets[0] != 0) return fail(KASA_E_ARG, "kasa_batch_set_scores: readOffsets does not start at 0");
+    for (uint64_t r = 0; r < nReads; ++r)
+        if (readOffsets[r + 1] < readOffsets[r]) return fail(KASA_E_ARG, "kasa_batch_set_scores: readOffsets descends at read %llu", (unsigned long long)r);
+    const uint64_t nnz = readOffsets[nReads];
+    if (nnz >= 0xFFFFFFF0ull) return fail(KASA_E_LIMIT, "kasa_batch_set_scores: %llu cells exceed the 32-bit positions of the staging buffer", (unsigned long long)nnz);
+    if (nnz && (!taxIdx || !score)) return fail(KASA_E_ARG, "kasa_batch_set_scores: NULL argument");
+    const uint32_t nTaxa = c->ix->nTaxa;
+    std::vector<uint2> cells((size_t)nnz);
+    std::vector<uint32_t> pos((size_t)nReads), len((size_t)nReads);
+    for (uint64_t r = 0; r < nReads; ++r) {
+        const uint64_t lo = readOffsets[r], hi = readOffsets[r + 1];
+        if (hi - lo >= (uint64_t)ROW_MERGE) return fail(KASA_E_LIMIT, "kasa_batch_set_scores: read %llu has 2^31 or more cells", (unsigned long long)r);
+        pos[(size_t)r] = (uint32_t)lo; len[(size_t)r] = (uint32_t)(hi - lo);
+        for (uint64_t i = lo; i < hi; ++i) {
+            if (taxIdx[i] >= nTaxa) return fail(KASA_E_ARG, "kasa_batch_set_scores: read %llu names taxon index %u of %u", (unsigned long long)r, taxIdx[i], nTaxa);
+            if (i > lo && taxIdx[i] <= taxIdx[i - 1]) return fail(KASA_E_ARG, "kasa_batch_set_scores: the taxon indices of read %llu do not ascend strictly", (unsigned long long)r);
+            uint32_t bits; memcpy(&bits, &score[i], 4);
+            cells[(size_t)i] = make_uint2(taxIdx[i], bits);
+        }
+    }
+    HIPCHK(hipSetDevice(c->ix->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->haveScores = false; c->rankValid = false; c->rankFlagged = 0; c->rankEntries = 0; c->txtValid = false; c->bgzValid = false; c->fltValid = false;
+    int rc;
+    if ((rc = c->st.reserve((size_t)nnz * 8 + 64)) || (rc = c->rowPos.reserve((size_t)nReads * 4 + 64)) || (rc = c->rowLen.reserve((size_t)nReads * 4 + 64)) ||
+        (rc = c->rowOff.reserve(((size_t)nReads + 1) * 8 + 64)))
+        return rc;
+    if (nnz) HIPCHK(hipMemcpyAsync(c->st.p, cells.data(), (size_t)nnz * 8, hipMemcpyHostToDevice, c->stream));
+    if (nReads) HIPCHK(hipMemcpyAsync(c->rowPos.p, pos.data(), (size_t)nReads * 4, hipMemcpyHostToDevice, c->stream));
+    if (nReads) HIPCHK(hipMemcpyAsync(c->rowLen.p, len.data(), (size_t)nReads * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->rowOff.p, readOffsets, ((size_t)nReads + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->nnz = nnz; c->csrPacked = false; c->haveScores = true;
+    return KASA_OK;
+}
+
+extern "C" int kasa_batch_set_scores(kasa_ctx *c, const uint64_t *readOffsets, const uint32_t *taxIdx, const float *score, uint64_t nReads)
+{
+    KASA_GUARDED(batch_set_scores_impl(c, readOffsets, taxIdx, score, nReads))
+}
+
 extern "C" int kasa_batch_fetch_lookup(kasa_ctx *c, uint8_t *depth, uint32_t *indexPos, uint64_t n)
 {
     if (!c) return fail(KASA_E_ARG, "ctx is NULL");

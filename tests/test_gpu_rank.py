@@ -163,8 +163,10 @@ def test_cpp_host_ties_follow_std_sort(kind, tmp_path):
 
 def test_device_number_format():
     """kasa_text.h's Grisu2 against the host's (kasa_amd/textnum.py, pinned on the reference's files): doubles of every
-    magnitude, float32 values widened (what k-mer scores and errors are), exact powers, subnormals, the specials."""
+    magnitude, float32 values widened (what k-mer scores and errors are), exact powers, subnormals, the specials; the float32
+    neighbours of the powers of ten and doubles of exactly 1 .. 16 fractional digits (rank_corpus.structured_numbers)."""
     from kasa_amd import textnum
+    from tests import rank_corpus
     rs = np.random.default_rng(5)
     vals = [0.0, -0.0, 1.0, -1.0, 0.1, 0.5, 1e21, 1e22, 1e-5, 1e-6, 1e-7, 123456789012345678.0, 5e-324, 2.2250738585072014e-308,
             1.7976931348623157e308, float("inf"), float("-inf"), float("nan"), 0.3, 2.0 / 3.0, 100.0, 1e20, 9.999999999999999e20]
@@ -174,6 +176,7 @@ def test_device_number_format():
     vals += [float(x) for x in rs.random(3000).astype(np.float32)]                                # float -> double as the writer passes them
     vals += [float(np.float32(a) / np.float32(b)) for a, b in zip(rs.integers(1, 5000, 2000), rs.integers(1, 5000, 2000))]
     vals += list(np.frombuffer(rs.bytes(8 * 3000), dtype=np.float64))                           # any bit pattern
+    vals += rank_corpus.structured_numbers()
     got = capi.device_dtoa(vals)
     for v, g in zip(vals, got):
         assert g == textnum.dtoa(float(v)), (v, g, textnum.dtoa(float(v)))
