@@ -6480,7 +6480,7 @@ static int group_stage(kasa_ctx *c, int coverage, bool exportSorted, uint32_t *r
         if ((rc = fetch(c->stream, used, cursor))) return rc;
         const unsigned long long poolUsed = used[CUR_POOL], keysUsed = used[CUR_PROF_KEYS];
         const bool tooLong = (used[CUR_GROUP_FLAG] & 1ull) != 0;
-        if (g2 && tooLong) return fail(KASA_E_LIMIT, "a query meets 255 or more taxa of a 128-bit index through narrow records; use the index's own k range");
+        if (tooLong && c->ix->wide) return fail(KASA_E_LIMIT, "a query meets 255 or more taxa of a 128-bit index through narrow records; use the index's own k range");
         if (RW == 8 && !g2 && !coop && !(c->debugFlags & 131072) && (tooLong || poolUsed > 6ull * nQ)) {
             // a list of 255 or more segments (the lean kernel cannot count it), or long lists on average: whole wavefronts
             // take the long lists from here on -- this batch again if it must be, the context's further batches anyway
