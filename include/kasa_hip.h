@@ -536,6 +536,12 @@ int kasa_ctx_counters(kasa_ctx *ctx, uint32_t *generalReads, uint32_t *secondPas
  * window in device memory (narrow records; 64-byte records return KASA_E_LIMIT there).  Ours: the reference's flush is a
  * hash map per thread and has no such window (Compare.hpp:917-955). */
 int kasa_ctx_third_pass_reads(kasa_ctx *ctx, uint32_t *thirdPassReads);
+/* Of the last batch's score stage (its last attempt, where the staging buffer grew): why score_main_kernel handed reads to
+ * the slower kernels.  out[0]: more k-mers than the counters' fields hold (255, or 60 000 with 16-bit fields); [1]: too many
+ * taxa (no kernel of this build counts it: always 0); [2]: a staging row longer than the row merge takes; [3]: a list of 8192 or more segments; [4]: the order rule (an
+ * earlier group of the read is still open at its next matched query).  Read-only: a copy of counters the kernel keeps anyway.
+ * Diagnostics for tests. */
+int kasa_ctx_hand_over_reasons(kasa_ctx *ctx, uint32_t out[5]);
 /* The row merge takes the staging rows of the fast score kernels in classes by length (256 / 512 / 1024 records up to 2048
  * taxa, 256 / 1024 up to 16 384 taxa where the second class stays empty, and a streaming class for the longer rows of long
  * reads): the first class's launch sweeps all reads, the others walk the rows score_main_kernel listed for them and are not

@@ -42,7 +42,7 @@ EXPORTS = [
     "kasa_pair_take", "kasa_pair_fetch",
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate", "kasa_ctx_set_bgzf_code", "kasa_bgzf_deflate_coded",
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
-    "kasa_ctx_row_classes", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
+    "kasa_ctx_row_classes", "kasa_ctx_hand_over_reasons", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
     "kasa_pool_keep_records", "kasa_pool_fetch_records", "kasa_batch_filter", "kasa_batch_filter_fetch_range", "kasa_filter_split",
 ]
 
@@ -1163,6 +1163,13 @@ class Context:
         n = C.c_uint32(0)
         _check(lib().kasa_ctx_third_pass_reads(self.h, C.byref(n)))
         return int(n.value)
+
+    def hand_over_reasons(self):
+        """Reads score_main_kernel handed on in the last batch, per reason: (k-mer count, taxa, row length, a list of 8192 or more
+        segments, the order rule) -- kasa_ctx_hand_over_reasons."""
+        out = np.zeros(5, dtype=np.uint32)
+        _check(lib().kasa_ctx_hand_over_reasons(self.h, _p(out)))
+        return tuple(int(v) for v in out)
 
     def row_classes(self):
         """Rows of the last batch per row-merge class: (first, second, third, long) -- kasa_ctx_row_classes."""

@@ -9040,6 +9040,19 @@ extern "C" int kasa_ctx_debug(kasa_ctx *c, int forceSlowScore, uint32_t *lastSlo
     return KASA_OK;
 }
 
+extern "C" int kasa_ctx_hand_over_reasons(kasa_ctx *c, uint32_t out[5])
+{
+    if (!c || !out) return fail(KASA_E_ARG, "kasa_ctx_hand_over_reasons: NULL argument");
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    if (!c->misc.p) return KASA_OK;                  // (no batch yet)
+    HIPCHK(hipSetDevice(c->ix->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint32_t w[8];
+    HIPCHK(hipMemcpy(w, c->ctr()->why, sizeof(w), hipMemcpyDeviceToHost));
+    for (int k = 0; k < 5; ++k) out[k] = w[k];
+    return KASA_OK;
+}
+
 extern "C" int kasa_device_memory(int device, uint64_t *freeBytes, uint64_t *totalBytes)
 {
     int ndev = 0;

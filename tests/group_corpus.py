@@ -273,6 +273,44 @@ def encode(recs: list, rw: int, k_high: int, k_low: int):
 
 
 # ------------------------------------------------------------------------------------------------
+# the records replayed: what tests/test_group_corpus_cpu.py and tests/test_score_corpus_cpu.py hold against the sequential oracle,
+# and the reference of tests/test_gpu_score_corpus.py
+# ------------------------------------------------------------------------------------------------
+def replay(c, recs, kh, kl):
+    """the reference's records as the reference program would flush them: events in (F, k) order, M[read][t] += w_k * (1 / |T_k|)
+    in float32 for every taxon of T_k; per group (level, F) hits / |T_k| into countAll, hits into countUnique where |T_k| = 1"""
+    n_taxa = c.ix.content.n_taxa
+    reads = c.sorted[1].tolist()
+    M = np.zeros((c.n_reads, n_taxa), dtype=np.float32)
+    ca, cu = np.zeros((kh - kl + 1, n_taxa), dtype=np.float64), np.zeros((kh - kl + 1, n_taxa), dtype=np.uint64)
+    groups = {}
+    for r in recs:
+        for i, f in enumerate(r.F):
+            groups.setdefault((f, kl + i), []).append(r.p)
+    taxa_of = {}
+    for (f, k), members in sorted(groups.items()):                       # a flush: one group of one level
+        sets = set()
+        for p in members:
+            key = (id(recs[p].segs), k)
+            if key not in taxa_of:
+                taxa_of[key] = tuple(sorted(t for t, kf, kl_ in recs[p].segs if kf <= k <= kl_))
+            sets.add(taxa_of[key])
+        assert len(sets) == 1, (c.name, k, f, "the members of a group see one taxon set")
+        t = np.array(sets.pop(), dtype=np.int64)
+        score = (np.float32(k * k) / np.float32(625)) * (np.float32(1) / np.float32(t.shape[0]))
+        rows = [reads[p] for p in members]
+        if len(set(rows)) == len(rows):                                   # every hit another read: the cells are all different
+            M[np.ix_(rows, t)] += score
+        else:
+            for r in rows:
+                M[r, t] += score
+        ca[kh - k, t] += float(len(members)) / float(t.shape[0])
+        if t.shape[0] == 1:
+            cu[kh - k, t] += np.uint64(len(members))
+    return M, ca, cu
+
+
+# ------------------------------------------------------------------------------------------------
 # what a batch asks of group_stage, from the reference and the constants above
 # ------------------------------------------------------------------------------------------------
 def leaders(recs: list) -> list:
