@@ -380,10 +380,30 @@ enum {
     KASA_INFLATE_OVERRUN = 9,       /* more output than ISIZE states */
     KASA_INFLATE_SHORT = 10,        /* less output than ISIZE states */
     KASA_INFLATE_TRAILING = 11,     /* bytes between the last block and the trailer */
-    KASA_INFLATE_CRC = 12           /* the output's CRC-32 is not the trailer's */
+    KASA_INFLATE_CRC = 12,          /* the output's CRC-32 is not the trailer's */
+    KASA_INFLATE_GZIP_HEADER = 13,  /* kasa_gzip_inflate: no gzip member header (1f 8b 08, no reserved flag) where one has to be */
+    KASA_INFLATE_SPAN = 14          /* kasa_gzip_inflate: a block (one wavefront's text) longer than the span limit of 2^30 bytes */
 };
 int kasa_bgzf_inflate(int device, const void *stream, uint64_t nBytes, void *text, uint64_t cap, uint64_t *nText, int *status, uint64_t *member);
 const char *kasa_inflate_status_text(int code);
+
+/* ---- plain gzip in: ONE LONG deflate stream inflated on the device (ours; kasa_amd/csrc/kasa_gunzip.h) ------
+ * The file gzip and pigz write has no member table, so the stream is cut into chunks of chunkBytes compressed bytes: every
+ * chunk searches its own bits for a dynamic block header that validates, a wavefront per chunk decodes whole blocks from
+ * there into 16-bit symbols (a byte, or a marker for a byte of the 32 KiB before the chunk), the host confirms the chain of
+ * block boundaries round by round, and the markers are replaced once the windows are known.  The host parses the member
+ * headers (FEXTRA, FNAME, FCOMMENT, FHCRC) and compares CRC-32 and ISIZE with each trailer; members follow one another.
+ * The same contract as kasa_bgzf_inflate: a malformed stream is a status, never a fault and never a hang.
+ *   kasa_gzip_inflate   test tap, host to host.  chunkBytes: 0 for the default (64 KiB), else 64 or more.  *nText = the text
+ *                       of all members; KASA_E_LIMIT (nothing written) when cap is smaller.  A bad stream: KASA_OK with
+ *                       *status = a KASA_INFLATE_* code and *member = the index of the member it is in (for
+ *                       KASA_INFLATE_GZIP_HEADER: of the member that should begin there); the text is then not written.
+ *                       ISIZE: a text shorter than stated is KASA_INFLATE_SHORT, a longer one KASA_INFLATE_OVERRUN.
+ *                       stats8, when not NULL: chunks, chunks with a start (the first chunk of a member has one by
+ *                       definition), chunks confirmed, candidates the chain rejected, rounds (the most any member took),
+ *                       marker symbols written, capacity reruns, members.  Streams of 2 GiB and more are KASA_E_LIMIT. */
+int kasa_gzip_inflate(int device, const void *stream, uint64_t nBytes, uint32_t chunkBytes, void *text, uint64_t cap, uint64_t *nText, int *status,
+                      uint64_t *member, uint64_t *stats8);
 
 /* Page-locked host memory for buffers that cross PCIe (reads in, ranked hits or CSR out).  NULL when it cannot be had. */
 void *kasa_host_alloc(size_t bytes);
@@ -745,6 +765,24 @@ int kasa_parse_stage_ms(kasa_parser *p, double *uploadMs, double *parseMs);
 int kasa_bgzf_parse_append(kasa_parser *p, const void *members, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
                            uint64_t *nTextBytes, uint64_t *carryBytes);
 int kasa_bgzf_parse_status(kasa_parser *p, int *code, uint64_t *member);
+/* The same pool fed with a PLAIN gzip file (kasa_gzip_inflate above): spans of the file's bytes as they come.  The parser keeps
+ * the stream's state between the calls: what stands at the span's first byte (a member header, deflate data from a confirmed
+ * bit on, a trailer), the last 32 KiB of the open member's text, its running CRC-32 and length.  Whole blocks are inflated
+ * behind the carry, the text is cut at the last whole record and parsed as with kasa_bgzf_parse_append.
+ *   *keepFrom     the byte of `bytes` from which the host sends again next time, more bytes behind it: where the last
+ *                 confirmed block ends (a block the span's end cuts is not output).  0 with no text: no whole block ends
+ *                 inside the span -- send a longer one.  A span of KASA_GZIP_SPAN_LIMIT bytes with no whole block is
+ *                 KASA_INFLATE_SPAN (16 MiB: 250 times the largest block zlib writes, 256 MiB of symbols on the device).
+ *   final         the file ends with the span: a member that does not end in it is KASA_INFLATE_TRUNCATED / _CUT.
+ *   *parsable = 0 pool, carry and stream state are as before the call; KASA_PARSE_INFLATE: the stream is malformed --
+ *                 kasa_gzip_parse_status gives the KASA_INFLATE_* code and the member's index in the FILE, and in stats8 (when
+ *                 not NULL) the chunk statistics of kasa_gzip_inflate summed over the calls (rounds: the most one stream took).
+ * kasa_gzip_parse_ms is kasa_bgzf_parse_ms (one counter).  KASA_GUNZIP_CHUNK in the environment: the chunk size in bytes. */
+#define KASA_GZIP_SPAN_LIMIT (16u << 20)
+int kasa_gzip_parse_append(kasa_parser *p, const void *bytes, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                           uint64_t *nTextBytes, uint64_t *keepFrom);
+int kasa_gzip_parse_status(kasa_parser *p, int *code, uint64_t *member, uint64_t *stats8);
+int kasa_gzip_parse_ms(kasa_parser *p, double *inflateMs);
 int kasa_bgzf_parse_ms(kasa_parser *p, double *inflateMs);
 /* Paired-end input (-1 <file> -2 <file>): TWO pools on one device, file 1 parsed into `first`, file 2 into `second`; pooled
  * read r of the one and pooled read r of the other are the mates of pair r.  The pools need not hold the same number of

@@ -11,7 +11,7 @@ HOST_SRCS = [os.path.join(HERE, "csrc", "kasa_refbatch.cpp")]   # host-only part
 SO = os.path.join(HERE, "libkasa_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "kasa_hip.h")
 CSRC_HEADERS = [os.path.join(HERE, "csrc", "stdsort_order.h"), os.path.join(HERE, "csrc", "kasa_radix.h"), os.path.join(HERE, "csrc", "kasa_text.h"), os.path.join(HERE, "csrc", "kasa_replay.h"),
-                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_filter.h"),
+                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h"), os.path.join(HERE, "csrc", "kasa_filter.h"),
                 os.path.join(HERE, "host", "grisu_powers.inc")]
 
 
@@ -77,6 +77,21 @@ def build_inflate_check(force: bool = False) -> str:
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                            "-o", INFLATE_CHECK_BIN, INFLATE_CHECK_SRC])
     return INFLATE_CHECK_BIN
+
+
+GUNZIP_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "gunzip_host_check.cpp")
+GUNZIP_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "gunzip_host_check")
+
+
+def build_gunzip_check(force: bool = False) -> str:
+    """tools/gunzip_host_check: the bodies and the rounds of csrc/kasa_gunzip.h for the CPU under AddressSanitizer + UBSan (a
+    stand-alone program; nothing is preloaded)."""
+    newest = max(os.path.getmtime(p) for p in (GUNZIP_CHECK_SRC, HEADER, os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h")))
+    if not force and os.path.exists(GUNZIP_CHECK_BIN) and os.path.getmtime(GUNZIP_CHECK_BIN) >= newest:
+        return GUNZIP_CHECK_BIN
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                           "-o", GUNZIP_CHECK_BIN, GUNZIP_CHECK_SRC])
+    return GUNZIP_CHECK_BIN
 
 
 if __name__ == "__main__":

@@ -41,7 +41,7 @@ EXPORTS = [
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
     "kasa_pair_take", "kasa_pair_fetch",
     "kasa_batch_bgzf", "kasa_batch_bgzf_fetch_range", "kasa_bgzf_deflate", "kasa_ctx_set_bgzf_code", "kasa_bgzf_deflate_coded",
-    "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
+    "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_gzip_inflate", "kasa_gzip_parse_append", "kasa_gzip_parse_status", "kasa_gzip_parse_ms", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
     "kasa_ctx_row_classes", "kasa_ctx_hand_over_reasons", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
     "kasa_pool_keep_records", "kasa_pool_fetch_records", "kasa_batch_filter", "kasa_batch_filter_fetch_range", "kasa_filter_split",
 ]
@@ -205,10 +205,14 @@ def lib():
         L.kasa_pair_take.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.kasa_pair_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5
         L.kasa_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_gzip_inflate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kasa_inflate_status_text.argtypes = [C.c_int]
         L.kasa_inflate_status_text.restype = C.c_char_p
         L.kasa_bgzf_parse_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.kasa_bgzf_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_gzip_parse_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.kasa_gzip_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_gzip_parse_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_bgzf_parse_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_parse_destroy.restype = None
         L.kasa_pool_keep_records.argtypes = [C.c_void_p, C.c_int]
@@ -394,6 +398,27 @@ def bgzf_inflate(device: int, stream, cap: int = None):
     if status.value:
         return None, int(status.value), int(member.value)
     return out[:got.value].tobytes(), 0, 0
+
+
+GZIP_STATS = ("chunks", "started", "confirmed", "rejected", "rounds", "markers", "reruns", "members")
+
+
+def gzip_inflate(device: int, stream, cap: int, chunk_bytes: int = 0):
+    """A plain gzip file (one long deflate stream per member) inflated by the DEVICE (kasa_gzip_inflate): (text, status,
+    member, stats).  status 0: text is the bytes of all members; else a KASA_INFLATE_* code, the index of the member it is in,
+    and text is None.  cap: the destination's size; too small raises RuntimeError (KASA_E_LIMIT) and nothing is written.
+    chunk_bytes: compressed bytes per chunk (0: the default; 64 or more).  stats: GZIP_STATS by name."""
+    src = np.frombuffer(bytes(stream), dtype=np.uint8)
+    n = int(src.shape[0])
+    out = np.zeros(max(1, cap), dtype=np.uint8)
+    stats = np.zeros(8, dtype=np.uint64)
+    got, status, member = C.c_uint64(0), C.c_int(0), C.c_uint64(0)
+    _check(lib().kasa_gzip_inflate(C.c_int(device), _p(src) if n else None, C.c_uint64(n), C.c_uint32(chunk_bytes), _p(out), C.c_uint64(cap), C.byref(got),
+                                   C.byref(status), C.byref(member), _p(stats)))
+    st = dict(zip(GZIP_STATS, (int(v) for v in stats)))
+    if status.value:
+        return None, int(status.value), int(member.value), st
+    return out[:got.value].tobytes(), 0, 0, st
 
 
 def pinned_empty(n: int, dtype) -> np.ndarray:
@@ -666,6 +691,23 @@ class Parser:
         _check(lib().kasa_bgzf_parse_append(self.h, _p(buf) if buf.shape[0] else None, C.c_uint64(buf.shape[0]), C.c_int(1 if fasta else 0), C.c_int(1 if final else 0),
                                             C.byref(n), C.byref(ok), C.byref(nt), C.byref(carry)))
         return int(n.value), bool(ok.value), int(nt.value), int(carry.value)
+
+    def append_gzip(self, data: bytes, fasta: bool, final: bool = False):
+        """A span of a plain gzip file's bytes (kasa_gzip_parse_append): whole blocks inflated on the device behind the carry,
+        cut at the last whole record (final: not cut), parsed.  (reads added, parsable, text bytes parsed, keep_from): the
+        next span begins with data[keep_from:]."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        n, ok, nt, keep = C.c_uint64(0), C.c_int(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_gzip_parse_append(self.h, _p(buf) if buf.shape[0] else None, C.c_uint64(buf.shape[0]), C.c_int(1 if fasta else 0), C.c_int(1 if final else 0),
+                                            C.byref(n), C.byref(ok), C.byref(nt), C.byref(keep)))
+        return int(n.value), bool(ok.value), int(nt.value), int(keep.value)
+
+    def gzip_status(self):
+        """(KASA_INFLATE_* code, its text, member index in the file, chunk statistics by GZIP_STATS' names) of append_gzip."""
+        code, member = C.c_int(0), C.c_uint64(0)
+        stats = np.zeros(8, dtype=np.uint64)
+        _check(lib().kasa_gzip_parse_status(self.h, C.byref(code), C.byref(member), _p(stats)))
+        return int(code.value), inflate_status_text(code.value), int(member.value), dict(zip(GZIP_STATS, (int(v) for v in stats)))
 
     def inflate_status(self):
         """(KASA_INFLATE_* code, its text, member index in the span) behind a KASA_PARSE_INFLATE refusal of append_bgzf."""

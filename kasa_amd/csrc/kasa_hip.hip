@@ -48,6 +48,7 @@
 #include "kasa_text.h"
 #include "kasa_bgzf.h"
 #include "kasa_inflate.h"
+#include "kasa_gunzip.h"
 
 // ------------------------------------------------------------------------------------------------
 // constants
@@ -8108,8 +8109,146 @@ extern "C" const char *kasa_inflate_status_text(int code)
     case KASA_INFLATE_SHORT: return "less output than ISIZE states";
     case KASA_INFLATE_TRAILING: return "bytes between the last block and the trailer";
     case KASA_INFLATE_CRC: return "a CRC-32 mismatch";
+    case KASA_INFLATE_GZIP_HEADER: return "no gzip member header";
+    case KASA_INFLATE_SPAN: return "a block longer than the span limit";
     default: return "unknown";
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// plain gzip in (kasa_gunzip.h): the device backend of inflate_stream / inflate_file
+// ------------------------------------------------------------------------------------------------
+struct GunzipDevice {
+    hipStream_t stream = nullptr;                 // every call below ends with a copy to the host that waited for its kernels
+    const uint8_t *dStream = nullptr;             // the span in device memory
+    uint32_t nBytes = 0;
+    uint8_t *dText = nullptr;                     // the destination
+    uint64_t textCap = 0;
+    const uint8_t *dPrev = nullptr;               // the last prevLen bytes of the member's text from the spans before, at the end of HIST bytes
+    uint32_t prevLen = 0;
+    std::vector<ScopedBuf> syms;                  // slabs of the jobs' symbols (kept while their stream is placed)
+    size_t slabUsed = 0;
+    ScopedBuf start, jobs, res, segs, word;
+
+    void begin() { if (syms.size() > 1) syms.erase(syms.begin(), syms.end() - 1); slabUsed = 0; }   // (the last slab serves the next stream)
+    int find(uint64_t dataAt, uint32_t chunkBytes, uint32_t nChunks, std::vector<uint64_t> &out)
+    {
+        int rc;
+        if ((rc = start.reserve((size_t)nChunks * 8))) return rc;
+        kasa_gunzip::find_kernel<<<nChunks - 1, 64, 0, stream>>>(dStream, nBytes, dataAt, chunkBytes, nChunks, start.as<unsigned long long>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out.data() + 1, start.as<uint64_t>() + 1, (size_t)(nChunks - 1) * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return KASA_OK;
+    }
+    int symbols(uint32_t n, uint16_t **p)
+    {
+        // (a slab for many jobs: one allocation a job would cost more than its decoding)
+        const size_t need = (((size_t)n * 2) + 255) & ~(size_t)255;
+        if (syms.empty() || slabUsed + need > syms.back().cap) {
+            syms.emplace_back();
+            slabUsed = 0;
+            int rc = syms.back().reserve(std::max<size_t>(need, (size_t)64 << 20));
+            if (rc) return rc;
+        }
+        *p = reinterpret_cast<uint16_t *>(syms.back().as<uint8_t>() + slabUsed);
+        slabUsed += need;
+        return KASA_OK;
+    }
+    int decode(const std::vector<kasa_gunzip::Job> &js, std::vector<kasa_gunzip::Result> &rs)
+    {
+        int rc;
+        const size_t n = js.size();
+        if (!n) return KASA_OK;
+        if ((rc = jobs.reserve(n * sizeof(kasa_gunzip::Job))) || (rc = res.reserve(n * sizeof(kasa_gunzip::Result)))) return rc;
+        HIPCHK(hipMemcpyAsync(jobs.p, js.data(), n * sizeof(kasa_gunzip::Job), hipMemcpyHostToDevice, stream));
+        kasa_gunzip::decode_kernel<<<(uint32_t)n, 64, 0, stream>>>(dStream, nBytes, jobs.as<kasa_gunzip::Job>(), (uint32_t)n, res.as<kasa_gunzip::Result>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rs.data(), res.p, n * sizeof(kasa_gunzip::Result), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return KASA_OK;
+    }
+    int place(const std::vector<kasa_gunzip::Seg> &sg, uint64_t textAt, uint64_t total, uint64_t *markers, bool *bad)
+    {
+        int rc;
+        if (textAt > textCap || total > textCap - textAt) return fail(KASA_E_ARG, "gzip inflate: %llu bytes at %llu pass the destination's end", (unsigned long long)total, (unsigned long long)textAt);
+        if ((rc = segs.reserve(sg.size() * sizeof(kasa_gunzip::Seg))) || (rc = word.reserve(16))) return rc;
+        HIPCHK(hipMemcpyAsync(segs.p, sg.data(), sg.size() * sizeof(kasa_gunzip::Seg), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(word.p, 0, 16, stream));
+        unsigned long long *dMarkers = word.as<unsigned long long>();
+        uint32_t *dBad = word.as<uint32_t>() + 2;
+        kasa_gunzip::chain_kernel<<<1, kasa_gunzip::CHAIN_THREADS, 0, stream>>>(segs.as<kasa_gunzip::Seg>(), (uint32_t)sg.size(), dText + textAt, total, dPrev, prevLen, dMarkers, dBad);
+        HIPCHK(hipGetLastError());
+        const uint64_t per = (uint64_t)kasa_gunzip::WRITE_THREADS * kasa_gunzip::WRITE_PER_THREAD;
+        kasa_gunzip::write_kernel<<<(uint32_t)((total + per - 1) / per), kasa_gunzip::WRITE_THREADS, 0, stream>>>(segs.as<kasa_gunzip::Seg>(), (uint32_t)sg.size(), dText + textAt, total, dPrev, prevLen, dMarkers, dBad);
+        HIPCHK(hipGetLastError());
+        uint64_t back[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(back, word.p, 16, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        *markers = back[0]; *bad = (uint32_t)back[1] != 0;
+        return KASA_OK;
+    }
+    // the CRC-32 register behind n more bytes of the destination (a member's first bytes: init = 0xFFFFFFFF; the CRC is its complement)
+    int crc_reg(uint64_t textAt, uint64_t n, uint32_t init, uint32_t *reg)
+    {
+        *reg = init;
+        if (!n) return KASA_OK;
+        int rc;
+        if ((rc = word.reserve(16))) return rc;
+        HIPCHK(hipMemsetAsync(word.p, 0, 4, stream));
+        const uint64_t slices = (n + kasa_gunzip::CRC_SLICE - 1) / kasa_gunzip::CRC_SLICE;
+        kasa_gunzip::crc_kernel<<<(uint32_t)((slices + kasa_gunzip::CRC_THREADS - 1) / kasa_gunzip::CRC_THREADS), kasa_gunzip::CRC_THREADS, 0, stream>>>(dText + textAt, n, init, word.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(reg, word.p, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return KASA_OK;
+    }
+    int crc(uint64_t textAt, uint64_t n, uint32_t *out)
+    {
+        uint32_t reg = 0;
+        int rc = crc_reg(textAt, n, 0xFFFFFFFFu, &reg);
+        *out = ~reg;
+        return rc;
+    }
+};
+
+// test tap: a host stream through the kernels of kasa_gunzip.h
+static int gzip_inflate_impl(int device, const uint8_t *stream, uint64_t nBytes, uint32_t chunkBytes, void *text, uint64_t cap, uint64_t *nText, int *status,
+                             uint64_t *member, uint64_t *stats8)
+{
+    if (!nText || !status || !member || (nBytes && !stream)) return fail(KASA_E_ARG, "kasa_gzip_inflate: NULL argument");
+    *nText = 0; *status = KASA_INFLATE_OK; *member = 0;
+    if (stats8) std::memset(stats8, 0, 8 * sizeof(uint64_t));
+    if (chunkBytes == 0) chunkBytes = kasa_gunzip::DEFAULT_CHUNK;
+    if (chunkBytes < kasa_gunzip::MIN_CHUNK) return fail(KASA_E_ARG, "kasa_gzip_inflate: chunkBytes %u is below %u", chunkBytes, kasa_gunzip::MIN_CHUNK);
+    if (nBytes >= (1ull << 31)) return fail(KASA_E_LIMIT, "kasa_gzip_inflate: a stream of %llu bytes is more than one call takes", (unsigned long long)nBytes);
+    if (cap && !text) return fail(KASA_E_ARG, "kasa_gzip_inflate: NULL destination");
+    HIPCHK(hipSetDevice(device));
+    GunzipDevice be;
+    ScopedBuf dStream, dOut;
+    int rc;
+    if ((rc = dStream.reserve((size_t)nBytes + 8)) || (rc = dOut.reserve((size_t)cap + 64))) return rc;
+    if (nBytes) HIPCHK(hipMemcpy(dStream.p, stream, nBytes, hipMemcpyHostToDevice));
+    be.dStream = dStream.as<uint8_t>(); be.nBytes = (uint32_t)nBytes; be.dText = dOut.as<uint8_t>(); be.textCap = cap;
+    kasa_gunzip::Stats st;
+    std::memset(&st, 0, sizeof st);
+    uint64_t total = 0;
+    rc = kasa_gunzip::inflate_file(be, stream, nBytes, chunkBytes, cap, st, status, member, &total);
+    HIPCHK(hipDeviceSynchronize());
+    if (rc == KASA_E_STATE) return fail(rc, "kasa_gzip_inflate: the rounds did not end");
+    if (rc) return rc;
+    if (stats8) { const uint64_t v[8] = {st.chunks, st.withStart, st.confirmed, st.rejected, st.rounds, st.markers, st.reruns, st.members}; std::memcpy(stats8, v, sizeof v); }
+    if (*status != KASA_INFLATE_OK) return KASA_OK;
+    *nText = total;
+    if (total > cap) return fail(KASA_E_LIMIT, "kasa_gzip_inflate: the text has %llu bytes, the destination takes %llu", (unsigned long long)total, (unsigned long long)cap);
+    if (total) HIPCHK(hipMemcpy(text, dOut.p, total, hipMemcpyDeviceToHost));
+    return KASA_OK;
+}
+
+extern "C" int kasa_gzip_inflate(int device, const void *stream, uint64_t nBytes, uint32_t chunkBytes, void *text, uint64_t cap, uint64_t *nText, int *status,
+                                 uint64_t *member, uint64_t *stats8)
+{
+    KASA_GUARDED(gzip_inflate_impl(device, static_cast<const uint8_t *>(stream), nBytes, chunkBytes, text, cap, nText, status, member, stats8))
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -373,6 +373,12 @@ struct kasa_parser {
     hipEvent_t evz[2] = {nullptr, nullptr};
     int inflateCode = 0; uint64_t inflateMember = 0;
     double msInflate = 0;
+    // kasa_gzip_parse_append: where the one long stream stands between two spans -- what comes next at the span's first byte
+    // (a member header, deflate data from bit `bit` on, a trailer), the member's CRC-32 register and length so far, and the
+    // last winLen bytes of its text at the end of gzWin's 32 KiB
+    struct GzState { int phase = 0; uint32_t bit = 0, crcReg = 0, winLen = 0; uint64_t memberBytes = 0, member = 0; } gz;
+    DevBuf gzWin, gzTmp;
+    uint64_t gzStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // kasa_pair_fetch (this pool as the first of the two): the interleaved arrays before they cross to the host
     DevBuf pairOff, pairNameOff, pairLengths, pairNames, pairBases;
     // kasa_pool_keep_records: records / recOff of the pool's arrays are kept like names / nameOff
@@ -689,6 +695,155 @@ static int append_bgzf_impl(kasa_parser *p, const uint8_t *span, uint64_t nBytes
     return KASA_OK;
 }
 
+// The backend of kasa_gunzip.h's rounds whose destination is the parser's text behind the carry: it grows as the streams of the
+// span are placed (their sizes are known only then).
+struct GunzipIntoParser : GunzipDevice {
+    kasa_parser *p = nullptr;
+    uint64_t base = 0;                            // the carry: the span's text begins behind it
+    int place(const std::vector<kasa_gunzip::Seg> &sg, uint64_t textAt, uint64_t total, uint64_t *markers, bool *bad)
+    {
+        const uint64_t end = base + textAt + total;
+        if (end >= MAX_CHUNK) return fail(KASA_E_LIMIT, "kasa_gzip_parse_append: the span's text passes %llu bytes", (unsigned long long)MAX_CHUNK);
+        int rc = grow_keep(p->text, (size_t)((end + TILE_BYTES - 1) / TILE_BYTES) * TILE_BYTES + 64, (size_t)(base + textAt), p->stream);
+        if (rc) return rc;
+        dText = p->text.as<uint8_t>() + base; textCap = textAt + total;
+        return GunzipDevice::place(sg, textAt, total, markers, bad);
+    }
+};
+
+// A span of a plain gzip file's bytes, from where the call before said (*keepFrom).  Whole blocks are inflated behind the carry
+// (kasa_gunzip.h), the text is cut at the last whole record and parsed as append_bgzf_impl does.  Nothing changes -- pool,
+// carry, the stream's state -- unless the span inflates cleanly and the cut text parses.
+static int append_gzip_impl(kasa_parser *p, const uint8_t *span, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                            uint64_t *nTextBytes, uint64_t *keepFrom)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (nBytes && !span) return fail(KASA_E_ARG, "kasa_gzip_parse_append: bytes is NULL");
+    if (nBytes >= (1ull << 31)) return fail(KASA_E_LIMIT, "kasa_gzip_parse_append: a span of %llu bytes is more than one call takes", (unsigned long long)nBytes);
+    if (nReadsAdded) *nReadsAdded = 0;
+    if (parsable) *parsable = 1;
+    if (nTextBytes) *nTextBytes = 0;
+    if (keepFrom) *keepFrom = 0;
+    p->lastCode = KASA_PARSE_OK; p->lastAt = 0; p->inflateCode = KASA_INFLATE_OK; p->inflateMember = 0;
+    HIPCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = pool_compact(p))) return rc;
+    if ((rc = p->gzWin.reserve(kasa_gunzip::HIST)) || (rc = p->gzTmp.reserve(kasa_gunzip::HIST)) || (rc = p->status.reserve(64))) return rc;
+    kasa_parser::GzState s = p->gz;
+    auto bad = [&](int code) { p->inflateCode = code; p->inflateMember = s.member; return refuse(p, KASA_PARSE_INFLATE, s.member, parsable); };
+    static const uint32_t chunkBytes = [] { const char *e = getenv("KASA_GUNZIP_CHUNK"); const long v = e ? atol(e) : 0; return v >= (long)kasa_gunzip::MIN_CHUNK ? (uint32_t)v : kasa_gunzip::DEFAULT_CHUNK; }();
+    GunzipIntoParser be;
+    be.stream = p->stream; be.p = p; be.base = p->carry;
+    HIPCHK(hipEventRecord(p->ev[0], p->stream));
+    HIPCHK(hipEventRecord(p->evz[0], p->stream));
+    if (nBytes) {
+        if ((rc = p->zStream.reserve(nBytes + 8))) return rc;
+        HIPCHK(hipMemcpyAsync(p->zStream.p, span, nBytes, hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipEventRecord(p->evz[0], p->stream));
+    }
+    be.dStream = p->zStream.as<uint8_t>(); be.nBytes = (uint32_t)nBytes;
+    kasa_gunzip::Stats st;
+    std::memset(&st, 0, sizeof st);
+    uint64_t at = 0, textN = 0;
+    uint64_t lastStart = 0; bool lastFresh = s.phase != 1;    // the member that is open at the end: where its text of this span begins, and whether it began in this span
+    for (;;) {
+        if (s.phase == 0) {
+            if (at == nBytes) break;
+            uint64_t dataAt = 0;
+            const int hs = kasa_gunzip::member_header(span, nBytes, at, &dataAt);
+            if (hs == KASA_INFLATE_CUT && !final) break;
+            if (hs != KASA_INFLATE_OK) return bad(hs);
+            at = dataAt;
+            s.phase = 1; s.bit = 0; s.crcReg = 0xFFFFFFFFu; s.winLen = 0; s.memberBytes = 0;
+            lastStart = textN; lastFresh = true;
+        }
+        if (s.phase == 1) {
+            int zs = KASA_INFLATE_OK; uint64_t endBit = 0, n = 0; bool ended = false;
+            be.dPrev = p->gzWin.as<uint8_t>(); be.prevLen = s.winLen;
+            if ((rc = kasa_gunzip::inflate_stream(be, nBytes, 8 * at + s.bit, chunkBytes, s.winLen, textN, ~0ull, !final, st, &zs, &endBit, &n, &ended))) return rc;
+            if (zs != KASA_INFLATE_OK) return bad(zs);
+            if (n) {
+                be.dText = p->text.as<uint8_t>() + p->carry;
+                if ((rc = be.crc_reg(textN, n, s.crcReg, &s.crcReg))) return rc;
+            }
+            textN += n; s.memberBytes += n;
+            if (!ended) { at = endBit >> 3; s.bit = (uint32_t)(endBit & 7u); break; }
+            at = (endBit + 7) >> 3; s.bit = 0; s.phase = 2;
+        }
+        if (s.phase == 2) {
+            if (nBytes - at < 8) { if (final) return bad(KASA_INFLATE_CUT); break; }
+            const uint8_t *t = span + at;
+            const uint32_t crc = (uint32_t)t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+            const uint32_t isize = (uint32_t)t[4] | (uint32_t)t[5] << 8 | (uint32_t)t[6] << 16 | (uint32_t)t[7] << 24;
+            if (~s.crcReg != crc) return bad(KASA_INFLATE_CRC);
+            if ((uint32_t)s.memberBytes != isize) return bad((uint32_t)s.memberBytes < isize ? KASA_INFLATE_SHORT : KASA_INFLATE_OVERRUN);
+            at += 8; s.phase = 0; ++s.member; ++st.members; s.winLen = 0;
+        }
+    }
+    if (final && s.phase != 0) return bad(s.phase == 1 ? KASA_INFLATE_TRUNCATED : KASA_INFLATE_CUT);
+    // no whole block in a span of the limit's size: the host path takes the file
+    if (at == 0 && textN == 0 && !final && nBytes >= KASA_GZIP_SPAN_LIMIT) return bad(KASA_INFLATE_SPAN);
+    const uint64_t total = p->carry + textN;
+    if (total >= MAX_CHUNK) return refuse(p, KASA_PARSE_TOO_LARGE, 0, parsable);
+    uint64_t added = 0, cutBytes = 0, rest = 0;
+    uint8_t *text = p->text.as<uint8_t>();
+    if (total) {
+        const size_t padded = (size_t)((total + TILE_BYTES - 1) / TILE_BYTES) * TILE_BYTES + 64;
+        if ((rc = grow_keep(p->text, padded, (size_t)total, p->stream))) return rc;
+        text = p->text.as<uint8_t>();
+        HIPCHK(hipMemsetAsync(text + total, 0, padded - total, p->stream));
+    }
+    HIPCHK(hipEventRecord(p->evz[1], p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, p->ev[0], p->evz[0]) == hipSuccess) p->msUpload += ms;
+    if (hipEventElapsedTime(&ms, p->evz[0], p->evz[1]) == hipSuccess) p->msInflate += ms;
+    if (total && (textN || final)) {                                             // (nothing new: the carry waits as it is)
+        TextCut cut;
+        cut.final = final != 0;
+        int ok = 1;
+        if ((rc = append_device(p, total, 0, 0, fasta, &cut, &added, &ok))) return rc;
+        if (!ok) { if (parsable) *parsable = 0; return KASA_OK; }                  // (carry and stream state are where they were)
+        cutBytes = cut.cutBytes; rest = total - cutBytes;
+    }
+    // ---- the window of the member that is still open: the last 32 KiB of its text, for the next span's first chunk
+    if (s.phase == 1) {
+        const uint64_t n = textN - lastStart;                                       // its text in this span
+        const uint8_t *src = text + p->carry + lastStart;
+        uint8_t *win = p->gzWin.as<uint8_t>();
+        const uint32_t H = kasa_gunzip::HIST;
+        if (n >= H) { HIPCHK(hipMemcpyAsync(win, src + (n - H), H, hipMemcpyDeviceToDevice, p->stream)); s.winLen = H; }
+        else if (n) {
+            const uint32_t keep = lastFresh ? 0u : (uint32_t)std::min<uint64_t>(p->gz.winLen, H - n);
+            if (keep) {                                                             // (the old window moves down by n: by way of a buffer)
+                HIPCHK(hipMemcpyAsync(p->gzTmp.p, win + (H - keep), keep, hipMemcpyDeviceToDevice, p->stream));
+                HIPCHK(hipMemcpyAsync(win + (H - n - keep), p->gzTmp.p, keep, hipMemcpyDeviceToDevice, p->stream));
+            }
+            HIPCHK(hipMemcpyAsync(win + (H - n), src, n, hipMemcpyDeviceToDevice, p->stream));
+            s.winLen = keep + (uint32_t)n;
+        } else if (lastFresh) s.winLen = 0;
+        HIPCHK(hipStreamSynchronize(p->stream));
+    }
+    // ---- what lies behind the cut moves to the front
+    if (rest && cutBytes) {
+        if (rest <= cutBytes) HIPCHK(hipMemcpyAsync(text, text + cutBytes, rest, hipMemcpyDeviceToDevice, p->stream));
+        else {
+            if ((rc = p->carryTmp.reserve(rest))) return rc;
+            HIPCHK(hipMemcpyAsync(p->carryTmp.p, text + cutBytes, rest, hipMemcpyDeviceToDevice, p->stream));
+            HIPCHK(hipMemcpyAsync(text, p->carryTmp.p, rest, hipMemcpyDeviceToDevice, p->stream));
+        }
+        HIPCHK(hipStreamSynchronize(p->stream));
+    }
+    p->carry = rest;
+    p->gz = s;
+    const uint64_t v[8] = {st.chunks, st.withStart, st.confirmed, st.rejected, st.rounds, st.markers, st.reruns, st.members};
+    for (int i = 0; i < 8; ++i) { if (i == 4) p->gzStats[i] = std::max(p->gzStats[i], v[i]); else p->gzStats[i] += v[i]; }
+    if (nReadsAdded) *nReadsAdded = added;
+    if (nTextBytes) *nTextBytes = cutBytes;
+    if (keepFrom) *keepFrom = at;
+    return KASA_OK;
+}
+
 static int pool_ends(kasa_parser *p, uint64_t r0, uint64_t n, uint64_t (&e)[4])
 {
     const PoolArrays &a = p->arrays[p->cur];
@@ -939,6 +1094,28 @@ extern "C" int kasa_bgzf_parse_append(kasa_parser *p, const void *members, uint6
                                       uint64_t *nTextBytes, uint64_t *carryBytes)
 {
     KASA_GUARDED(kasa_parse_impl::append_bgzf_impl(p, static_cast<const uint8_t *>(members), nBytes, fasta, final, nReadsAdded, parsable, nTextBytes, carryBytes))
+}
+
+extern "C" int kasa_gzip_parse_append(kasa_parser *p, const void *bytes, uint64_t nBytes, int fasta, int final, uint64_t *nReadsAdded, int *parsable,
+                                      uint64_t *nTextBytes, uint64_t *keepFrom)
+{
+    KASA_GUARDED(kasa_parse_impl::append_gzip_impl(p, static_cast<const uint8_t *>(bytes), nBytes, fasta, final, nReadsAdded, parsable, nTextBytes, keepFrom))
+}
+
+extern "C" int kasa_gzip_parse_status(kasa_parser *p, int *code, uint64_t *member, uint64_t *stats8)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (code) *code = p->inflateCode;
+    if (member) *member = p->inflateMember;
+    if (stats8) std::memcpy(stats8, p->gzStats, sizeof p->gzStats);
+    return KASA_OK;
+}
+
+extern "C" int kasa_gzip_parse_ms(kasa_parser *p, double *inflateMs)
+{
+    if (!p) return fail(KASA_E_ARG, "parser is NULL");
+    if (inflateMs) *inflateMs = p->msInflate;
+    return KASA_OK;
 }
 
 extern "C" int kasa_bgzf_parse_status(kasa_parser *p, int *code, uint64_t *member)

@@ -532,7 +532,11 @@ struct ChunkReader {
     bool bgzf = false; const char *bgzfWhy = nullptr;
     uint64_t membersOut = 0, textOut = 0, spanFileStart = 0;
     vector<std::pair<uint64_t, uint64_t>> spanStarts;
-    explicit ChunkReader(const string &path, bool wantBgzf = false)
+    // --device-gunzip: a gzip file that is not BGZF is one long stream and goes out as spans of its raw bytes (nextRaw); the
+    // device says from which byte it needs them again (keepRaw).  The way back to gzread starts at the file's first byte.
+    bool stream = false, rawDone = false;
+    string path;
+    explicit ChunkReader(const string &path_, bool wantBgzf = false, bool wantGunzip = false) : path(path_)
     {
         fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) throw std::runtime_error("Input file not found");
@@ -540,10 +544,13 @@ struct ChunkReader {
         const ssize_t m = ::pread(fd, magic, 18, 0);
         if (wantBgzf) {
             if (m < 2 || magic[0] != 0x1f || magic[1] != 0x8b) bgzfWhy = "the input is not gzip";
-            else if (m < 18 || std::memcmp(magic, kBgzfEof, 4) != 0 || std::memcmp(magic + 10, kBgzfEof + 10, 6) != 0) bgzfWhy = "gzip without a BC subfield in its first member: one long stream";
+            else if (m < 18 || std::memcmp(magic, kBgzfEof, 4) != 0 || std::memcmp(magic + 10, kBgzfEof + 10, 6) != 0) {
+                if (wantGunzip) stream = true;
+                else bgzfWhy = "gzip without a BC subfield in its first member: one long stream";
+            }
             else bgzf = true;
         }
-        if (bgzf) { /* the descriptor stays: pread */ }
+        if (bgzf || stream) { /* the descriptor stays: pread */ }
         else if (m >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
             g = gzdopen(fd, "rb");                 // takes the descriptor over
             if (!g) { ::close(fd); fd = -1; throw std::runtime_error("Input file not found"); }
@@ -634,6 +641,48 @@ struct ChunkReader {
             if (n <= 0) eof = true; else have += (size_t)n;
         }
     }
+    // --device-gunzip: the bytes kept from the span before and the next block of the file behind them (false once the span that
+    // ends the file has gone out).  Before the first span the text's first bytes are inflated here, with zlib, for what next()
+    // reads off them.
+    bool nextRaw(const char *&span, size_t &size, bool &final, bool verbose)
+    {
+        span = nullptr; size = 0; final = false;
+        if (rawDone) return false;
+        if (first) {
+            ScopedTimer tmCut(g_ht.cut);
+            gzFile h = gzopen(path.c_str(), "rb");
+            if (!h) throw std::runtime_error("Input file not found");
+            string head(65536, '\0');
+            const int got = gzread(h, &head[0], (unsigned)head.size());
+            gzclose(h);
+            if (got > 0) {
+                if (head[0] != '>' && head[0] != '@') throw std::runtime_error("Input does not start with @ or >.");
+                fasta = head[0] == '>';
+                protein = detectProtein(head.data(), (size_t)got, verbose);
+            }
+            first = false;
+        }
+        HugeVec<char> &D = buf[cur];
+        const size_t want = std::min<size_t>(std::max<size_t>(blockBytes, 1), 32u << 20);      // (a span's symbols take 16 bytes a byte on the device)
+        {
+            ScopedTimer tm(g_ht.read);
+            D.reserve(have + want);
+            const long n = readSome(D.data() + have, want);
+            if (n <= 0) eof = true; else have += (size_t)n;
+            if (fileSize > 0 && filePos >= fileSize) eof = true;
+        }
+        span = D.data(); size = have; final = eof;
+        if (final) rawDone = true;
+        return true;
+    }
+    void keepRaw(size_t from)                     // the span's bytes from `from` on open the next span
+    {
+        if (from == 0) return;
+        HugeVec<char> &D = buf[cur], &T = buf[cur ^ 1];
+        T.reserve(have - from + std::min<size_t>(std::max<size_t>(blockBytes, 1), 32u << 20) + (1u << 17));
+        std::memcpy(T.data(), D.data() + from, have - from);
+        have -= from; cur ^= 1;
+    }
     // The way back: the host reads the rest of the file, which starts at inflated byte `textAt`, through gzread -- from the
     // start of the span that holds that byte, the bytes before it dropped.
     void toGzread(uint64_t textAt)
@@ -644,7 +693,7 @@ struct ChunkReader {
         if (::lseek(fd, (off_t)fileAt, SEEK_SET) < 0) throw std::runtime_error("the input cannot be read again from where the device stopped");
         g = gzdopen(fd, "rb");
         if (!g) throw std::runtime_error("the input cannot be read again from where the device stopped");
-        fd = -1; bgzf = false;
+        fd = -1; bgzf = false; stream = false;
         gzbuffer(g, 1u << 20);
         vector<char> drop(1u << 16);
         for (uint64_t left = textAt - from; left > 0;) {
@@ -742,6 +791,7 @@ struct Params {
     bool bgzf = false;                             // --bgzf: the per-read file is a BGZF stream (blocked gzip), compressed where its text is made
     bool bgzfDynamic = false;                      // --bgzf-dynamic (implies --bgzf): device batches get a Huffman table of their own (KASA_BGZF_DYNAMIC); what the host writes stays zlib level 1
     bool deviceParse = false;                      // --device-parse: the input's text is parsed on the device (kasa_parse_*), the letters never come back
+    bool deviceGunzip = false;                     // --device-gunzip (implies --device-inflate): gzip input that is not BGZF -- one long stream -- goes up compressed too (kasa_gzip_parse_append)
     bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
     bool deviceFilter = false;                     // --device-filter (implies --device-parse, needs --filter): the two files of --filter are split on the device batch by batch (kasa_batch_filter)
     bool deviceFilterOn = false;                   // ... and this file's input takes that path (identifyFile decides)
@@ -1226,10 +1276,12 @@ struct Batcher {
             devParse = true;
         }
         if (paired && devParse) {
-            reader.reset(new ChunkReader(p.input, p.deviceInflate));
-            reader2.reset(new ChunkReader(p.input2, p.deviceInflate));
-            if (p.verbose) for (const ChunkReader *cr : {reader.get(), reader2.get()})
+            reader.reset(new ChunkReader(p.input, p.deviceInflate, p.deviceGunzip));
+            reader2.reset(new ChunkReader(p.input2, p.deviceInflate, p.deviceGunzip));
+            if (p.verbose) for (const ChunkReader *cr : {reader.get(), reader2.get()}) {
+                if (cr->stream) std::cout << "OUT: --device-gunzip: the stream of file " << (cr == reader.get() ? 1 : 2) << " is inflated on the device" << std::endl;
                 if (cr->bgzfWhy) std::cout << "OUT: --device-inflate: the host path is used for file " << (cr == reader.get() ? 1 : 2) << " (" << cr->bgzfWhy << ")" << std::endl;
+            }
             refill();
         } else if (paired) {
             ReadSet r1 = readInput(p.input, p.verbose, p.threads), r2 = readInput(p.input2, false, p.threads);
@@ -1237,7 +1289,8 @@ struct Batcher {
             appendPairs(pending, r1, r2);
             protein = pending.protein;
         } else {
-            reader.reset(new ChunkReader(p.input, devParse && p.deviceInflate));
+            reader.reset(new ChunkReader(p.input, devParse && p.deviceInflate, devParse && p.deviceGunzip));
+            if (reader->stream && p.verbose) std::cout << "OUT: --device-gunzip: the stream is inflated on the device" << std::endl;
             if (reader->bgzfWhy && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << reader->bgzfWhy << ")" << std::endl;
             refill();
             protein = reader->protein;
@@ -1270,6 +1323,19 @@ struct Batcher {
                 if (pending.size() != before || final) return;
             }
             // (the reader is a gzread reader now and stands at the first byte the device has not parsed)
+            if (!reader->next(chunk, chunkBytes, p.verbose)) return;
+            parsePiece(chunk, chunkBytes, reader->fasta, p.threads, 1u << 20, pending, parts, reader->chunkStart);
+            return;
+        }
+        if (devParse && reader->stream) {           // --device-gunzip: spans of the file's bytes, likewise
+            for (;;) {
+                bool final = false;
+                if (!reader->nextRaw(chunk, chunkBytes, final, p.verbose)) return;
+                if (pendPos > 0) { ReadSet rest = pending.slice(pendPos, pending.size(), 1, p.threads); pending = std::move(rest); pendPos = 0; }
+                const size_t before = pending.size();
+                if (!refillDeviceGzip(chunk, chunkBytes, final)) break;
+                if (pending.size() != before || final) return;
+            }
             if (!reader->next(chunk, chunkBytes, p.verbose)) return;
             parsePiece(chunk, chunkBytes, reader->fasta, p.threads, 1u << 20, pending, parts, reader->chunkStart);
             return;
@@ -1335,6 +1401,43 @@ struct Batcher {
         }
         const bool ok = pooled(ps, before, added, parsable, textParsed);
         if (ok) textParsed += nText;
+        else reader->toGzread(textParsed);
+        return ok;
+    }
+    // --device-gunzip: the same with a span of a plain gzip file's bytes (kasa_gzip_parse_append).  A stream that does not inflate
+    // ends the run; one whose block is longer than the span limit goes to the host like text the device parser does not take.
+    void gzipRefused(kasa_parser *ps, bool &spanLimit)
+    {
+        int zc = 0; uint64_t member = 0;
+        (void)kasa_gzip_parse_status(ps, &zc, &member, nullptr);
+        spanLimit = zc == KASA_INFLATE_SPAN;
+        if (!spanLimit) throw std::runtime_error(string(kasa_inflate_status_text(zc)) + " in gzip member " + std::to_string(member));
+        if (p.verbose) std::cout << "OUT: --device-gunzip: the host path is used (" << kasa_inflate_status_text(zc) << ")" << std::endl;
+    }
+    void gzipStats(kasa_parser *ps, int file)
+    {
+        uint64_t st[8] = {0};
+        int zc = 0; uint64_t member = 0;
+        if (kasa_gzip_parse_status(ps, &zc, &member, st)) throwLast();
+        std::cout << "OUT: --device-gunzip:" << (file ? " file " + std::to_string(file) + ":" : string()) << " chunks " << st[0] << ", confirmed " << st[2] << ", rejected " << st[3] << ", rounds " << st[4] << std::endl;
+    }
+    bool refillDeviceGzip(const char *span, size_t spanBytes, bool final)
+    {
+        std::lock_guard<std::mutex> lk(pool->mu);
+        kasa_parser *ps = pool->ps;
+        uint64_t before = 0, added = 0, nText = 0, keep = 0; int parsable = 0;
+        double up0 = 0, ps0 = 0, z0 = 0, up1 = 0, ps1 = 0, z1 = 0;
+        if (kasa_parse_sizes(ps, &before, nullptr, nullptr) || kasa_parse_stage_ms(ps, &up0, &ps0) || kasa_gzip_parse_ms(ps, &z0)) throwLast();
+        if (kasa_gzip_parse_append(ps, span, spanBytes, reader->fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &keep)) throwLast();
+        if (kasa_parse_stage_ms(ps, &up1, &ps1) || kasa_gzip_parse_ms(ps, &z1)) throwLast();
+        g_ht.uploadText += (up1 - up0) * 1e-3; g_ht.deviceParse += (ps1 - ps0) * 1e-3; g_ht.inflate += (z1 - z0) * 1e-3;
+        if (!parsable) {
+            int code = 0; uint64_t at = 0;
+            (void)kasa_parse_status(ps, &code, &at);
+            if (code == KASA_PARSE_INFLATE) { bool spanLimit = false; gzipRefused(ps, spanLimit); parsable = 0; }
+        }
+        const bool ok = pooled(ps, before, added, parsable, textParsed);
+        if (ok) { textParsed += nText; reader->keepRaw((size_t)keep); if (final && p.verbose) gzipStats(ps, 0); }
         else reader->toGzread(textParsed);
         return ok;
     }
@@ -1424,14 +1527,20 @@ struct Batcher {
         kasa_parser *ps = w ? pool->ps2 : pool->ps;
         uint64_t &parsedText = w ? textParsed2 : textParsed;
         const char *chunk = nullptr; size_t chunkBytes = 0; bool final = false;
-        if (cr.bgzf ? !cr.nextSpan(chunk, chunkBytes, final, p.verbose && w == 0) : !cr.next(chunk, chunkBytes, p.verbose && w == 0)) return 0;
+        if (cr.stream ? !cr.nextRaw(chunk, chunkBytes, final, p.verbose && w == 0)
+                      : cr.bgzf ? !cr.nextSpan(chunk, chunkBytes, final, p.verbose && w == 0) : !cr.next(chunk, chunkBytes, p.verbose && w == 0)) return 0;
         if (w == 0) protein = pending.protein = cr.protein;          // (the first file's alphabet, as on the host path)
         uint64_t added = 0, nText = 0, carry = 0, textStart = cr.chunkStart; int parsable = 0;
         {
             std::lock_guard<std::mutex> lk(pool->mu);
             double up0 = 0, ps0 = 0, z0 = 0, up1 = 0, ps1 = 0, z1 = 0;
             if (kasa_parse_stage_ms(ps, &up0, &ps0) || kasa_bgzf_parse_ms(ps, &z0)) throwLast();
-            if (cr.bgzf) {
+            if (cr.stream) {
+                textStart = parsedText;
+                uint64_t keep = 0;
+                if (kasa_gzip_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &keep)) throwLast();
+                if (parsable) { parsedText += nText; cr.keepRaw((size_t)keep); if (final && p.verbose) gzipStats(ps, w + 1); }
+            } else if (cr.bgzf) {
                 textStart = parsedText;
                 if (kasa_bgzf_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &carry)) throwLast();
                 if (parsable) parsedText += nText;
@@ -1442,12 +1551,13 @@ struct Batcher {
         if (parsable) return 1;
         int code = 0; uint64_t at = 0;
         (void)kasa_parse_status(ps, &code, &at);
-        if (code == KASA_PARSE_INFLATE) {
+        if (code == KASA_PARSE_INFLATE && cr.stream) { bool spanLimit = false; gzipRefused(ps, spanLimit); }
+        else if (code == KASA_PARSE_INFLATE) {
             int zc = 0; uint64_t member = 0;
             (void)kasa_bgzf_parse_status(ps, &zc, &member);
             throw std::runtime_error(string(kasa_inflate_status_text(zc)) + " in BGZF member " + std::to_string(cr.membersOut - membersIn(chunk, chunkBytes) + member));
         }
-        if (p.verbose) std::cout << "OUT: --device-pairs: the host parser takes over from byte " << textStart + at << " of file " << w + 1 << " (" << kasa_parse_status_text(code) << ")" << std::endl;
+        else if (p.verbose) std::cout << "OUT: --device-pairs: the host parser takes over from byte " << textStart + at << " of file " << w + 1 << " (" << kasa_parse_status_text(code) << ")" << std::endl;
         pairsToHost(w, chunk, chunkBytes);
         return -1;
     }
@@ -1478,7 +1588,7 @@ struct Batcher {
         for (int x = 0; x < 2; ++x) {
             ChunkReader &cr = x ? *reader2 : *reader;
             const char *c = nullptr; size_t cb = 0;
-            if (cr.bgzf) cr.toGzread(x ? textParsed2 : textParsed);   // (the reader is a gzread reader now and stands at the first byte the device has not parsed)
+            if (cr.bgzf || cr.stream) cr.toGzread(x ? textParsed2 : textParsed);   // (the reader is a gzread reader now and stands at the first byte the device has not parsed)
             else if (x == w) parsePiece(chunk, chunkBytes, cr.fasta, p.threads, 1u << 20, rest[x], parts, cr.chunkStart);
             while (cr.next(c, cb, false)) parsePiece(c, cb, cr.fasta, p.threads, 1u << 20, rest[x], parts, cr.chunkStart);
         }
@@ -2295,6 +2405,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         if (!why) poolDevice = p.devices[(size_t)devSlots[0]];
         else if (p.verbose) std::cout << "OUT: " << (pairs ? "--device-pairs" : "--device-parse") << ": the host parser is used (" << why << ")" << std::endl;
         if (why && p.deviceInflate && p.verbose) std::cout << "OUT: --device-inflate: the host path is used (" << why << ")" << std::endl;
+        if (why && p.deviceGunzip && p.verbose) std::cout << "OUT: --device-gunzip: the host path is used (" << why << ")" << std::endl;
         if (filterWhy && p.verbose) std::cout << "OUT: --device-filter: the host path is used (" << filterWhy << ")" << std::endl;
     }
     Batcher batcher(p, ixf, wantRows, maxKmersPerBatch, poolDevice);
@@ -2582,6 +2693,7 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "DevicePairs") flag("--device-pairs", val);
         else if (key == "DeviceFilter") flag("--device-filter", val);
         else if (key == "DeviceInflate") flag("--device-inflate", val);
+        else if (key == "DeviceGunzip") flag("--device-gunzip", val);
     }
     vector<string> out = {exe, mode};
     if (!kH.empty() && !kL.empty()) { out.push_back("-k"); out.push_back(kH); out.push_back(kL); }
@@ -3316,7 +3428,8 @@ static int run(int argc, char **argv)
     }
     if (argc >= 4 && a[1] == "parse-dump-device") {              // test tap: parse-dump's streamed half with the reads coming out of the device's pool
         const unsigned nt = (unsigned)std::stoul(a[3]);
-        ChunkReader cr(a[2]);
+        const bool gunzip = argc >= 5 && a[4] == "--device-gunzip";  // a plain .gz goes up compressed (kasa_gzip_parse_append)
+        ChunkReader cr(a[2], gunzip, gunzip);
         const char *chunk; size_t chunkBytes; ReadSet all; vector<ReadSet> parts;
         kasa_parser *ps = nullptr;
         if (kasa_parse_create(0, (uint64_t)kLongSequence, &ps)) throwLast();
@@ -3329,6 +3442,18 @@ static int run(int argc, char **argv)
             if (kasa_parse_fetch(ps, 0, n, q.lengths.data(), q.nameOff.data(), q.nameBlob.data(), q.off.data(), q.bases.data())) throwLast();
             all.appendSet(q, nt);
         };
+        if (cr.bgzf) throw std::runtime_error("parse-dump-device: BGZF input is not taken here");
+        uint64_t textParsed = 0; bool final = false;
+        while (cr.stream && cr.nextRaw(chunk, chunkBytes, final, false)) {
+            uint64_t added = 0, nText = 0, keep = 0; int parsable = 0;
+            if (kasa_gzip_parse_append(ps, chunk, chunkBytes, cr.fasta ? 1 : 0, final ? 1 : 0, &added, &parsable, &nText, &keep)) throwLast();
+            if (parsable) { textParsed += nText; cr.keepRaw((size_t)keep); continue; }
+            int code = 0, zc = 0; uint64_t at = 0, member = 0;
+            (void)kasa_parse_status(ps, &code, &at); (void)kasa_gzip_parse_status(ps, &zc, &member, nullptr);
+            if (code == KASA_PARSE_INFLATE) throw std::runtime_error(string(kasa_inflate_status_text(zc)) + " in gzip member " + std::to_string(member));
+            drainPool(); onDevice = false;
+            cr.toGzread(textParsed);                               // as the driver does: the host parser has the rest of the file
+        }
         while (cr.next(chunk, chunkBytes, false)) {
             uint64_t added = 0; int parsable = 0;
             if (onDevice) {
@@ -3425,6 +3550,7 @@ static int run(int argc, char **argv)
         else if (s == "--host-text") p.hostText = true;
         else if (s == "--device-parse") p.deviceParse = true;
         else if (s == "--device-inflate") p.deviceInflate = p.deviceParse = true;
+        else if (s == "--device-gunzip") p.deviceGunzip = p.deviceInflate = p.deviceParse = true;
         else if (s == "--device-pairs") p.devicePairs = p.deviceParse = true;
         else if (s == "--device-filter") p.deviceFilter = p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
