@@ -672,7 +672,7 @@ void kasa_build_destroy(kasa_builder *b);
  *   kasa_build_shrink      once per builder.  strategy 1: per taxon, the j-th record in index order (j = 1, 2, ...) goes iff
  *                          j == (uint64_t)d_m for some m, d_1 = step = 100.0 / fabsf(percentage) in double, d_m+1 = d_m +
  *                          step (no record goes when step < 1 or percentage = 0).  2: the halved index (64-bit K only, at most
- *                          65535 content rows with row 0): records with fewer than seven real letters go, the others are
+ *                          65535 content rows with row 0): records whose six low letters are all '^' go, the others are
  *                          fetched as 6-byte records {u32 low 30 bits of the k-mer, u16 content row} and the frequencies
  *                          are those of the full index.  3: records whose normalised Shannon entropy of the K letters
  *                          ('^' included) is 0.5 or less go.  A shrink that leaves no record fails kasa_build_finish

@@ -14,7 +14,7 @@
 //             the ordinal is in the host's table {floor(d_m)} (a bitmap)             [edit_rank_hist, edit_nth_flag, edit_carry]
 //   entropy : the multiplicity of every distinct letter of a k-mer as a popcount, the normalised Shannon entropy in double
 //                                                                                                      [edit_entropy_flag]
-//   halved  : kept iff the seventh letter (bits 25-29) is not '^'; 6-byte records {u32 low 30 bits, u16 content row}
+//   halved  : kept iff the six low letters (bits 0-29) are not all '^'; 6-byte records {u32 low 30 bits, u16 content row}
 //                                                                                         [edit_half_flag, edit_emit_half]
 //   taxa    : after the finish, over the packed file records: how many distinct k-mers carry exactly c records (redundancy,
 //             Shrink.hpp:35-72).  A record that opens a k-mer's run contributes its index to a running maximum (rocPRIM), so
@@ -65,12 +65,14 @@ __global__ void edit_drop_flag_kernel(const uint32_t *__restrict__ v, uint64_t n
         f[i] = drop[v[i]] ? 0u : 1u;
 }
 
-// halved (Shrink.hpp:78-143): an entry whose six low letters are all '^' holds fewer than seven real letters and goes
+// halved (Shrink.hpp:78-143): an entry whose six low letters are all '^' goes (Shrink.hpp:108 compares the low 30 bits with
+// that one value); a '^' at letter 5 over a real letter below it -- amino-acid input may hold '^' or '~' -- stays
+static constexpr uint32_t HALF_SIX_PADS = 30u * ((1u << 25) | (1u << 20) | (1u << 15) | (1u << 10) | (1u << 5) | 1u);   // 1039104990
 template <class Key>
 __global__ void edit_half_flag_kernel(const Key *__restrict__ k, uint64_t n, uint32_t *__restrict__ f)
 {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        f[i] = (uint32_t)((k[i] >> 25) & 31) != 30u ? 1u : 0u;
+        f[i] = ((uint32_t)k[i] & 0x3FFFFFFFu) != HALF_SIX_PADS ? 1u : 0u;
 }
 
 // entropy (Shrink.hpp:152-236): H = -sum over the distinct letters (c / K) log2(c / K), '^' included; kept iff H ln2 / ln22 > 0.5.

@@ -30,6 +30,7 @@ KEY128_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")], align=False)  # a 128-bi
 K64 = 12  # letters per packed k-mer in a 64-bit index
 K128 = 25  # ... in a 128-bit index (source/utils/uint128_t.hpp, main.cpp --kH)
 TRIE_LETTERS = 6
+HALF_SIX_PADS = 1039104990  # six '^' (30) in the low 30 bits: the entries `shrink -s 2` drops (Shrink.hpp:108)
 
 
 def is_wide(kmer: np.ndarray) -> bool:
@@ -265,12 +266,12 @@ def write_index(ix: Index, prefix: str, content_path: str) -> None:
 
 
 def write_index_halved(ix: Index, prefix: str) -> None:
-    """The index of `shrink -s 2` (source/modes/Shrink.hpp:78-143): entries with fewer than seven real letters (their
-    seventh letter is already '^') are dropped, the others keep the low 30 bits of the k-mer and the dense taxon index
+    """The index of `shrink -s 2` (source/modes/Shrink.hpp:78-143): entries whose six low letters are all '^' (low 30 bits ==
+    HALF_SIX_PADS, Shrink.hpp:108) are dropped, the others keep the low 30 bits of the k-mer and the dense taxon index
     -- {u32, u16} = 6 bytes -- next to a `_trie` that supplies the upper 30 bits.  64-bit indices only."""
     if is_wide(ix.kmer):
         raise NotImplementedError("the halved format exists for 64-bit indices only")
-    keep = ((ix.kmer >> np.uint64(25)) & np.uint64(31)) != np.uint64(30)
+    keep = (ix.kmer & np.uint64(0x3FFFFFFF)) != np.uint64(HALF_SIX_PADS)
     km, tax, taxid = ix.kmer[keep], ix.tax[keep], ix.taxid[keep]
     rec = np.zeros(km.shape[0], dtype=HALF_DTYPE)
     rec["low"] = (km & np.uint64(0x3FFFFFFF)).astype(np.uint32)
