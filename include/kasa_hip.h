@@ -495,6 +495,11 @@ int kasa_batch_query_count(kasa_ctx *ctx, uint64_t *n);
 /* Queries of the batch after encode / after sort (k-mer, read id); for parity tests.  A k-mer is one
  * uint64_t with a 64-bit index, two (low word, high word) with a 128-bit index. */
 int kasa_batch_fetch_queries(kasa_ctx *ctx, void *kmers, uint32_t *reads, uint64_t n);
+/* Test tap: the payload word of every query as kasa_batch_encode left it, in emission order -- the query's slot in the
+ * read-major, sorted-within-read record array where the encoder ranked the reads' k-mers (kasa_ctx_batch_stats: stats8[7]
+ * = 1), the read id otherwise.  A plain copy to the host: no kernel runs, nothing of the batch changes.  KASA_E_STATE unless
+ * the batch was encoded by kasa_batch_encode and not sorted yet (the sort moves and then replaces these words). */
+int kasa_batch_fetch_payload(kasa_ctx *ctx, uint32_t *out, uint64_t n);
 /* Test tap: install (k-mer, read id) queries directly instead of upload + encode (any order). */
 int kasa_batch_set_queries(kasa_ctx *ctx, const void *kmers, const uint32_t *reads, uint64_t n, int64_t nReads);
 /* Test tap (like kasa_batch_set_queries and kasa_text_dtoa): replace the per-read score rows of the batch that is loaded

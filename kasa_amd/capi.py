@@ -24,7 +24,7 @@ EXPORTS = [
     "kasa_batch_sort_and_range", "kasa_batch_lookup_score", "kasa_batch_group", "kasa_batch_group_to", "kasa_batch_score", "kasa_batch_records_size",
     "kasa_batch_records_fetch", "kasa_batch_records_import", "kasa_batch_scores_size", "kasa_batch_scores_fetch",
     "kasa_profile_reset", "kasa_profile_absorb", "kasa_profile_fetch", "kasa_profile_export_limbs", "kasa_profile_import_limbs", "kasa_profile_allreduce",
-    "kasa_ctx_stage_ms", "kasa_ctx_stage_reset", "kasa_ctx_kernel_ms", "kasa_ctx_batch_stats", "kasa_batch_query_count", "kasa_batch_fetch_queries",
+    "kasa_ctx_stage_ms", "kasa_ctx_stage_reset", "kasa_ctx_kernel_ms", "kasa_ctx_batch_stats", "kasa_batch_query_count", "kasa_batch_fetch_queries", "kasa_batch_fetch_payload",
     "kasa_batch_fetch_lookup", "kasa_ctx_device_bytes", "kasa_device_memory", "kasa_batch_bytes_per_query", "kasa_ctx_counters", "kasa_ctx_third_pass_reads", "kasa_ctx_synchronize", "kasa_batch_set_queries", "kasa_batch_set_scores", "kasa_ctx_debug",
     "kasa_refbatch_budget", "kasa_refbatch_sequence_cost", "kasa_refbatch_read_overhead", "kasa_refbatch_cut",
     "kasa_batch_rank", "kasa_batch_rank_fetch", "kasa_host_alloc", "kasa_host_free", "kasa_thread_device",
@@ -1288,6 +1288,14 @@ class Context:
         rd = np.zeros(n, dtype=np.uint32)
         _check(lib().kasa_batch_fetch_queries(self.h, _p(km), _p(rd), C.c_uint64(n)))
         return km, rd
+
+    def payload(self) -> np.ndarray:
+        """kasa_batch_fetch_payload (test tap): the payload words as encode() left them -- slots where
+        batch_stats()["encoder_ranked"], read ids else.  Only between encode() and sort_and_range()."""
+        _check(lib().kasa_batch_fetch_payload(self.h, None, C.c_uint64(0)))            # (the state, before anything is sized)
+        out = np.zeros(self.query_count(), dtype=np.uint32)
+        _check(lib().kasa_batch_fetch_payload(self.h, _p(out), C.c_uint64(out.shape[0])))
+        return out
 
     def set_queries(self, kmers: np.ndarray, reads: np.ndarray, n_reads: int):
         from .formats import KEY128_DTYPE

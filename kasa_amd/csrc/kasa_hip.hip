@@ -9060,6 +9060,18 @@ extern "C" int kasa_batch_fetch_queries(kasa_ctx *c, void *kmers, uint32_t *read
     return KASA_OK;
 }
 
+// test tap: the payload words as the encoder left them (slots where it ranked the reads' k-mers, read ids else); a copy, nothing more
+extern "C" int kasa_batch_fetch_payload(kasa_ctx *c, uint32_t *out, uint64_t n)
+{
+    if (!c) return fail(KASA_E_ARG, "ctx is NULL");
+    if (c->state != 2 || !c->readsUploaded) return fail(KASA_E_STATE, "kasa_batch_fetch_payload: needs a batch that kasa_batch_encode has encoded and nothing has sorted yet");
+    if (n > c->nQ || (n && !out)) return fail(KASA_E_ARG, "kasa_batch_fetch_payload: n exceeds the batch, or out is NULL");
+    HIPCHK(hipSetDevice(c->ix->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n) HIPCHK(hipMemcpy(out, c->qRead, n * 4, hipMemcpyDeviceToHost));
+    return KASA_OK;
+}
+
 static int batch_set_queries_impl(kasa_ctx *c, const void *kmers, const uint32_t *reads, uint64_t n, int64_t nReads)
 {
     if (!c) return fail(KASA_E_ARG, "ctx is NULL");
