@@ -6,7 +6,7 @@ INDEX  = kasa_amd/host/kasa_index
 
 all: $(LIB) $(HOST) $(INDEX) oracle
 
-$(LIB): kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp kasa_amd/csrc/stdsort_order.h kasa_amd/csrc/kasa_radix.h kasa_amd/csrc/kasa_text.h kasa_amd/csrc/kasa_replay.h kasa_amd/csrc/kasa_build.h kasa_amd/csrc/kasa_edit.h kasa_amd/csrc/kasa_parse.h kasa_amd/csrc/kasa_bgzf.h kasa_amd/csrc/kasa_inflate.h kasa_amd/csrc/kasa_gunzip.h kasa_amd/host/grisu_powers.inc include/kasa_hip.h
+$(LIB): kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp kasa_amd/csrc/stdsort_order.h kasa_amd/csrc/kasa_radix.h kasa_amd/csrc/kasa_text.h kasa_amd/csrc/kasa_replay.h kasa_amd/csrc/kasa_build.h kasa_amd/csrc/kasa_edit.h kasa_amd/csrc/kasa_spill.h kasa_amd/csrc/kasa_spill_plan.h kasa_amd/csrc/kasa_parse.h kasa_amd/csrc/kasa_bgzf.h kasa_amd/csrc/kasa_inflate.h kasa_amd/csrc/kasa_gunzip.h kasa_amd/host/grisu_powers.inc include/kasa_hip.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wall -Wno-unused-result -o $@ kasa_amd/csrc/kasa_hip.hip kasa_amd/csrc/kasa_refbatch.cpp -ldl -Wl,-rpath,/opt/rocm/lib
 
 $(HOST): kasa_amd/host/kasa_identify.cpp kasa_amd/host/grisu_powers.inc include/kasa_hip.h $(LIB)
@@ -37,6 +37,11 @@ tools/inflate_host_check: tools/inflate_host_check.cpp kasa_amd/csrc/kasa_inflat
 tools/gunzip_host_check: tools/gunzip_host_check.cpp kasa_amd/csrc/kasa_gunzip.h kasa_amd/csrc/kasa_inflate.h include/kasa_hip.h
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -o $@ $<
 
+# the slab plan of kasa_spill_plan.h (builds larger than device memory) likewise:
+#   tools/spill_plan_check FILE ...    (FILE: "letters budget runs", then per run its length and its keys; tests/test_spill_cpu.py writes them)
+tools/spill_plan_check: tools/spill_plan_check.cpp kasa_amd/csrc/kasa_spill_plan.h
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -pthread -o $@ $<
+
 test:
 	python -m pytest tests -q -m "not gpu"
 
@@ -44,7 +49,7 @@ test-gpu:
 	python -m pytest tests -q -m gpu
 
 clean:
-	rm -f $(LIB) $(HOST) $(INDEX) kasa_amd/libkasa_hip_asan.so kasa_amd/host/kasa_identify_asan tools/inflate_host_check tools/gunzip_host_check
+	rm -f $(LIB) $(HOST) $(INDEX) kasa_amd/libkasa_hip_asan.so kasa_amd/host/kasa_identify_asan tools/inflate_host_check tools/gunzip_host_check tools/spill_plan_check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle test test-gpu clean asan

@@ -641,8 +641,9 @@ int kasa_ctx_synchronize(kasa_ctx *ctx);
  *   kasa_build_add     any number of calls, as a parser hands sequences over: nSeq sequences (bases, offsets[nSeq + 1]),
  *                      seqTaxId[s] one of taxIds (KASA_E_ARG otherwise: unknown accessions are the host's to skip,
  *                      Read.hpp:2352-2368), protein = amino-acid letters (kASA::detectAlphabet per file).
- *   kasa_build_finish  the last brick, the merges (KASA_E_LIMIT when the unique result plus one merge buffer does not fit
- *                      the device), records, trie and frequencies.  nRecords = unique (k-mer, tax ID) entries, nTrie =
+ *   kasa_build_finish  the last brick, the merges (a result that does not fit the device with one merge buffer is built by
+ *                      slabs, see "indices larger than device memory" below; KASA_E_LIMIT only for a builder with edits, or
+ *                      when a single 6-letter prefix exceeds a slab), records, trie and frequencies.  nRecords = unique (k-mer, tax ID) entries, nTrie =
  *                      trie entries.
  *   kasa_build_fetch   records: nRecords packed file records, 12 bytes {u64 kmer, u32 taxid} or 20 bytes {u64 lo, u64 hi,
  *                      u32 taxid}; triePrefix / trieCount: nTrie entries of the `_trie` file; freq: nTaxa x K, row r =
@@ -697,6 +698,46 @@ int kasa_build_drop_taxa(kasa_builder *b, const uint32_t *taxIds, uint64_t n);
 int kasa_build_shrink(kasa_builder *b, int strategy, float percentage);
 int kasa_build_edit_stats(kasa_builder *b, uint64_t *stats4);
 int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, uint64_t *distinctKmers);
+
+/* ---- build: indices larger than device memory ---------------------------------------------------------------------------
+ * The reference builds any size through STXXL temporaries (Build.hpp:305-477).  Here the bricks' runs leave the device for
+ * ordinary (pageable) host memory once they outgrow a resident budget, and the finish walks the key space in slabs: intervals
+ * of 6-letter trie prefixes, so that no k-mer, duplicate pair or trie entry is split.  A slab's slices are uploaded, merged,
+ * emitted and trie'd by the kernels of the in-core finish; the frequency histograms live across the slabs.  The slabs' records
+ * and trie entries concatenate to the index; a builder that never spills runs the in-core finish as before.
+ *   kasa_build_set_resident  before the first kasa_build_add (KASA_E_STATE after it, and after an edit call):
+ *                          maxResidentRecords = the most input records a slab may bring to the device.  0 (the default) =
+ *                          automatic: the builder spills once the in-core finish of the runs it holds is no longer sure to
+ *                          fit (36 bytes per record with 64-bit keys, 52 with 128-bit, against 0.8 of the free memory), or
+ *                          when the finish's memory check refuses a merge, and sizes the slabs by the same arithmetic.
+ *                          Otherwise: as soon as the runs on the device hold more records than this they go to the host,
+ *                          and every later run follows.
+ *   kasa_build_finish_begin  the last brick and the plan; *nSlabs = the slabs to take.  KASA_E_LIMIT names the prefix, its
+ *                          input records and the budget when one prefix alone exceeds the budget; KASA_E_NOMEM when the
+ *                          host has no memory for a run.
+ *   kasa_build_slab        slab 0, 1, .. nSlabs - 1 in order, each once (KASA_E_STATE otherwise): *nRecords and *nTrie of
+ *                          this slab.
+ *   kasa_build_fetch_slab  records [first, first + count) of the current slab and its trie entries (all nTrie of them);
+ *                          any pointer may be NULL.
+ *   kasa_build_finish_end  after the last slab: the totals.  Then kasa_build_fetch(b, NULL, NULL, NULL, freq) gives the
+ *                          frequency rows.
+ *   kasa_build_spill_stats stats8 = {runs spilled, records spilled, slabs, the largest slab's input records, the heaviest
+ *                          prefix's input records, host microseconds of the copies host -> device, device -> host, 0}; all
+ *                          zero for a builder that did not spill.
+ * On a builder that did not spill, kasa_build_finish_begin is kasa_build_finish and reports one slab, kasa_build_slab(b, 0)
+ * returns the totals and kasa_build_fetch_slab is kasa_build_fetch_range plus the trie: a host needs one code path.
+ * kasa_build_finish on a builder that spilled takes every slab and gathers records and trie in host memory, so
+ * kasa_build_fetch and kasa_build_fetch_range keep working, bounded by the host's RAM; after the streaming calls they return
+ * KASA_E_STATE for records and trie.  kasa_build_stats' merges counts the merges of all slabs.
+ * Edits need the runs on the device: kasa_build_add_index, kasa_build_drop_taxa and kasa_build_shrink return KASA_E_STATE on a
+ * builder with a non-zero budget or spilled runs, a builder with edits never spills (KASA_E_LIMIT as before), and
+ * kasa_build_taxa_histogram returns KASA_E_STATE after a spilled finish. */
+int kasa_build_set_resident(kasa_builder *b, uint64_t maxResidentRecords);
+int kasa_build_finish_begin(kasa_builder *b, uint64_t *nSlabs);
+int kasa_build_slab(kasa_builder *b, uint64_t slab, uint64_t *nRecords, uint64_t *nTrie);
+int kasa_build_fetch_slab(kasa_builder *b, uint64_t first, uint64_t count, void *records, uint32_t *triePrefix, uint64_t *trieCount);
+int kasa_build_finish_end(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie);
+int kasa_build_spill_stats(kasa_builder *b, uint64_t *stats8);
 
 /* ---- parse: FASTA / FASTQ text -> reads, on the device ------------------------------------------------------------------
  * The producer of what kasa_batch_upload_device takes: the text of whole records goes in, the reads come out in device

@@ -11,7 +11,7 @@ HOST_SRCS = [os.path.join(HERE, "csrc", "kasa_refbatch.cpp")]   # host-only part
 SO = os.path.join(HERE, "libkasa_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "kasa_hip.h")
 CSRC_HEADERS = [os.path.join(HERE, "csrc", "stdsort_order.h"), os.path.join(HERE, "csrc", "kasa_radix.h"), os.path.join(HERE, "csrc", "kasa_text.h"), os.path.join(HERE, "csrc", "kasa_replay.h"),
-                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h"), os.path.join(HERE, "csrc", "kasa_filter.h"),
+                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_spill.h"), os.path.join(HERE, "csrc", "kasa_spill_plan.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h"), os.path.join(HERE, "csrc", "kasa_filter.h"),
                 os.path.join(HERE, "host", "grisu_powers.inc")]
 
 
@@ -92,6 +92,21 @@ def build_gunzip_check(force: bool = False) -> str:
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
                            "-o", GUNZIP_CHECK_BIN, GUNZIP_CHECK_SRC])
     return GUNZIP_CHECK_BIN
+
+
+SPILL_PLAN_CHECK_SRC = os.path.join(os.path.dirname(HERE), "tools", "spill_plan_check.cpp")
+SPILL_PLAN_CHECK_BIN = os.path.join(os.path.dirname(HERE), "tools", "spill_plan_check")
+
+
+def build_spill_plan_check(force: bool = False) -> str:
+    """tools/spill_plan_check: the slab plan of csrc/kasa_spill_plan.h for the CPU under AddressSanitizer + UBSan (a stand-alone
+    program; nothing is preloaded)."""
+    newest = max(os.path.getmtime(p) for p in (SPILL_PLAN_CHECK_SRC, os.path.join(HERE, "csrc", "kasa_spill_plan.h")))
+    if not force and os.path.exists(SPILL_PLAN_CHECK_BIN) and os.path.getmtime(SPILL_PLAN_CHECK_BIN) >= newest:
+        return SPILL_PLAN_CHECK_BIN
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-pthread",
+                           "-o", SPILL_PLAN_CHECK_BIN, SPILL_PLAN_CHECK_SRC])
+    return SPILL_PLAN_CHECK_BIN
 
 
 if __name__ == "__main__":

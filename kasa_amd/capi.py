@@ -36,6 +36,7 @@ EXPORTS = [
     "kasa_device_alloc", "kasa_device_free", "kasa_device_write", "kasa_device_read", "kasa_batch_records_pack_size", "kasa_batch_records_pack", "kasa_batch_records_unpack",
     "kasa_build_create", "kasa_build_add", "kasa_build_finish", "kasa_build_fetch", "kasa_build_fetch_range", "kasa_build_stats", "kasa_build_destroy",
     "kasa_build_add_index", "kasa_build_drop_taxa", "kasa_build_shrink", "kasa_build_edit_stats", "kasa_build_taxa_histogram",
+    "kasa_build_set_resident", "kasa_build_finish_begin", "kasa_build_slab", "kasa_build_fetch_slab", "kasa_build_finish_end", "kasa_build_spill_stats",
     "kasa_encode_group_reads",
     "kasa_parse_create", "kasa_parse_append", "kasa_parse_status", "kasa_parse_status_text", "kasa_parse_sizes", "kasa_parse_fetch", "kasa_parse_take",
     "kasa_parse_tile_bytes", "kasa_parse_stage_ms", "kasa_parse_destroy",
@@ -191,6 +192,12 @@ def lib():
         L.kasa_build_shrink.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.kasa_build_edit_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_build_taxa_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kasa_build_set_resident.argtypes = [C.c_void_p, C.c_uint64]
+        L.kasa_build_finish_begin.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_build_slab.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kasa_build_fetch_slab.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_build_finish_end.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kasa_build_spill_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.kasa_parse_create.argtypes = [C.c_int, C.c_uint64, C.c_void_p]
         L.kasa_parse_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         L.kasa_parse_status.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -546,12 +553,16 @@ class DeviceIndex:
 
 class Builder:
     """`kASA build` on the device (kasa_build_*): sequences tagged with tax IDs -> the records, trie and frequencies of an
-    index.  K = 12 or 25 letters, frames = 3 or 1 (--one); max_pairs_per_brick = 0: sized from the device's free memory."""
+    index.  K = 12 or 25 letters, frames = 3 or 1 (--one); max_pairs_per_brick = 0: sized from the device's free memory.
+    max_resident_records: the most input records a slab of the finish brings to the device -- once the runs on the device hold
+    more, they live in host memory and the index is finished slab by slab (0: only when the device's memory asks for it)."""
 
+    SPILL_STATS = ("runs_spilled", "records_spilled", "slabs", "largest_slab_input", "heaviest_prefix_input", "upload_us", "download_us")
     STATS = ("pairs_in", "bricks", "merges", "records_out", "encode_us", "sort_unique_us", "merge_us", "emit_us")
     EDIT_STATS = ("index_in", "dropped_delete", "dropped_shrink", "edit_us")
 
-    def __init__(self, taxids, K: int = 12, frames: int = 3, codon_lut=None, max_pairs_per_brick: int = 0, device: int = 0):
+    def __init__(self, taxids, K: int = 12, frames: int = 3, codon_lut=None, max_pairs_per_brick: int = 0, device: int = 0,
+                 max_resident_records: int = 0):
         self.K = K
         self.taxids = np.ascontiguousarray(taxids, dtype=np.uint32)
         lut = np.ascontiguousarray(codon_lut, dtype=np.uint8) if codon_lut is not None else None
@@ -560,6 +571,54 @@ class Builder:
                                        C.c_uint32(self.taxids.shape[0]), C.c_uint64(max_pairs_per_brick), C.byref(h)))
         self.h = h
         self.n_records = self.n_trie = None
+        if max_resident_records:
+            self.set_resident(max_resident_records)
+
+    def set_resident(self, max_resident_records: int):
+        _check(lib().kasa_build_set_resident(self.h, C.c_uint64(max_resident_records)))
+
+    def spill_stats(self) -> dict:
+        s = np.zeros(8, dtype=np.uint64)
+        _check(lib().kasa_build_spill_stats(self.h, _p(s)))
+        return dict(zip(self.SPILL_STATS, (int(x) for x in s)))
+
+    def finish_begin(self) -> int:
+        n = C.c_uint64(0)
+        _check(lib().kasa_build_finish_begin(self.h, C.byref(n)))
+        return int(n.value)
+
+    def slab(self, i: int):
+        """slab i (in order, each once): its (records, trie entries)"""
+        n, m = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_build_slab(self.h, C.c_uint64(i), C.byref(n), C.byref(m)))
+        return int(n.value), int(m.value)
+
+    def fetch_slab(self, n: int, m: int):
+        """(records, trie prefixes, trie counts) of the current slab, of the n records and m trie entries slab() reported"""
+        from .formats import REC_DTYPE, REC128_DTYPE, HALF_DTYPE
+        rec = np.zeros(n, dtype=HALF_DTYPE if getattr(self, "halved", False) else (REC128_DTYPE if self.K == 25 else REC_DTYPE))
+        tp, tc = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint64)
+        _check(lib().kasa_build_fetch_slab(self.h, C.c_uint64(0), C.c_uint64(n), _p(rec), _p(tp), _p(tc)))
+        return rec, tp, tc
+
+    def finish_end(self):
+        n, m = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().kasa_build_finish_end(self.h, C.byref(n), C.byref(m)))
+        self.n_records, self.n_trie = int(n.value), int(m.value)
+        return self.n_records, self.n_trie
+
+    def finish_slabs(self):
+        """The finish slab by slab: yields (records, trie prefixes, trie counts) per slab -- file records of REC_DTYPE or
+        REC128_DTYPE; the slabs' arrays concatenate to the index.  Afterwards n_records and n_trie hold the totals and
+        fetch_freq() the frequency rows.  A builder that did not spill yields one slab."""
+        for i in range(self.finish_begin()):
+            yield self.fetch_slab(*self.slab(i))
+        self.finish_end()
+
+    def fetch_freq(self) -> np.ndarray:
+        freq = np.zeros((self.taxids.shape[0], self.K), dtype=np.uint64)
+        _check(lib().kasa_build_fetch(self.h, None, None, None, _p(freq)))
+        return freq
 
     def add(self, bases: np.ndarray, offsets: np.ndarray, seq_taxid: np.ndarray, protein: bool = False):
         bases = np.ascontiguousarray(bases, dtype=np.uint8)

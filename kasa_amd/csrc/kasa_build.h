@@ -16,6 +16,7 @@
 // Counts and offsets are 64-bit throughout; a single radix sort (one brick) holds fewer than 2^32 pairs.
 #pragma once
 #include <memory>
+#include "kasa_spill_plan.h"
 
 namespace kasa_build_impl {
 
@@ -227,6 +228,21 @@ struct kasa_builder {
     bool halved = false, freqDone = false;
     uint64_t indexIn = 0, droppedDelete = 0, droppedShrink = 0;
     double msEdit = 0;                     // device ms of the loads and the filters
+    // building an index larger than device memory (kasa_spill.h): runs in host memory, merged and emitted in key-range slabs
+    uint64_t resident = 0;                 // kasa_build_set_resident: the most input records of a slab (0: sized by the device)
+    bool added = false, edited = false;    // kasa_build_add / an edit call was made
+    bool spilled = false;                  // the runs live in hostRuns; every new run follows them
+    std::vector<kasa_spill_plan::HostRun> hostRuns;
+    kasa_spill_plan::Plan plan;
+    int phase = 0;                         // 0: adding, 1: kasa_build_finish_begin done, 2: kasa_build_finish_end done
+    uint64_t slabNext = 0, totalRec = 0, totalTrie = 0;
+    bool collected = false;                // kasa_build_finish on a spilled builder: records and trie of all slabs, in host memory
+    std::vector<uint8_t> hRec;
+    std::vector<uint32_t> hTriePrefix;
+    std::vector<uint64_t> hTrieCount;
+    DevBuf freqHist, freqExtra;            // the frequency histograms, kept from the first slab to the last
+    uint64_t spillRuns = 0, spillRecords = 0;
+    double usUp = 0, usDown = 0;           // host microseconds of the copies host -> device, device -> host
     int keyBytes() const { return wide ? 16 : 8; }
     int recBytes() const { return halved ? 6 : (wide ? 20 : 12); }
 };
@@ -236,6 +252,9 @@ namespace kasa_build_impl {
 // kasa_edit.h: the index runs' merges and the filters after the brick merges; the 6-byte records of a halved index
 template <class Key> static int edit_finish(kasa_builder *b);
 template <class Key> static int edit_emit_halved(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n);
+// kasa_spill.h: a new run joins the spilled ones (nothing for a builder that does not spill); the finish, in one call or by slabs
+template <class Key> static int spill_after_brick(kasa_builder *b);
+template <class Key> static int finish_all(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie);
 
 // elapsed device time of a stage: events around it, read after the stream has drained
 struct StageClock {
@@ -365,7 +384,7 @@ static int flush_brick(kasa_builder *b)
     b->runs.push_back(std::move(run));
     ++b->bricks;
     reset();
-    return KASA_OK;
+    return spill_after_brick<Key>(b);
 }
 
 template <class Key>
@@ -399,61 +418,85 @@ static int merge_two(kasa_builder *b, kasa_builder::Run &A, kasa_builder::Run &B
     return KASA_OK;
 }
 
-// the frequency rows by rank of the run (k, v, n) into b->freqR
+// the frequency rows by rank into b->freqR in three steps: the histograms zeroed, the run (k, v, n) counted into them (any
+// number of runs: the slabs of kasa_spill.h), the running sums
 template <class Key>
-static int freq_into(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n)
+static int freq_zero(kasa_builder *b)
 {
     const uint32_t nRank = (uint32_t)b->ids.size();
     constexpr int KL = KeyTraits<Key>::LETTERS;
     int rc;
-    DevBuf hist, extra;
-    if ((rc = b->freqR.reserve((size_t)nRank * KL * 8 + 64)) || (rc = hist.reserve((size_t)nRank * (KL + 1) * 8 + 64)) || (rc = extra.reserve((size_t)nRank * KL * 8 + 64))) return rc;
-    HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nRank * (KL + 1) * 8, b->stream));
-    HIPCHK(hipMemsetAsync(extra.p, 0, (size_t)nRank * KL * 8, b->stream));
+    if ((rc = b->freqR.reserve((size_t)nRank * KL * 8 + 64)) || (rc = b->freqHist.reserve((size_t)nRank * (KL + 1) * 8 + 64)) || (rc = b->freqExtra.reserve((size_t)nRank * KL * 8 + 64))) return rc;
+    HIPCHK(hipMemsetAsync(b->freqHist.p, 0, (size_t)nRank * (KL + 1) * 8, b->stream));
+    HIPCHK(hipMemsetAsync(b->freqExtra.p, 0, (size_t)nRank * KL * 8, b->stream));
+    return KASA_OK;
+}
+template <class Key>
+static int freq_accumulate(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n)
+{
+    const uint32_t nRank = (uint32_t)b->ids.size();
+    constexpr int KL = KeyTraits<Key>::LETTERS;
     if (n) {
         if ((uint64_t)nRank * (KL + 1) <= (uint64_t)FREQ_LDS_CELLS)
-            bld_freq_kernel<Key, true><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
+            bld_freq_kernel<Key, true><<<grid_for(n, 256, 1024), 256, 0, b->stream>>>(k, v, n, nRank, b->freqHist.as<unsigned long long>(), b->freqExtra.as<unsigned long long>());
         else
-            bld_freq_kernel<Key, false><<<grid_for(n, 256, 8192), 256, 0, b->stream>>>(k, v, n, nRank, hist.as<unsigned long long>(), extra.as<unsigned long long>());
+            bld_freq_kernel<Key, false><<<grid_for(n, 256, 8192), 256, 0, b->stream>>>(k, v, n, nRank, b->freqHist.as<unsigned long long>(), b->freqExtra.as<unsigned long long>());
         HIPCHK(hipGetLastError());
     }
-    bld_freq_final_kernel<<<blocks_for(nRank, 256), 256, 0, b->stream>>>(hist.as<unsigned long long>(), extra.as<unsigned long long>(), nRank, KL, b->freqR.as<uint64_t>());
+    return KASA_OK;
+}
+template <class Key>
+static int freq_final(kasa_builder *b)
+{
+    const uint32_t nRank = (uint32_t)b->ids.size();
+    constexpr int KL = KeyTraits<Key>::LETTERS;
+    bld_freq_final_kernel<<<blocks_for(nRank, 256), 256, 0, b->stream>>>(b->freqHist.as<unsigned long long>(), b->freqExtra.as<unsigned long long>(), nRank, KL, b->freqR.as<uint64_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(b->stream));                          // (hist and extra go out of scope here)
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->freqHist.release(); b->freqExtra.release();
+    return KASA_OK;
+}
+template <class Key>
+static int freq_into(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n)
+{
+    int rc;
+    if ((rc = freq_zero<Key>(b)) || (rc = freq_accumulate<Key>(b, k, v, n))) return rc;
+    return freq_final<Key>(b);
+}
+
+// the runs merged pairwise, level by level, until one is left: every record takes part in log2(runs) merges.  When a merge fails
+// the runs stay whole -- those merged so far and the rest -- and the caller may go on by slabs (kasa_spill.h).
+template <class Key>
+static int merge_runs(kasa_builder *b, std::vector<kasa_builder::Run> &runs)
+{
+    int rc;
+    while (runs.size() > 1) {
+        std::vector<kasa_builder::Run> next;
+        for (size_t i = 0; i + 1 < runs.size(); i += 2) {
+            kasa_builder::Run m;
+            if ((rc = merge_two<Key>(b, runs[i], runs[i + 1], m))) {
+                for (size_t j = i; j < runs.size(); ++j) next.push_back(std::move(runs[j]));
+                runs.swap(next);
+                return rc;
+            }
+            runs[i].k.release(); runs[i].v.release(); runs[i + 1].k.release(); runs[i + 1].v.release();
+            next.push_back(std::move(m));
+        }
+        if (runs.size() % 2) next.push_back(std::move(runs.back()));
+        runs.swap(next);
+    }
     return KASA_OK;
 }
 
+// b->result -> the file records in b->rec and the trie in b->triePrefix / trieCount (b->nTrie entries)
 template <class Key>
-static int finish_impl(kasa_builder *b)
+static int emit_result(kasa_builder *b)
 {
     int rc;
-    if ((rc = flush_brick<Key>(b))) return rc;
-    // the brick buffers are not needed any more: their memory goes to the merges
-    for (DevBuf *d : {&b->dBases, &b->dBaseOff, &b->dSeqOff, &b->dSeqRank, &b->dLong, &b->kA, &b->vA, &b->kB, &b->vB, &b->sortTmp}) d->release();
-    {
-        StageClock clk(&b->ms[2], b->stream);
-        while (b->runs.size() > 1) {                                  // pairwise, level by level: every record takes part in log2(runs) merges
-            std::vector<kasa_builder::Run> next;
-            for (size_t i = 0; i + 1 < b->runs.size(); i += 2) {
-                kasa_builder::Run m;
-                if ((rc = merge_two<Key>(b, b->runs[i], b->runs[i + 1], m))) return rc;
-                b->runs[i].k.release(); b->runs[i].v.release(); b->runs[i + 1].k.release(); b->runs[i + 1].v.release();
-                next.push_back(std::move(m));
-            }
-            if (b->runs.size() % 2) next.push_back(std::move(b->runs.back()));
-            b->runs.swap(next);
-        }
-        clk.stop();
-    }
-    if (b->runs.empty()) b->runs.emplace_back();
-    b->result = std::move(b->runs[0]);
-    b->runs.clear();
-    if ((rc = edit_finish<Key>(b))) return rc;                       // nothing when no kasa_build_add_index/drop_taxa/shrink was called
     const uint64_t n = b->result.n;
     const Key *k = b->result.k.as<Key>();
     const uint32_t *v = b->result.v.as<uint32_t>();
     constexpr int KL = KeyTraits<Key>::LETTERS;
-    StageClock clk(&b->ms[3], b->stream);
     if ((rc = b->rec.reserve(n * (uint64_t)b->recBytes() + 64))) return rc;
     if (n) {
         if (b->halved) { if ((rc = edit_emit_halved<Key>(b, k, v, n))) return rc; }
@@ -477,8 +520,30 @@ static int finish_impl(kasa_builder *b)
         bld_trie_scatter_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, n, shift, p, b->trieFirst.as<uint64_t>(), b->triePrefix.as<uint32_t>());
         bld_trie_count_kernel<<<grid_for(b->nTrie), 256, 0, b->stream>>>(b->trieFirst.as<uint64_t>(), b->nTrie, n, b->trieCount.as<uint64_t>());
         HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(b->stream));                      // (pos goes out of scope here)
     } else b->nTrie = 0;
-    if (!b->freqDone && (rc = freq_into<Key>(b, k, v, n))) return rc;  // (a halved index keeps the frequencies of the full one)
+    return KASA_OK;
+}
+
+template <class Key>
+static int finish_impl(kasa_builder *b)
+{
+    int rc;
+    if ((rc = flush_brick<Key>(b))) return rc;
+    // the brick buffers are not needed any more: their memory goes to the merges
+    for (DevBuf *d : {&b->dBases, &b->dBaseOff, &b->dSeqOff, &b->dSeqRank, &b->dLong, &b->kA, &b->vA, &b->kB, &b->vB, &b->sortTmp}) d->release();
+    {
+        StageClock clk(&b->ms[2], b->stream);
+        if ((rc = merge_runs<Key>(b, b->runs))) return rc;
+        clk.stop();
+    }
+    if (b->runs.empty()) b->runs.emplace_back();
+    b->result = std::move(b->runs[0]);
+    b->runs.clear();
+    if ((rc = edit_finish<Key>(b))) return rc;                       // nothing when no kasa_build_add_index/drop_taxa/shrink was called
+    StageClock clk(&b->ms[3], b->stream);
+    if ((rc = emit_result<Key>(b))) return rc;
+    if (!b->freqDone && (rc = freq_into<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), b->result.n))) return rc;  // (a halved index keeps the frequencies of the full one)
     clk.stop();
     HIPCHK(hipStreamSynchronize(b->stream));
     b->result.k.release(); b->result.v.release();
@@ -555,6 +620,7 @@ static int build_add_impl(kasa_builder *b, const uint8_t *bases, const int64_t *
     HIPCHK(hipSetDevice(b->device));
     const int mode = protein ? ENC_PROTEIN : (b->frames == 1 ? ENC_ONE : ENC_DNA);
     int rc;
+    b->added = true;
     for (int64_t s = 0; s < nSeq; ++s) {
         const int64_t len = offsets[s + 1] - offsets[s];
         if (len < 0) return fail(KASA_E_ARG, "kasa_build_add: offsets are not ascending at sequence %lld", (long long)s);
@@ -617,13 +683,8 @@ extern "C" int kasa_build_finish(kasa_builder *b, uint64_t *nRecords, uint64_t *
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
     if (b->finished) return fail(KASA_E_STATE, "kasa_build_finish: called twice");
     HIPCHK(hipSetDevice(b->device));
-    int rc;
-    try { rc = b->wide ? kasa_build_impl::finish_impl<key128>(b) : kasa_build_impl::finish_impl<uint64_t>(b); }
+    try { return b->wide ? kasa_build_impl::finish_all<key128>(b, nRecords, nTrie) : kasa_build_impl::finish_all<uint64_t>(b, nRecords, nTrie); }
     catch (const std::bad_alloc &) { return fail(KASA_E_NOMEM, "host allocation failed"); }
-    if (rc) return rc;
-    if (nRecords) *nRecords = b->result.n;
-    if (nTrie) *nTrie = b->nTrie;
-    return KASA_OK;
 }
 
 extern "C" int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t count, void *records)
@@ -633,6 +694,11 @@ extern "C" int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t 
     if (first > b->result.n || count > b->result.n - first) return fail(KASA_E_ARG, "kasa_build_fetch_range: [%llu, +%llu) outside the %llu records",
                                                                          (unsigned long long)first, (unsigned long long)count, (unsigned long long)b->result.n);
     if (count && !records) return fail(KASA_E_ARG, "kasa_build_fetch_range: records is NULL");
+    if (b->spilled) {                                                  // (kasa_spill.h: the slabs' records, kept by kasa_build_finish)
+        if (b->phase != 2 || !b->collected) return fail(KASA_E_STATE, "kasa_build_fetch_range: the records of a spilled build were handed out slab by slab (kasa_build_fetch_slab)");
+        if (count) memcpy(records, b->hRec.data() + first * (uint64_t)b->recBytes(), count * (uint64_t)b->recBytes());
+        return KASA_OK;
+    }
     HIPCHK(hipSetDevice(b->device));
     if (count) HIPCHK(hipMemcpy(records, b->rec.as<uint8_t>() + first * (uint64_t)b->recBytes(), count * (uint64_t)b->recBytes(), hipMemcpyDeviceToHost));
     return KASA_OK;
@@ -643,7 +709,14 @@ extern "C" int kasa_build_fetch(kasa_builder *b, void *records, uint32_t *triePr
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
     if (!b->finished) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish first");
     HIPCHK(hipSetDevice(b->device));
+    if (b->spilled && b->phase != 2) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish_end first");
     if (records) { const int rc = kasa_build_fetch_range(b, 0, b->result.n, records); if (rc) return rc; }
+    if (b->spilled) {                                                  // (kasa_spill.h: the slabs' trie entries, kept by kasa_build_finish)
+        if ((triePrefix || trieCount) && !b->collected) return fail(KASA_E_STATE, "kasa_build_fetch: the trie of a spilled build was handed out slab by slab (kasa_build_fetch_slab)");
+        if (triePrefix && b->nTrie) memcpy(triePrefix, b->hTriePrefix.data(), b->nTrie * 4);
+        if (trieCount && b->nTrie) memcpy(trieCount, b->hTrieCount.data(), b->nTrie * 8);
+        triePrefix = nullptr; trieCount = nullptr;
+    }
     if (triePrefix && b->nTrie) HIPCHK(hipMemcpy(triePrefix, b->triePrefix.p, b->nTrie * 4, hipMemcpyDeviceToHost));
     if (trieCount && b->nTrie) HIPCHK(hipMemcpy(trieCount, b->trieCount.p, b->nTrie * 8, hipMemcpyDeviceToHost));
     if (freq) {

@@ -418,6 +418,8 @@ static int build_add_index_impl(kasa_builder *b, uint64_t first, uint64_t count,
     using namespace kasa_build_impl;
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
     if (b->finished) return fail(KASA_E_STATE, "kasa_build_add_index: the build is finished");
+    if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_add_index: edits need the runs on the device (the builder has a resident budget or spilled runs)");
+    b->edited = true;
     if (count && !records) return fail(KASA_E_ARG, "kasa_build_add_index: records is NULL");
     if (first > total || count > total - first)
         return fail(KASA_E_ARG, "kasa_build_add_index: records [%llu, +%llu) outside the run of %llu", (unsigned long long)first, (unsigned long long)count, (unsigned long long)total);
@@ -475,6 +477,8 @@ static int build_drop_taxa_impl(kasa_builder *b, const uint32_t *taxIds, uint64_
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
     if (b->finished) return fail(KASA_E_STATE, "kasa_build_drop_taxa: the build is finished");
+    if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_drop_taxa: edits need the runs on the device (the builder has a resident budget or spilled runs)");
+    b->edited = true;
     if (n && !taxIds) return fail(KASA_E_ARG, "kasa_build_drop_taxa: taxIds is NULL");
     if (b->dropRank.empty()) b->dropRank.assign(b->ids.size(), 0);
     for (uint64_t i = 0; i < n; ++i) {                                 // IDs the content file does not list name no record
@@ -493,6 +497,8 @@ extern "C" int kasa_build_shrink(kasa_builder *b, int strategy, float percentage
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
     if (b->finished) return fail(KASA_E_STATE, "kasa_build_shrink: the build is finished");
+    if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_shrink: edits need the runs on the device (the builder has a resident budget or spilled runs)");
+    b->edited = true;
     if (b->shrinkStrategy) return fail(KASA_E_STATE, "kasa_build_shrink: called twice");
     if (strategy < 1 || strategy > 3) return fail(KASA_E_ARG, "kasa_build_shrink: strategy must be 1 (every n-th k-mer of a taxon), 2 (halved) or 3 (entropy), got %d", strategy);
     if (strategy == 2 && b->wide) return fail(KASA_E_ARG, "kasa_build_shrink: If k is larger than 12, the index can not be halved as of now!");
@@ -517,6 +523,7 @@ static int build_taxa_histogram_impl(kasa_builder *b, uint64_t *hist, uint64_t n
     using namespace kasa_build_impl;
     if (!b || !hist || !distinctKmers || nBins == 0) return fail(KASA_E_ARG, "kasa_build_taxa_histogram: NULL argument or no bins");
     if (!b->finished) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: kasa_build_finish first");
+    if (b->spilled) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: the records of a spilled build are not on the device");
     if (b->halved) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: a halved index keeps 30 bits of a k-mer, its records do not tell k-mers apart");
     HIPCHK(hipSetDevice(b->device));
     return b->wide ? taxa_histogram<key128>(b, hist, nBins, distinctKmers) : taxa_histogram<uint64_t>(b, hist, nBins, distinctKmers);

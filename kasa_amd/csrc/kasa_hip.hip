@@ -9341,6 +9341,7 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
 // ------------------------------------------------------------------------------------------------
 #include "kasa_build.h"
 #include "kasa_edit.h"
+#include "kasa_spill.h"
 
 // ------------------------------------------------------------------------------------------------
 // parse: FASTA / FASTQ text -> the reads of a batch on the device (kasa_parse_*)

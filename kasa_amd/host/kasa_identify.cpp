@@ -2839,6 +2839,65 @@ static void writeIndexFiles(kasa_builder *b, const string &index, const Content 
     if (withFreq) writeFreqFile(index + "_f.txt", c, K, freq);
 }
 
+// The finish of a build slab by slab (kasa_build_finish_begin / slab / fetch_slab / finish_end: one slab for an index that fits
+// the device, key-range slabs for one that was spilled to host memory): the records file is written as the slabs come, a range
+// while the next one is copied, the trie is gathered and _info.txt, _trie, _trie.txt and _f.txt are written at the end.  An
+// error leaves no _info.txt, and no records file of this run.  tFinish: the seconds inside finish_begin and slab.
+static void writeIndexBySlabs(kasa_builder *b, const string &index, const Content &c, int K, const char *infoTail, uint64_t &nRec, uint64_t &nTrie, uint64_t &nSlabs,
+                              double &tFinish)
+{
+    const size_t nTaxa = c.taxids.size(), recBytes = K == 25 ? 20 : 12;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&]() { tFinish += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+    if (kasa_build_finish_begin(b, &nSlabs)) throwLast();
+    lap();
+    vector<uint32_t> tp; vector<uint64_t> tc;
+    FILE *f = nullptr;
+    std::future<size_t> pending;
+    auto drop = [&]() { if (pending.valid()) pending.get(); if (f) { fclose(f); f = nullptr; std::remove(index.c_str()); } };
+    try {
+        const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
+        vector<uint8_t> bufs[2];
+        int cur = 0;
+        for (uint64_t s = 0; s < nSlabs; ++s) {
+            uint64_t n = 0, m = 0;
+            t0 = std::chrono::steady_clock::now();
+            if (kasa_build_slab(b, s, &n, &m)) throwLast();
+            lap();
+            const size_t at = tp.size();
+            tp.resize(at + m); tc.resize(at + m);
+            if (m && kasa_build_fetch_slab(b, 0, 0, nullptr, tp.data() + at, tc.data() + at)) throwLast();
+            if (n && !f) {
+                f = fopen(index.c_str(), "wb");
+                if (!f) throw std::runtime_error("The index file cannot be written: " + index);
+            }
+            for (uint64_t first = 0; first < n; first += step) {
+                const uint64_t cnt = std::min(step, n - first);
+                if (bufs[cur].size() < (size_t)cnt * recBytes) bufs[cur].resize((size_t)cnt * recBytes);
+                if (kasa_build_fetch_slab(b, first, cnt, bufs[cur].data(), nullptr, nullptr)) throwLast();
+                if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
+                const uint8_t *src = bufs[cur].data(); const size_t bytes = (size_t)cnt * recBytes; FILE *out = f;
+                pending = std::async(std::launch::async, [out, src, bytes] { return fwrite(src, 1, bytes, out) == bytes ? bytes + 1 : (size_t)0; });
+                cur ^= 1;
+            }
+        }
+        if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
+        if (kasa_build_finish_end(b, &nRec, &nTrie)) throwLast();
+        if (nRec == 0) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
+        if (f) { FILE *g = f; f = nullptr; if (fclose(g) != 0) throw std::runtime_error("writing the index file failed"); }
+    } catch (...) { drop(); throw; }
+    vector<uint64_t> freq(nTaxa * (size_t)K);
+    if (kasa_build_fetch(b, nullptr, nullptr, nullptr, freq.data())) throwLast();
+    { std::ofstream o(index + "_info.txt", std::ios::binary); o << nRec << infoTail; }
+    {
+        vector<uint8_t> t(nTrie * 12);
+        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
+        std::ofstream o(index + "_trie", std::ios::binary); o.write((const char *)t.data(), (std::streamsize)t.size());
+        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
+    }
+    writeFreqFile(index + "_f.txt", c, K, freq);
+}
+
 static int buildMode(const vector<string> &a)
 {
     string input, contentPath, index, codonFile, codonId;
@@ -2884,26 +2943,26 @@ static int buildMode(const vector<string> &a)
     if (kasa_build_create(device, K, frames, lut.empty() ? nullptr : lut.data(), bc.c.taxids.data(), (uint32_t)bc.c.taxids.size(),
                           brickEnv ? (uint64_t)atoll(brickEnv) : 0, &b)) throwLast();
     std::unique_ptr<kasa_builder, void (*)(kasa_builder *)> guard(b, kasa_build_destroy);
+    if (const char *residentEnv = getenv("KASA_BUILD_RESIDENT_RECORDS"))                     // tests: a spilled build of a small database
+        if (kasa_build_set_resident(b, (uint64_t)atoll(residentEnv))) throwLast();
     double tParse = 0, tAdd = 0;
     uint64_t nSeq = 0, nSkipped = 0;
     addDatabase(b, input, bc, threads, verbose, nSeq, nSkipped, tParse, tAdd);
     if (verbose && nSkipped) std::cout << "OUT: " << nSkipped << " sequence(s) without an accession of the content file were skipped" << std::endl;
     auto tf = std::chrono::steady_clock::now();
-    uint64_t nRec = 0, nTrie = 0;
-    if (kasa_build_finish(b, &nRec, &nTrie)) throwLast();
-    const double tFinish = secs(tf);
-    if (nRec == 0) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
-    // files: records, _info.txt, _trie, _trie.txt, _f.txt (formats.write_index's layout)
-    tf = std::chrono::steady_clock::now();
-    writeIndexFiles(b, index, bc.c, K, nRec, nTrie, K == 25 ? "\n128" : "", true);
-    const double tWrite = secs(tf);
-    uint64_t st[8] = {0};
-    if (kasa_build_stats(b, st)) throwLast();
+    uint64_t nRec = 0, nTrie = 0, nSlabs = 0;
+    // the finish and the files, slab by slab: records, _info.txt, _trie, _trie.txt, _f.txt (formats.write_index's layout)
+    double tFinish = 0;
+    writeIndexBySlabs(b, index, bc.c, K, K == 25 ? "\n128" : "", nRec, nTrie, nSlabs, tFinish);
+    const double tWrite = secs(tf) - tFinish;
+    uint64_t st[8] = {0}, sp[8] = {0};
+    if (kasa_build_stats(b, st) || kasa_build_spill_stats(b, sp)) throwLast();
     std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries, from " << nSeq << " sequence(s)" << std::endl;
     if (getenv("KASA_BUILD_TIMING") || verbose)
         std::cout << "OUT: build timing: parse " << tParse << " s, add " << tAdd << " s, finish " << tFinish << " s, write " << tWrite << " s, total " << secs(t0)
                   << " s; pairs " << st[0] << ", bricks " << st[1] << ", merges " << st[2] << ", device ms encode " << st[4] / 1e3 << " sort+unique " << st[5] / 1e3
-                  << " merge " << st[6] / 1e3 << " emit " << st[7] / 1e3 << std::endl;
+                  << " merge " << st[6] / 1e3 << " emit " << st[7] / 1e3 << "; spilled runs " << sp[0] << ", slabs " << nSlabs << ", copy ms up " << sp[5] / 1e3
+                  << " down " << sp[6] / 1e3 << std::endl;
     std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;
     return 0;
 }

@@ -55,7 +55,7 @@ def accession_of(header: str, acc_to_tax: dict):
 
 
 def build_index(fasta_path: str, content_path: str, device: int = 0, K: int = formats.K64, codon_lut=None,
-                frames: int = 3, max_pairs_per_brick: int = 0) -> formats.Index:
+                frames: int = 3, max_pairs_per_brick: int = 0, max_resident_records: int = 0) -> formats.Index:
     content = formats.read_content(content_path)
     acc_to_tax = accession_map(content_path)
     db = reads.parse_reads(fasta_path)
@@ -69,7 +69,7 @@ def build_index(fasta_path: str, content_path: str, device: int = 0, K: int = fo
     off = np.zeros(len(keep) + 1, dtype=np.int64)
     np.cumsum(lens, out=off[1:])
     bases = np.concatenate([db.bases[db.offsets[i]:db.offsets[i + 1]] for i in keep]) if keep else np.zeros(0, np.uint8)
-    b = capi.Builder(content.taxids, K, frames, codon_lut, max_pairs_per_brick, device)
+    b = capi.Builder(content.taxids, K, frames, codon_lut, max_pairs_per_brick, device, max_resident_records)
     try:
         b.add(bases, off, np.asarray(tax, dtype=np.uint32), db.protein)
         b.finish()
