@@ -703,8 +703,8 @@ int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, u
  * The reference builds any size through STXXL temporaries (Build.hpp:305-477).  Here the bricks' runs leave the device for
  * ordinary (pageable) host memory once they outgrow a resident budget, and the finish walks the key space in slabs: intervals
  * of 6-letter trie prefixes, so that no k-mer, duplicate pair or trie entry is split.  A slab's slices are uploaded, merged,
- * emitted and trie'd by the kernels of the in-core finish; the frequency histograms live across the slabs.  The slabs' records
- * and trie entries concatenate to the index; a builder that never spills runs the in-core finish as before.
+ * emitted and trie'd; the frequency histograms live across the slabs.  The slabs' records and trie entries concatenate to the
+ * index.  There is one finish: a builder whose runs stayed on the device has one slab, all of its records, made by the same code.
  *   kasa_build_set_resident  before the first kasa_build_add (KASA_E_STATE after it, and after an edit call):
  *                          maxResidentRecords = the most input records a slab may bring to the device.  0 (the default) =
  *                          automatic: the builder spills once the in-core finish of the runs it holds is no longer sure to
@@ -712,9 +712,10 @@ int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, u
  *                          when the finish's memory check refuses a merge, and sizes the slabs by the same arithmetic.
  *                          Otherwise: as soon as the runs on the device hold more records than this they go to the host,
  *                          and every later run follows.
- *   kasa_build_finish_begin  the last brick and the plan; *nSlabs = the slabs to take.  KASA_E_LIMIT names the prefix, its
- *                          input records and the budget when one prefix alone exceeds the budget; KASA_E_NOMEM when the
- *                          host has no memory for a run.
+ *   kasa_build_finish_begin  the last brick; then, runs on the device: the merges, the edits and the one slab; runs in host
+ *                          memory: the plan.  *nSlabs = the slabs to take.  KASA_E_LIMIT names the prefix, its input records
+ *                          and the budget when one prefix alone exceeds the budget; KASA_E_NOMEM when the host has no
+ *                          memory for a run.
  *   kasa_build_slab        slab 0, 1, .. nSlabs - 1 in order, each once (KASA_E_STATE otherwise): *nRecords and *nTrie of
  *                          this slab.
  *   kasa_build_fetch_slab  records [first, first + count) of the current slab and its trie entries (all nTrie of them);
@@ -724,9 +725,11 @@ int kasa_build_taxa_histogram(kasa_builder *b, uint64_t *hist, uint64_t nBins, u
  *   kasa_build_spill_stats stats8 = {runs spilled, records spilled, slabs, the largest slab's input records, the heaviest
  *                          prefix's input records, host microseconds of the copies host -> device, device -> host, 0}; all
  *                          zero for a builder that did not spill.
- * On a builder that did not spill, kasa_build_finish_begin is kasa_build_finish and reports one slab, kasa_build_slab(b, 0)
- * returns the totals and kasa_build_fetch_slab is kasa_build_fetch_range plus the trie: a host needs one code path.
- * kasa_build_finish on a builder that spilled takes every slab and gathers records and trie in host memory, so
+ * kasa_build_finish is kasa_build_finish_begin, every kasa_build_slab and kasa_build_finish_end in one call.  On a builder that
+ * did not spill, kasa_build_finish_begin does all the work of kasa_build_finish and reports one slab, kasa_build_slab(b, 0)
+ * returns the totals and kasa_build_fetch_slab is kasa_build_fetch_range plus the trie: a host needs one code path, and edited
+ * builders (update, delete, shrink, merge) take it too.
+ * kasa_build_finish on a builder that spilled gathers the records and trie of every slab in host memory, so
  * kasa_build_fetch and kasa_build_fetch_range keep working, bounded by the host's RAM; after the streaming calls they return
  * KASA_E_STATE for records and trie.  kasa_build_stats' merges counts the merges of all slabs.
  * Edits need the runs on the device: kasa_build_add_index, kasa_build_drop_taxa and kasa_build_shrink return KASA_E_STATE on a

@@ -190,7 +190,24 @@ static inline unsigned grid_for(uint64_t n, unsigned threads = 256, unsigned cap
 
 struct kasa_builder {
     int device = 0, K = 12, frames = 3;
-    bool wide = false, finished = false;
+    bool wide = false;
+    // Where the build stands -- what every entry point checks first.  A finish that fails leaves ADDING.
+    //   ADDING  add, add_index, drop_taxa, shrink and set_resident are taken
+    //   SLABS   kasa_build_finish_begin is done; kasa_build_slab and fetch_slab hand the slabs out, slabNext is the next one
+    //   DONE    kasa_build_finish_end is done (kasa_build_finish is begin + every slab + end)
+    enum State { ADDING, SLABS, DONE } state = ADDING;
+    // where the runs live: b->runs on the device, or (spilled) hostRuns, where every new run follows them
+    bool spilled = false;
+    // where the finished records and trie live, from SLABS on: all in rec / triePrefix / trieCount; the current slab's there and
+    // no others; all in hRec / hTriePrefix / hTrieCount
+    enum Records { ON_DEVICE, BY_SLAB, GATHERED } records = ON_DEVICE;
+    // what was called: kasa_build_add; an edit call (add_index, drop_taxa, shrink); add_index in the middle of a run
+    // (idxRuns.back() holds [0, loadNext) of loadTotal records)
+    bool added = false, edited = false, loading = false;
+    // The combinations that occur:
+    //   spilled  records                                         edited, loading, halved
+    //   false    ON_DEVICE: one slab, made by finish_begin        any: the edit calls refuse a budget and spilled runs
+    //   true     BY_SLAB, or GATHERED after kasa_build_finish     never: set_resident refuses an edited builder, which never spills
     hipStream_t stream = nullptr;
     uint64_t maxPairs = 0;
     std::vector<uint32_t> ids;             // content tax IDs sorted ascending, unique: rank -> tax ID
@@ -219,25 +236,20 @@ struct kasa_builder {
     double ms[4] = {0, 0, 0, 0};
     // editing an existing index (kasa_edit.h): its runs, the taxa to drop, the shrink strategy
     std::vector<Run> idxRuns;
-    bool loading = false;                  // idxRuns.back() is being loaded: [0, loadNext) of loadTotal records are in
     uint64_t loadNext = 0, loadTotal = 0;
     DevBuf loadStage, loadErr;
     std::vector<uint8_t> dropRank;         // rank -> dropped (kasa_build_drop_taxa); empty: nothing dropped
     int shrinkStrategy = 0;                // 0: none, 1: every n-th of a taxon, 2: halved, 3: entropy
     float shrinkP = 0.f;
-    bool halved = false, freqDone = false;
+    bool halved = false;                   // set by the finish of shrink strategy 2: 6-byte records, and freqR holds the frequencies of the full index
     uint64_t indexIn = 0, droppedDelete = 0, droppedShrink = 0;
     double msEdit = 0;                     // device ms of the loads and the filters
     // building an index larger than device memory (kasa_spill.h): runs in host memory, merged and emitted in key-range slabs
     uint64_t resident = 0;                 // kasa_build_set_resident: the most input records of a slab (0: sized by the device)
-    bool added = false, edited = false;    // kasa_build_add / an edit call was made
-    bool spilled = false;                  // the runs live in hostRuns; every new run follows them
     std::vector<kasa_spill_plan::HostRun> hostRuns;
     kasa_spill_plan::Plan plan;
-    int phase = 0;                         // 0: adding, 1: kasa_build_finish_begin done, 2: kasa_build_finish_end done
     uint64_t slabNext = 0, totalRec = 0, totalTrie = 0;
-    bool collected = false;                // kasa_build_finish on a spilled builder: records and trie of all slabs, in host memory
-    std::vector<uint8_t> hRec;
+    std::vector<uint8_t> hRec;             // records = GATHERED: the records and trie entries of all slabs
     std::vector<uint32_t> hTriePrefix;
     std::vector<uint64_t> hTrieCount;
     DevBuf freqHist, freqExtra;            // the frequency histograms, kept from the first slab to the last
@@ -245,6 +257,7 @@ struct kasa_builder {
     double usUp = 0, usDown = 0;           // host microseconds of the copies host -> device, device -> host
     int keyBytes() const { return wide ? 16 : 8; }
     int recBytes() const { return halved ? 6 : (wide ? 20 : 12); }
+    uint64_t nSlabs() const { return spilled ? plan.slabs.size() : 1; }
 };
 
 namespace kasa_build_impl {
@@ -252,7 +265,7 @@ namespace kasa_build_impl {
 // kasa_edit.h: the index runs' merges and the filters after the brick merges; the 6-byte records of a halved index
 template <class Key> static int edit_finish(kasa_builder *b);
 template <class Key> static int edit_emit_halved(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n);
-// kasa_spill.h: a new run joins the spilled ones (nothing for a builder that does not spill); the finish, in one call or by slabs
+// kasa_spill.h: a new run joins the spilled ones (nothing for a builder that does not spill); begin + every slab + end in one call
 template <class Key> static int spill_after_brick(kasa_builder *b);
 template <class Key> static int finish_all(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie);
 
@@ -456,14 +469,6 @@ static int freq_final(kasa_builder *b)
     b->freqHist.release(); b->freqExtra.release();
     return KASA_OK;
 }
-template <class Key>
-static int freq_into(kasa_builder *b, const Key *k, const uint32_t *v, uint64_t n)
-{
-    int rc;
-    if ((rc = freq_zero<Key>(b)) || (rc = freq_accumulate<Key>(b, k, v, n))) return rc;
-    return freq_final<Key>(b);
-}
-
 // the runs merged pairwise, level by level, until one is left: every record takes part in log2(runs) merges.  When a merge fails
 // the runs stay whole -- those merged so far and the rest -- and the caller may go on by slabs (kasa_spill.h).
 template <class Key>
@@ -485,6 +490,18 @@ static int merge_runs(kasa_builder *b, std::vector<kasa_builder::Run> &runs)
         if (runs.size() % 2) next.push_back(std::move(runs.back()));
         runs.swap(next);
     }
+    return KASA_OK;
+}
+
+// flags f[0, n), n > 0 -> pos[i] = how many of f[0, i) are set, `kept` = how many of all n: where each flagged item goes, in 64 bits
+static int flag_places(kasa_builder *b, const uint32_t *f, uint64_t n, uint64_t *pos, uint64_t &kept)
+{
+    int rc;
+    rocprim::transform_iterator<const uint32_t *, rocprim::identity<uint64_t>, uint64_t> fin(f, rocprim::identity<uint64_t>());
+    if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, fin, pos, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>()))) return rc;
+    uint64_t lastPos = 0; uint32_t lastF = 0;
+    if ((rc = fetch_async(b->stream, lastPos, pos + n - 1)) || (rc = fetch(b->stream, lastF, f + n - 1))) return rc;
+    kept = lastPos + lastF;
     return KASA_OK;
 }
 
@@ -511,11 +528,7 @@ static int emit_result(kasa_builder *b)
         bld_trie_flag_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, n, shift, f);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(p + n, 0, 8, b->stream));
-        rocprim::transform_iterator<const uint32_t *, rocprim::identity<uint64_t>, uint64_t> fin(f, rocprim::identity<uint64_t>());
-        if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>()))) return rc;
-        uint64_t lastPos = 0; uint32_t lastF = 0;
-        if ((rc = fetch_async(b->stream, lastPos, p + n - 1)) || (rc = fetch(b->stream, lastF, f + n - 1))) return rc;
-        b->nTrie = lastPos + lastF;
+        if ((rc = flag_places(b, f, n, p, b->nTrie))) return rc;
         if ((rc = b->trieFirst.reserve(b->nTrie * 8 + 64)) || (rc = b->triePrefix.reserve(b->nTrie * 4 + 64)) || (rc = b->trieCount.reserve(b->nTrie * 8 + 64))) return rc;
         bld_trie_scatter_kernel<Key><<<grid_for(n), 256, 0, b->stream>>>(k, n, shift, p, b->trieFirst.as<uint64_t>(), b->triePrefix.as<uint32_t>());
         bld_trie_count_kernel<<<grid_for(b->nTrie), 256, 0, b->stream>>>(b->trieFirst.as<uint64_t>(), b->nTrie, n, b->trieCount.as<uint64_t>());
@@ -525,29 +538,26 @@ static int emit_result(kasa_builder *b)
     return KASA_OK;
 }
 
+// The tail of every slab -- of the only one, first = last = true, when the runs stayed on the device: b->result -> the file records
+// and the trie of the slab, its share of the frequency histograms (zeroed before the first slab, summed up after the last one),
+// the running totals.  b->result's keys and ranks are released, the records and the trie stay until the next slab.
 template <class Key>
-static int finish_impl(kasa_builder *b)
+static int finish_slab(kasa_builder *b, bool first, bool last)
 {
     int rc;
-    if ((rc = flush_brick<Key>(b))) return rc;
-    // the brick buffers are not needed any more: their memory goes to the merges
-    for (DevBuf *d : {&b->dBases, &b->dBaseOff, &b->dSeqOff, &b->dSeqRank, &b->dLong, &b->kA, &b->vA, &b->kB, &b->vB, &b->sortTmp}) d->release();
     {
-        StageClock clk(&b->ms[2], b->stream);
-        if ((rc = merge_runs<Key>(b, b->runs))) return rc;
+        StageClock clk(&b->ms[3], b->stream);
+        if ((rc = emit_result<Key>(b))) return rc;
+        if (!b->halved) {                                              // (a halved index keeps the frequencies of the full one: edit_finish)
+            if (first && (rc = freq_zero<Key>(b))) return rc;
+            if ((rc = freq_accumulate<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), b->result.n))) return rc;
+            if (last && (rc = freq_final<Key>(b))) return rc;
+        }
         clk.stop();
     }
-    if (b->runs.empty()) b->runs.emplace_back();
-    b->result = std::move(b->runs[0]);
-    b->runs.clear();
-    if ((rc = edit_finish<Key>(b))) return rc;                       // nothing when no kasa_build_add_index/drop_taxa/shrink was called
-    StageClock clk(&b->ms[3], b->stream);
-    if ((rc = emit_result<Key>(b))) return rc;
-    if (!b->freqDone && (rc = freq_into<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), b->result.n))) return rc;  // (a halved index keeps the frequencies of the full one)
-    clk.stop();
     HIPCHK(hipStreamSynchronize(b->stream));
     b->result.k.release(); b->result.v.release();
-    b->finished = true;
+    b->totalRec += b->result.n; b->totalTrie += b->nTrie;
     return KASA_OK;
 }
 
@@ -615,7 +625,7 @@ extern "C" int kasa_build_create(int device, int K, int frames, const uint8_t *c
 static int build_add_impl(kasa_builder *b, const uint8_t *bases, const int64_t *offsets, int64_t nSeq, const uint32_t *seqTaxId, int protein)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished) return fail(KASA_E_STATE, "kasa_build_add: the build is finished");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_add: the build is finished");
     if (nSeq < 0 || (nSeq > 0 && (!offsets || !bases || !seqTaxId))) return fail(KASA_E_ARG, "kasa_build_add: bad arguments");
     HIPCHK(hipSetDevice(b->device));
     const int mode = protein ? ENC_PROTEIN : (b->frames == 1 ? ENC_ONE : ENC_DNA);
@@ -681,7 +691,7 @@ extern "C" int kasa_build_add(kasa_builder *b, const uint8_t *bases, const int64
 extern "C" int kasa_build_finish(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished) return fail(KASA_E_STATE, "kasa_build_finish: called twice");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_finish: called twice");
     HIPCHK(hipSetDevice(b->device));
     try { return b->wide ? kasa_build_impl::finish_all<key128>(b, nRecords, nTrie) : kasa_build_impl::finish_all<uint64_t>(b, nRecords, nTrie); }
     catch (const std::bad_alloc &) { return fail(KASA_E_NOMEM, "host allocation failed"); }
@@ -690,12 +700,12 @@ extern "C" int kasa_build_finish(kasa_builder *b, uint64_t *nRecords, uint64_t *
 extern "C" int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t count, void *records)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (!b->finished) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish first");
+    if (b->state == kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish first");
     if (first > b->result.n || count > b->result.n - first) return fail(KASA_E_ARG, "kasa_build_fetch_range: [%llu, +%llu) outside the %llu records",
                                                                          (unsigned long long)first, (unsigned long long)count, (unsigned long long)b->result.n);
     if (count && !records) return fail(KASA_E_ARG, "kasa_build_fetch_range: records is NULL");
-    if (b->spilled) {                                                  // (kasa_spill.h: the slabs' records, kept by kasa_build_finish)
-        if (b->phase != 2 || !b->collected) return fail(KASA_E_STATE, "kasa_build_fetch_range: the records of a spilled build were handed out slab by slab (kasa_build_fetch_slab)");
+    if (b->records != kasa_builder::ON_DEVICE) {                       // (kasa_spill.h: the slabs' records, kept by kasa_build_finish)
+        if (b->state != kasa_builder::DONE || b->records != kasa_builder::GATHERED) return fail(KASA_E_STATE, "kasa_build_fetch_range: the records of a spilled build were handed out slab by slab (kasa_build_fetch_slab)");
         if (count) memcpy(records, b->hRec.data() + first * (uint64_t)b->recBytes(), count * (uint64_t)b->recBytes());
         return KASA_OK;
     }
@@ -707,12 +717,12 @@ extern "C" int kasa_build_fetch_range(kasa_builder *b, uint64_t first, uint64_t 
 extern "C" int kasa_build_fetch(kasa_builder *b, void *records, uint32_t *triePrefix, uint64_t *trieCount, uint64_t *freq)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (!b->finished) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish first");
+    if (b->state == kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish first");
     HIPCHK(hipSetDevice(b->device));
-    if (b->spilled && b->phase != 2) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish_end first");
+    if (b->records != kasa_builder::ON_DEVICE && b->state != kasa_builder::DONE) return fail(KASA_E_STATE, "kasa_build_fetch: kasa_build_finish_end first");
     if (records) { const int rc = kasa_build_fetch_range(b, 0, b->result.n, records); if (rc) return rc; }
-    if (b->spilled) {                                                  // (kasa_spill.h: the slabs' trie entries, kept by kasa_build_finish)
-        if ((triePrefix || trieCount) && !b->collected) return fail(KASA_E_STATE, "kasa_build_fetch: the trie of a spilled build was handed out slab by slab (kasa_build_fetch_slab)");
+    if (b->records != kasa_builder::ON_DEVICE) {                       // (kasa_spill.h: the slabs' trie entries, kept by kasa_build_finish)
+        if ((triePrefix || trieCount) && b->records != kasa_builder::GATHERED) return fail(KASA_E_STATE, "kasa_build_fetch: the trie of a spilled build was handed out slab by slab (kasa_build_fetch_slab)");
         if (triePrefix && b->nTrie) memcpy(triePrefix, b->hTriePrefix.data(), b->nTrie * 4);
         if (trieCount && b->nTrie) memcpy(trieCount, b->hTrieCount.data(), b->nTrie * 8);
         triePrefix = nullptr; trieCount = nullptr;

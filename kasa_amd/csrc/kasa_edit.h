@@ -249,11 +249,8 @@ static int compact_result(kasa_builder *b, const uint32_t *f)
     DevBuf pos;
     if ((rc = pos.reserve(n * 8 + 64))) return rc;
     uint64_t *p = pos.as<uint64_t>();
-    rocprim::transform_iterator<const uint32_t *, rocprim::identity<uint64_t>, uint64_t> fin(f, rocprim::identity<uint64_t>());
-    if ((rc = dev_exclusive_scan(b->scanTmp, b->stream, fin, p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>()))) return rc;
-    uint64_t lastPos = 0; uint32_t lastF = 0;
-    if ((rc = fetch_async(b->stream, lastPos, p + n - 1)) || (rc = fetch(b->stream, lastF, f + n - 1))) return rc;
-    const uint64_t nu = lastPos + lastF;
+    uint64_t nu = 0;
+    if ((rc = flag_places(b, f, n, p, nu))) return rc;
     if (nu == n) return KASA_OK;
     kasa_builder::Run out;
     if ((rc = out.k.reserve(nu * sizeof(Key) + 64)) || (rc = out.v.reserve(nu * 4 + 64))) return rc;
@@ -377,8 +374,7 @@ static int edit_finish(kasa_builder *b)
     b->droppedDelete = n0 - b->result.n;
     const uint64_t n1 = b->result.n;
     if (b->shrinkStrategy == 2) {                                     // the halved index keeps the frequency file of the full one
-        if ((rc = freq_into<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), n1))) return rc;
-        b->freqDone = true;
+        if ((rc = freq_zero<Key>(b)) || (rc = freq_accumulate<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), n1)) || (rc = freq_final<Key>(b))) return rc;
     }
     if (b->shrinkStrategy && n1) {
         const Key *k = b->result.k.as<Key>();
@@ -417,7 +413,7 @@ static int build_add_index_impl(kasa_builder *b, uint64_t first, uint64_t count,
 {
     using namespace kasa_build_impl;
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished) return fail(KASA_E_STATE, "kasa_build_add_index: the build is finished");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_add_index: the build is finished");
     if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_add_index: edits need the runs on the device (the builder has a resident budget or spilled runs)");
     b->edited = true;
     if (count && !records) return fail(KASA_E_ARG, "kasa_build_add_index: records is NULL");
@@ -476,7 +472,7 @@ extern "C" int kasa_build_add_index(kasa_builder *b, uint64_t first, uint64_t co
 static int build_drop_taxa_impl(kasa_builder *b, const uint32_t *taxIds, uint64_t n)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished) return fail(KASA_E_STATE, "kasa_build_drop_taxa: the build is finished");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_drop_taxa: the build is finished");
     if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_drop_taxa: edits need the runs on the device (the builder has a resident budget or spilled runs)");
     b->edited = true;
     if (n && !taxIds) return fail(KASA_E_ARG, "kasa_build_drop_taxa: taxIds is NULL");
@@ -496,7 +492,7 @@ extern "C" int kasa_build_drop_taxa(kasa_builder *b, const uint32_t *taxIds, uin
 extern "C" int kasa_build_shrink(kasa_builder *b, int strategy, float percentage)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished) return fail(KASA_E_STATE, "kasa_build_shrink: the build is finished");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_shrink: the build is finished");
     if (b->resident || b->spilled) return fail(KASA_E_STATE, "kasa_build_shrink: edits need the runs on the device (the builder has a resident budget or spilled runs)");
     b->edited = true;
     if (b->shrinkStrategy) return fail(KASA_E_STATE, "kasa_build_shrink: called twice");
@@ -522,8 +518,8 @@ static int build_taxa_histogram_impl(kasa_builder *b, uint64_t *hist, uint64_t n
 {
     using namespace kasa_build_impl;
     if (!b || !hist || !distinctKmers || nBins == 0) return fail(KASA_E_ARG, "kasa_build_taxa_histogram: NULL argument or no bins");
-    if (!b->finished) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: kasa_build_finish first");
-    if (b->spilled) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: the records of a spilled build are not on the device");
+    if (b->state == kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: kasa_build_finish first");
+    if (b->records != kasa_builder::ON_DEVICE) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: the records of a spilled build are not on the device");
     if (b->halved) return fail(KASA_E_STATE, "kasa_build_taxa_histogram: a halved index keeps 30 bits of a k-mer, its records do not tell k-mers apart");
     HIPCHK(hipSetDevice(b->device));
     return b->wide ? taxa_histogram<key128>(b, hist, nBins, distinctKmers) : taxa_histogram<uint64_t>(b, hist, nBins, distinctKmers);

@@ -7,9 +7,11 @@
 //             unique_into.  The copies are hipMemcpyAsync on the builder's stream from and to pageable memory: the runtime
 //             stages them through its own page-locked buffers, the runs themselves are never page-locked.
 //   plan    : kasa_spill_plan.h (host only): slabs as intervals of 6-letter prefixes, greedy under the budget, per run a slice
-//   slab    : the slices uploaded, merged pairwise by merge_two as the in-core finish merges runs, then bld_emit_kernel and the
+//   slab    : the slices uploaded and merged pairwise (merge_runs), then finish_slab of kasa_build.h: bld_emit_kernel and the
 //             bld_trie_* kernels on the slab's result; bld_freq_kernel adds to histograms that live from the first slab to the
 //             last, bld_freq_final_kernel runs once.  No kernel of its own.
+// The finish has one body for every builder: runs that stayed on the device are one slab, which finish_begin_impl merges, edits
+// (kasa_edit.h) and hands to the same finish_slab; kasa_build_slab(b, 0) then only reports it.
 // A cut between two prefixes splits no k-mer, no duplicate pair and no trie entry ({count, prefix}, no global offsets), and the
 // frequency rows are sums over records: the slabs' records and trie entries concatenate to what the in-core finish gives.
 //
@@ -85,40 +87,49 @@ static int spill_after_brick(kasa_builder *b)
     return spill_all_runs<Key>(b);
 }
 
-// the last brick, then either the in-core finish (one slab) or the plan of the spilled runs
+// kasa_build_finish_begin.  Runs on the device: merged, edited and emitted here, as the one slab kasa_build_slab(b, 0) reports.
+// Runs in host memory: the plan of the slabs, which kasa_build_slab brings up one by one.
 template <class Key>
 static int finish_begin_impl(kasa_builder *b, uint64_t *nSlabs)
 {
     int rc;
     if ((rc = flush_brick<Key>(b))) return rc;
-    if (!b->spilled) {
-        rc = finish_impl<Key>(b);
-        // merge_two's memory check refused: the runs are whole (merge_runs), the build goes on by slabs
-        const bool bySlabs = rc == KASA_E_LIMIT && !b->edited && !b->runs.empty();
-        if (!bySlabs) {
-            if (rc) return rc;
-            b->phase = 1; b->slabNext = 0;
-            if (nSlabs) *nSlabs = 1;
-            return KASA_OK;
-        }
-        if ((rc = spill_all_runs<Key>(b))) return rc;
-    }
+    // the brick buffers are not needed any more: their memory goes to the merges
     for (DevBuf *d : {&b->dBases, &b->dBaseOff, &b->dSeqOff, &b->dSeqRank, &b->dLong, &b->kA, &b->vA, &b->kB, &b->vB, &b->sortTmp, &b->flags}) d->release();
-    uint64_t budget = b->resident;
-    if (!budget) {
-        size_t freeB = 0, totalB = 0;
-        HIPCHK(hipMemGetInfo(&freeB, &totalB));
-        budget = std::max<uint64_t>(1, (uint64_t)(SPILL_HEADROOM * (double)freeB) / spill_bytes_per_record(b));
+    b->totalRec = 0; b->totalTrie = 0;
+    if (!b->spilled) {
+        {
+            StageClock clk(&b->ms[2], b->stream);
+            rc = merge_runs<Key>(b, b->runs);
+            clk.stop();
+        }
+        // merge_two's memory check refused: the runs are whole (merge_runs), the build goes on by slabs -- edits need them on the device
+        if (rc == KASA_E_LIMIT && !b->edited) rc = spill_all_runs<Key>(b);
+        if (rc) return rc;
     }
-    std::vector<const Key *> keys;
-    std::vector<uint64_t> n;
-    for (const kasa_spill_plan::HostRun &h : b->hostRuns) { keys.push_back(static_cast<const Key *>(h.k)); n.push_back(h.n); }
-    if (!kasa_spill_plan::make_plan<Key>(keys.data(), n.data(), keys.size(), KeyTraits<Key>::LETTERS, budget, b->plan))
-        return fail(KASA_E_LIMIT, "kasa_build_finish: %s (a slab holds whole 6-letter prefixes)", kasa_spill_plan::refusal_text(b->plan).c_str());
-    b->finished = true;
-    b->phase = 1; b->slabNext = 0; b->totalRec = 0; b->totalTrie = 0;
-    b->result.n = 0; b->nTrie = 0;
-    if (nSlabs) *nSlabs = b->plan.slabs.size();
+    if (!b->spilled) {
+        if (b->runs.empty()) b->runs.emplace_back();
+        b->result = std::move(b->runs[0]);
+        b->runs.clear();
+        if ((rc = edit_finish<Key>(b))) return rc;                   // nothing when no kasa_build_add_index/drop_taxa/shrink was called
+        if ((rc = finish_slab<Key>(b, true, true))) return rc;
+    } else {
+        uint64_t budget = b->resident;
+        if (!budget) {
+            size_t freeB = 0, totalB = 0;
+            HIPCHK(hipMemGetInfo(&freeB, &totalB));
+            budget = std::max<uint64_t>(1, (uint64_t)(SPILL_HEADROOM * (double)freeB) / spill_bytes_per_record(b));
+        }
+        std::vector<const Key *> keys;
+        std::vector<uint64_t> n;
+        for (const kasa_spill_plan::HostRun &h : b->hostRuns) { keys.push_back(static_cast<const Key *>(h.k)); n.push_back(h.n); }
+        if (!kasa_spill_plan::make_plan<Key>(keys.data(), n.data(), keys.size(), KeyTraits<Key>::LETTERS, budget, b->plan))
+            return fail(KASA_E_LIMIT, "kasa_build_finish: %s (a slab holds whole 6-letter prefixes)", kasa_spill_plan::refusal_text(b->plan).c_str());
+        b->result.n = 0; b->nTrie = 0;
+    }
+    b->state = kasa_builder::SLABS; b->slabNext = 0;
+    b->records = b->spilled ? kasa_builder::BY_SLAB : kasa_builder::ON_DEVICE;
+    if (nSlabs) *nSlabs = b->nSlabs();
     return KASA_OK;
 }
 
@@ -128,6 +139,7 @@ static int slab_impl(kasa_builder *b, uint64_t s)
 {
     int rc;
     const kasa_spill_plan::Slab &sl = b->plan.slabs[(size_t)s];
+    const bool last = s + 1 == b->plan.slabs.size();
     for (DevBuf *d : {&b->rec, &b->trieFirst, &b->triePrefix, &b->trieCount}) d->release();   // (the slab before)
     std::vector<kasa_builder::Run> runs;
     {
@@ -151,31 +163,20 @@ static int slab_impl(kasa_builder *b, uint64_t s)
     }
     if (runs.empty()) runs.emplace_back();
     b->result = std::move(runs[0]);
-    {
-        StageClock clk(&b->ms[3], b->stream);
-        if ((rc = emit_result<Key>(b))) return rc;
-        if (s == 0 && (rc = freq_zero<Key>(b))) return rc;
-        if ((rc = freq_accumulate<Key>(b, b->result.k.as<Key>(), b->result.v.as<uint32_t>(), b->result.n))) return rc;
-        if (s + 1 == b->plan.slabs.size() && (rc = freq_final<Key>(b))) return rc;
-        clk.stop();
-    }
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->result.k.release(); b->result.v.release();
-    b->totalRec += b->result.n; b->totalTrie += b->nTrie;
-    if (s + 1 == b->plan.slabs.size()) b->hostRuns.clear();           // the last slab: the host memory of the runs goes back
+    if ((rc = finish_slab<Key>(b, s == 0, last))) return rc;
+    if (last) b->hostRuns.clear();                                     // the host memory of the runs goes back
     return KASA_OK;
 }
 
 static int build_slab_impl(kasa_builder *b, uint64_t slab, uint64_t *nRecords, uint64_t *nTrie)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->phase != 1) return fail(KASA_E_STATE, b->phase == 0 ? "kasa_build_slab: kasa_build_finish_begin first" : "kasa_build_slab: the build is finished");
-    const uint64_t nSlabs = b->spilled ? b->plan.slabs.size() : 1;
-    if (slab != b->slabNext || slab >= nSlabs)
+    if (b->state != kasa_builder::SLABS) return fail(KASA_E_STATE, b->state == kasa_builder::ADDING ? "kasa_build_slab: kasa_build_finish_begin first" : "kasa_build_slab: the build is finished");
+    if (slab != b->slabNext || slab >= b->nSlabs())
         return fail(KASA_E_STATE, "kasa_build_slab: slab %llu asked, slab %llu of %llu is next (the slabs are taken in order, each once)", (unsigned long long)slab,
-                    (unsigned long long)b->slabNext, (unsigned long long)nSlabs);
+                    (unsigned long long)b->slabNext, (unsigned long long)b->nSlabs());
     HIPCHK(hipSetDevice(b->device));
-    if (b->spilled) { if (int rc = b->wide ? slab_impl<key128>(b, slab) : slab_impl<uint64_t>(b, slab)) return rc; }
+    if (b->spilled) { if (int rc = b->wide ? slab_impl<key128>(b, slab) : slab_impl<uint64_t>(b, slab)) return rc; }   // (else: finish_begin made the one slab)
     ++b->slabNext;
     if (nRecords) *nRecords = b->result.n;
     if (nTrie) *nTrie = b->nTrie;
@@ -185,7 +186,7 @@ static int build_slab_impl(kasa_builder *b, uint64_t slab, uint64_t *nRecords, u
 static int build_fetch_slab_impl(kasa_builder *b, uint64_t first, uint64_t count, void *records, uint32_t *triePrefix, uint64_t *trieCount)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->phase != 1 || b->slabNext == 0) return fail(KASA_E_STATE, "kasa_build_fetch_slab: no slab is current (kasa_build_slab first, kasa_build_finish_end after the last fetch)");
+    if (b->state != kasa_builder::SLABS || b->slabNext == 0) return fail(KASA_E_STATE, "kasa_build_fetch_slab: no slab is current (kasa_build_slab first, kasa_build_finish_end after the last fetch)");
     if (first > b->result.n || count > b->result.n - first)
         return fail(KASA_E_ARG, "kasa_build_fetch_slab: [%llu, +%llu) outside the slab's %llu records", (unsigned long long)first, (unsigned long long)count, (unsigned long long)b->result.n);
     HIPCHK(hipSetDevice(b->device));
@@ -201,15 +202,13 @@ static int build_fetch_slab_impl(kasa_builder *b, uint64_t first, uint64_t count
 static int build_finish_end_impl(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->phase != 1) return fail(KASA_E_STATE, b->phase == 0 ? "kasa_build_finish_end: kasa_build_finish_begin first" : "kasa_build_finish_end: called twice");
-    const uint64_t nSlabs = b->spilled ? b->plan.slabs.size() : 1;
-    if (b->slabNext != nSlabs)
-        return fail(KASA_E_STATE, "kasa_build_finish_end: %llu of %llu slabs were taken", (unsigned long long)b->slabNext, (unsigned long long)nSlabs);
-    if (b->spilled) {
+    if (b->state != kasa_builder::SLABS) return fail(KASA_E_STATE, b->state == kasa_builder::ADDING ? "kasa_build_finish_end: kasa_build_finish_begin first" : "kasa_build_finish_end: called twice");
+    if (b->slabNext != b->nSlabs())
+        return fail(KASA_E_STATE, "kasa_build_finish_end: %llu of %llu slabs were taken", (unsigned long long)b->slabNext, (unsigned long long)b->nSlabs());
+    if (b->records != kasa_builder::ON_DEVICE)                         // (the last slab; records on the device stay for kasa_build_fetch)
         for (DevBuf *d : {&b->rec, &b->trieFirst, &b->triePrefix, &b->trieCount}) d->release();
-        b->result.n = b->totalRec; b->nTrie = b->totalTrie;
-    }
-    b->phase = 2;
+    b->result.n = b->totalRec; b->nTrie = b->totalTrie;
+    b->state = kasa_builder::DONE;
     if (nRecords) *nRecords = b->result.n;
     if (nTrie) *nTrie = b->nTrie;
     return KASA_OK;
@@ -225,15 +224,16 @@ static int finish_all(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie)
     for (uint64_t s = 0; s < nSlabs; ++s) {
         uint64_t n = 0, m = 0;
         if ((rc = build_slab_impl(b, s, &n, &m))) return rc;
-        if (!b->spilled) continue;
+        if (b->records == kasa_builder::ON_DEVICE) continue;
         const size_t rb = (size_t)b->recBytes(), at = b->hRec.size(), tAt = b->hTriePrefix.size();
         b->hRec.resize(at + (size_t)n * rb);
         b->hTriePrefix.resize(tAt + (size_t)m);
         b->hTrieCount.resize(tAt + (size_t)m);
         if ((rc = build_fetch_slab_impl(b, 0, n, b->hRec.data() + at, b->hTriePrefix.data() + tAt, b->hTrieCount.data() + tAt))) return rc;
     }
-    b->collected = b->spilled;
-    return build_finish_end_impl(b, nRecords, nTrie);
+    if ((rc = build_finish_end_impl(b, nRecords, nTrie))) return rc;
+    if (b->records == kasa_builder::BY_SLAB) b->records = kasa_builder::GATHERED;
+    return KASA_OK;
 }
 
 } // namespace kasa_build_impl
@@ -241,7 +241,7 @@ static int finish_all(kasa_builder *b, uint64_t *nRecords, uint64_t *nTrie)
 extern "C" int kasa_build_set_resident(kasa_builder *b, uint64_t maxResidentRecords)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->added || b->finished) return fail(KASA_E_STATE, "kasa_build_set_resident: the budget is set before the first kasa_build_add");
+    if (b->added || b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_set_resident: the budget is set before the first kasa_build_add");
     if (b->edited) return fail(KASA_E_STATE, "kasa_build_set_resident: edits need the runs on the device");
     b->resident = maxResidentRecords;
     return KASA_OK;
@@ -250,7 +250,7 @@ extern "C" int kasa_build_set_resident(kasa_builder *b, uint64_t maxResidentReco
 extern "C" int kasa_build_finish_begin(kasa_builder *b, uint64_t *nSlabs)
 {
     if (!b) return fail(KASA_E_ARG, "builder is NULL");
-    if (b->finished || b->phase != 0) return fail(KASA_E_STATE, "kasa_build_finish_begin: called twice");
+    if (b->state != kasa_builder::ADDING) return fail(KASA_E_STATE, "kasa_build_finish_begin: called twice");
     HIPCHK(hipSetDevice(b->device));
     KASA_GUARDED(b->wide ? kasa_build_impl::finish_begin_impl<key128>(b, nSlabs) : kasa_build_impl::finish_begin_impl<uint64_t>(b, nSlabs))
 }
@@ -274,7 +274,7 @@ extern "C" int kasa_build_spill_stats(kasa_builder *b, uint64_t *stats8)
 {
     if (!b || !stats8) return fail(KASA_E_ARG, "kasa_build_spill_stats: NULL argument");
     stats8[0] = b->spillRuns; stats8[1] = b->spillRecords;
-    stats8[2] = b->spilled && b->phase ? b->plan.slabs.size() : 0;
+    stats8[2] = b->spilled && b->state != kasa_builder::ADDING ? b->plan.slabs.size() : 0;
     stats8[3] = b->spilled ? b->plan.largestSlab : 0;
     stats8[4] = b->spilled ? b->plan.heaviestCount : 0;
     stats8[5] = b->spilled ? (uint64_t)(b->usUp + 0.5) : 0; stats8[6] = b->spilled ? (uint64_t)(b->usDown + 0.5) : 0; stats8[7] = 0;

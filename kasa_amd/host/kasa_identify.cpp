@@ -2804,49 +2804,27 @@ static void writeFreqFile(const string &path, const Content &c, int K, const vec
     if (!f) throw std::runtime_error("writing " + path + " failed");
 }
 
-// the index files of a finished builder under `prefix` (formats.write_index's layout): records (12, 20 or, halved, 6 bytes),
-// _info.txt (count + infoTail), _trie, _trie.txt and, withFreq, _f.txt
-static void writeIndexFiles(kasa_builder *b, const string &index, const Content &c, int K, uint64_t nRec, uint64_t nTrie, const char *infoTail, bool withFreq)
+// _trie ({u64 count, u32 prefix} per entry, 12 bytes packed) and _trie.txt (the number of entries)
+static void writeTrieFiles(const string &triePath, const string &countPath, const vector<uint32_t> &prefix, const vector<uint64_t> &count)
 {
-    const size_t nTaxa = c.taxids.size(), recBytes = string(infoTail) == "\n3" ? 6 : (K == 25 ? 20 : 12);
-    vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie), freq(nTaxa * (size_t)K);
-    if (kasa_build_fetch(b, nullptr, tp.data(), tc.data(), freq.data())) throwLast();
-    {
-        FILE *f = fopen(index.c_str(), "wb");
-        if (!f) throw std::runtime_error("The index file cannot be written: " + index);
-        const uint64_t step = std::max<uint64_t>(1, ((uint64_t)256 << 20) / recBytes);
-        vector<uint8_t> bufs[2] = {vector<uint8_t>((size_t)std::min(step, nRec) * recBytes), vector<uint8_t>((size_t)std::min(step, nRec) * recBytes)};
-        std::future<size_t> pending;                                                          // a range is written while the next one is copied
-        int cur = 0;
-        for (uint64_t first = 0; first < nRec; first += step) {
-            const uint64_t cnt = std::min(step, nRec - first);
-            if (kasa_build_fetch_range(b, first, cnt, bufs[cur].data())) { if (pending.valid()) pending.get(); fclose(f); throwLast(); }
-            if (pending.valid() && pending.get() == 0) { fclose(f); throw std::runtime_error("writing the index file failed"); }
-            const uint8_t *src = bufs[cur].data(); const size_t bytes = (size_t)cnt * recBytes;
-            pending = std::async(std::launch::async, [f, src, bytes] { return fwrite(src, 1, bytes, f) == bytes ? bytes + 1 : (size_t)0; });
-            cur ^= 1;
-        }
-        if (pending.valid() && pending.get() == 0) { fclose(f); throw std::runtime_error("writing the index file failed"); }
-        if (fclose(f) != 0) throw std::runtime_error("writing the index file failed");
-    }
-    { std::ofstream f(index + "_info.txt", std::ios::binary); f << nRec << infoTail; }
-    {
-        vector<uint8_t> t(nTrie * 12);
-        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
-        std::ofstream f(index + "_trie", std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
-        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
-    }
-    if (withFreq) writeFreqFile(index + "_f.txt", c, K, freq);
+    vector<uint8_t> t(prefix.size() * 12);
+    for (size_t j = 0; j < prefix.size(); ++j) { memcpy(&t[j * 12], &count[j], 8); memcpy(&t[j * 12 + 8], &prefix[j], 4); }
+    std::ofstream f(triePath, std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
+    std::ofstream g(countPath, std::ios::binary); g << prefix.size();
+    if (!f || !g) throw std::runtime_error("writing " + triePath + " failed");
 }
 
-// The finish of a build slab by slab (kasa_build_finish_begin / slab / fetch_slab / finish_end: one slab for an index that fits
-// the device, key-range slabs for one that was spilled to host memory): the records file is written as the slabs come, a range
-// while the next one is copied, the trie is gathered and _info.txt, _trie, _trie.txt and _f.txt are written at the end.  An
-// error leaves no _info.txt, and no records file of this run.  tFinish: the seconds inside finish_begin and slab.
-static void writeIndexBySlabs(kasa_builder *b, const string &index, const Content &c, int K, const char *infoTail, uint64_t &nRec, uint64_t &nTrie, uint64_t &nSlabs,
-                              double &tFinish)
+// The finish of a builder and its index files under `index` (formats.write_index's layout), slab by slab (kasa_build_finish_begin /
+// slab / fetch_slab / finish_end: one slab when the runs stayed on the device, key-range slabs when they were spilled to host
+// memory): the records file is written as the slabs come, a range while the next one is copied, the trie is gathered and
+// _info.txt, _trie, _trie.txt and _f.txt are written at the end.  An error leaves no _info.txt, and no records file of this run.
+// halved (shrink -s 2): records of 6 bytes, "3" in _info.txt and no _f.txt -- the caller copies the one of the full index.
+// emptyIsError: `build` refuses an index without records; an edit may leave none: an empty records file and _info.txt = 0.
+// tFinish: the seconds inside finish_begin and slab.
+static void writeIndexBySlabs(kasa_builder *b, const string &index, const Content &c, int K, bool halved, bool emptyIsError, uint64_t &nRec, uint64_t &nTrie,
+                              uint64_t &nSlabs, double &tFinish)
 {
-    const size_t nTaxa = c.taxids.size(), recBytes = K == 25 ? 20 : 12;
+    const size_t nTaxa = c.taxids.size(), recBytes = halved ? 6 : (K == 25 ? 20 : 12);
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&]() { tFinish += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
     if (kasa_build_finish_begin(b, &nSlabs)) throwLast();
@@ -2867,7 +2845,7 @@ static void writeIndexBySlabs(kasa_builder *b, const string &index, const Conten
             const size_t at = tp.size();
             tp.resize(at + m); tc.resize(at + m);
             if (m && kasa_build_fetch_slab(b, 0, 0, nullptr, tp.data() + at, tc.data() + at)) throwLast();
-            if (n && !f) {
+            if (!f && (n || !emptyIsError)) {                  // (an empty build leaves no records file behind)
                 f = fopen(index.c_str(), "wb");
                 if (!f) throw std::runtime_error("The index file cannot be written: " + index);
             }
@@ -2883,19 +2861,16 @@ static void writeIndexBySlabs(kasa_builder *b, const string &index, const Conten
         }
         if (pending.valid() && pending.get() == 0) throw std::runtime_error("writing the index file failed");
         if (kasa_build_finish_end(b, &nRec, &nTrie)) throwLast();
-        if (nRec == 0) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
+        if (nRec == 0 && emptyIsError) throw std::runtime_error("Index is empty, are all input files okay?");     // Read.hpp:3116
         if (f) { FILE *g = f; f = nullptr; if (fclose(g) != 0) throw std::runtime_error("writing the index file failed"); }
     } catch (...) { drop(); throw; }
-    vector<uint64_t> freq(nTaxa * (size_t)K);
-    if (kasa_build_fetch(b, nullptr, nullptr, nullptr, freq.data())) throwLast();
-    { std::ofstream o(index + "_info.txt", std::ios::binary); o << nRec << infoTail; }
-    {
-        vector<uint8_t> t(nTrie * 12);
-        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
-        std::ofstream o(index + "_trie", std::ios::binary); o.write((const char *)t.data(), (std::streamsize)t.size());
-        std::ofstream g(index + "_trie.txt", std::ios::binary); g << nTrie;
+    { std::ofstream o(index + "_info.txt", std::ios::binary); o << nRec << (halved ? "\n3" : (K == 25 ? "\n128" : "")); }
+    writeTrieFiles(index + "_trie", index + "_trie.txt", tp, tc);
+    if (!halved) {
+        vector<uint64_t> freq(nTaxa * (size_t)K);
+        if (kasa_build_fetch(b, nullptr, nullptr, nullptr, freq.data())) throwLast();
+        writeFreqFile(index + "_f.txt", c, K, freq);
     }
-    writeFreqFile(index + "_f.txt", c, K, freq);
 }
 
 static int buildMode(const vector<string> &a)
@@ -2953,7 +2928,7 @@ static int buildMode(const vector<string> &a)
     uint64_t nRec = 0, nTrie = 0, nSlabs = 0;
     // the finish and the files, slab by slab: records, _info.txt, _trie, _trie.txt, _f.txt (formats.write_index's layout)
     double tFinish = 0;
-    writeIndexBySlabs(b, index, bc.c, K, K == 25 ? "\n128" : "", nRec, nTrie, nSlabs, tFinish);
+    writeIndexBySlabs(b, index, bc.c, K, false, true, nRec, nTrie, nSlabs, tFinish);
     const double tWrite = secs(tf) - tFinish;
     uint64_t st[8] = {0}, sp[8] = {0};
     if (kasa_build_stats(b, st) || kasa_build_spill_stats(b, sp)) throwLast();
@@ -3125,13 +3100,13 @@ static int editMode(const vector<string> &a)
     loadIndexRun(b, index, n, recBytes, tRead, tUpload);
     uint64_t nSeq = 0, nSkipped = 0;
     if (mode == "update") addDatabase(b, input, bc, threads, verbose, nSeq, nSkipped, tParse, tAdd);
-    auto tf = std::chrono::steady_clock::now();
-    uint64_t nRec = 0, nTrie = 0;
-    if (kasa_build_finish(b, &nRec, &nTrie)) throwLast();
-    const double tFinish = secs(tf);
-    tf = std::chrono::steady_clock::now();
+    const auto tf = std::chrono::steady_clock::now();
+    uint64_t nRec = 0, nTrie = 0, nSlabs = 0;
+    double tFinish = 0;
     StagedFiles staged(out);
     if (mode == "getFrequency") {
+        if (kasa_build_finish(b, &nRec, &nTrie)) throwLast();
+        tFinish = secs(tf);
         vector<uint64_t> freq(bc.c.taxids.size() * (size_t)K);
         if (kasa_build_fetch(b, nullptr, nullptr, nullptr, freq.data())) throwLast();
         writeFreqFile(staged.add("_f.txt", index + "_f.txt"), bc.c, K, freq);
@@ -3140,7 +3115,7 @@ static int editMode(const vector<string> &a)
         const string tmp = staged.add("", out);
         for (const char *suf : {"_info.txt", "_trie", "_trie.txt", "_f.txt"}) staged.add(suf, out + suf);
         // (delete of a 128-bit index: the reference omits the "128" line, Update.hpp:75, and its own identify would misread the index)
-        writeIndexFiles(b, tmp, bc.c, K, nRec, nTrie, halved ? "\n3" : (K == 25 ? "\n128" : ""), !halved);
+        writeIndexBySlabs(b, tmp, bc.c, K, halved, false, nRec, nTrie, nSlabs, tFinish);
         if (halved) {                                                                       // the frequency file of the full index (Shrink.hpp:381-392)
             std::ifstream src(index + "_f.txt", std::ios::binary);
             if (!src) throw std::runtime_error("The frequency file of the index cannot be found: " + index + "_f.txt");
@@ -3154,7 +3129,7 @@ static int editMode(const vector<string> &a)
         }
     }
     staged.commit();
-    const double tWrite = secs(tf);
+    const double tWrite = secs(tf) - tFinish;
     uint64_t st[8] = {0}, es[4] = {0};
     if (kasa_build_stats(b, st) || kasa_build_edit_stats(b, es)) throwLast();
     std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries; " << es[0] << " read from the index, " << es[1] << " deleted, " << es[2] << " shrunk away";
@@ -3325,17 +3300,15 @@ static int indexToolMode(const vector<string> &a)
         auto b = create(bc, K);
         loadIndexRun(b.get(), first, n1, recBytes, tRead, tUpload);
         loadIndexRun(b.get(), second, n2, recBytes, tRead, tUpload);
-        auto tf = std::chrono::steady_clock::now();
-        uint64_t nRec = 0, nTrie = 0;
-        if (kasa_build_finish(b.get(), &nRec, &nTrie)) throwLast();
-        const double tFinish = secs(tf);
-        tf = std::chrono::steady_clock::now();
+        const auto tf = std::chrono::steady_clock::now();
+        uint64_t nRec = 0, nTrie = 0, nSlabs = 0;
+        double tFinish = 0;
         const string tmp = staged.add("", out);
         for (const char *suf : {"_info.txt", "_trie", "_trie.txt", "_f.txt"}) staged.add(suf, out + suf);
         // (the reference writes no _info.txt and an _f.txt of zeros, Read.hpp:3221,3238: here the result can be identified against at once)
-        writeIndexFiles(b.get(), tmp, bc.c, K, nRec, nTrie, K == 25 ? "\n128" : "", true);
+        writeIndexBySlabs(b.get(), tmp, bc.c, K, false, false, nRec, nTrie, nSlabs, tFinish);
         staged.commit();
-        const double tWrite = secs(tf);
+        const double tWrite = secs(tf) - tFinish;
         uint64_t st[8] = {0}, es[4] = {0};
         if (kasa_build_stats(b.get(), st) || kasa_build_edit_stats(b.get(), es)) throwLast();
         std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries; " << es[0] << " read from the two indices, " << es[0] - nRec << " in both" << std::endl;
@@ -3395,13 +3368,8 @@ static int indexToolMode(const vector<string> &a)
     vector<uint32_t> tp(nTrie); vector<uint64_t> tc(nTrie);
     if (kasa_build_fetch(b.get(), nullptr, tp.data(), tc.data(), nullptr)) throwLast();                               // (no record comes down)
     StagedFiles staged(index);
-    {
-        vector<uint8_t> t(nTrie * 12);
-        for (uint64_t j = 0; j < nTrie; ++j) { memcpy(&t[j * 12], &tc[j], 8); memcpy(&t[j * 12 + 8], &tp[j], 4); }
-        std::ofstream f(staged.add("_trie", index + "_trie"), std::ios::binary); f.write((const char *)t.data(), (std::streamsize)t.size());
-        std::ofstream g(staged.add("_trie.txt", index + "_trie.txt"), std::ios::binary); g << nTrie;
-        if (!f || !g) throw std::runtime_error("writing the trie of " + index + " failed");
-    }
+    const string triePath = staged.add("_trie", index + "_trie"), countPath = staged.add("_trie.txt", index + "_trie.txt");
+    writeTrieFiles(triePath, countPath, tp, tc);
     staged.commit();
     std::cout << "OUT: Index: " << nRec << " entries, trie: " << nTrie << " entries" << std::endl;
     std::cout << "OUT: Time: " << (long long)secs(t0) << " s" << std::endl;

@@ -5,6 +5,8 @@ corpus's plain reference, all exact.  A halved result (shrink 2) is compared as 
 records.  tests/test_build_corpus_cpu.py shows on the CPU that every case holds what its family claims.
 
 No case is left out: every family's test runs all of the family's cases and counts them, and the counts add up to the corpus's.
+Every case with an index, drop or shrink step runs a second time finished by finish_slabs() -- the calls the C++ edit modes and
+`kasa_index merge` write their files through: exactly one slab, and the same comparisons.
 
 The C++ hosts run one round trip -- `kasa_identify build` twice, `kasa_index merge`, `kasa_identify shrink -s 2` -- on the small
 amino-acid database of tests/golden/dbedit/halved_pads/, whose sequences hold '^' and '~': against the plain reference's
@@ -44,8 +46,28 @@ def _refusal(ex):
     return str(ex)
 
 
-def run_case(c, monkeypatch):
-    """the case through one capi.Builder, everything compared with the reference; raises AssertionError with the case's name"""
+def _finish_by_slabs(b, c):
+    """finish_slabs() in fetch()'s form, for a builder whose runs stayed on the device: exactly one slab"""
+    parts = list(b.finish_slabs())
+    assert len(parts) == 1, f"{c.name}: {len(parts)} slabs"
+    rec, tp, tc = parts[0]
+    assert (b.n_records, b.n_trie) == (rec.shape[0], tp.shape[0]), c.name
+    b.raw_records = rec
+    if rec.dtype == formats.HALF_DTYPE:                              # (as fetch() rebuilds a halved result)
+        km = (np.repeat(tp.astype(np.uint64), tc.astype(np.int64)) << np.uint64(30)) | rec["low"].astype(np.uint64)
+        tid = b.taxids[rec["tax"].astype(np.int64)]
+    elif c.K == 25:
+        km = np.zeros(rec.shape[0], dtype=formats.KEY128_DTYPE)
+        km["lo"], km["hi"] = rec["lo"], rec["hi"]
+        tid = np.ascontiguousarray(rec["tax"])
+    else:
+        km, tid = np.ascontiguousarray(rec["kmer"]), np.ascontiguousarray(rec["tax"])
+    return b.n_records, b.n_trie, (km, tid, tp, tc, b.fetch_freq())
+
+
+def run_case(c, monkeypatch, by_slabs=False):
+    """the case through one capi.Builder, everything compared with the reference; raises AssertionError with the case's name.
+    by_slabs: finished by finish_slabs() (finish_begin / slab / fetch_slab / finish_end) instead of finish() + fetch()."""
     e = bc.expect(c)
     if c.edit_chunk:
         monkeypatch.setenv("KASA_EDIT_CHUNK_RECORDS", str(c.edit_chunk))
@@ -71,14 +93,17 @@ def run_case(c, monkeypatch):
                 break
         if error is None:
             try:
-                n, m = b.finish()
+                if by_slabs:
+                    n, m, fetched = _finish_by_slabs(b, c)
+                else:
+                    n, m = b.finish()
             except RuntimeError as ex:
                 error = ("finish", _refusal(ex))
         if e.error is not None:
             assert error is not None and error[0] == e.error[0] and e.error[1] in error[1], f"{c.name}: refusal {error}, expected {e.error}"
             return
         assert error is None, f"{c.name}: refused at step {error[0]}: {error[1]}"
-        km, tid, tp, tc, freq = b.fetch()
+        km, tid, tp, tc, freq = fetched if by_slabs else b.fetch()
         wkm, wtid, wtp, wtc = bc.arrays(e, c.K)
         assert n == wkm.shape[0] and m == wtp.shape[0], f"{c.name}: {n} records and {m} trie entries, expected {wkm.shape[0]} and {wtp.shape[0]}"
         assert np.array_equal(km, wkm), f"{c.name}: k-mers differ, first at {_first_difference(km, wkm)} of {n}"
@@ -140,6 +165,26 @@ def test_large(name, monkeypatch):
     run_case(c, monkeypatch)
     RAN[name] = 1
     bc.case.cache_clear()
+
+
+def _edits(c):
+    return any(step[0] in ("index", "drop", "shrink") for step in c.steps)
+
+
+def test_edited_builders_through_the_slab_calls(monkeypatch):
+    """Every case of the small families with an index, drop or shrink step, refusals included, finished by finish_begin / slab /
+    fetch_slab / finish_end as the C++ edit modes and `kasa_index merge` finish: one slab, everything else as in test_family."""
+    _gpu_or_fail()
+    names = [n for n in bc.case_names() if _edits(bc.case(n))]
+    ran, failures = 0, []
+    for name in names:
+        try:
+            run_case(bc.case(name), monkeypatch, by_slabs=True)
+        except AssertionError as ex:
+            failures.append(str(ex))
+        ran += 1
+    assert ran == sum(1 for f in SMALL_FAMILIES for n in bc.case_names(f) if _edits(bc.case(n))) and ran > 0
+    assert not failures, "%d of %d cases differ:\n%s" % (len(failures), ran, "\n".join(failures[:20]))
 
 
 def test_every_case_ran():

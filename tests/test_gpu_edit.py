@@ -107,6 +107,21 @@ def test_cpp_delete_onto_itself(tmp_path):
     _same(str(tmp_path / "x"), os.path.join(d, "idx"))
 
 
+def test_cpp_delete_every_taxon_leaves_an_empty_index(tmp_path):
+    """delnodes lists every taxon of the small halved_pads database: no record is left, which `build` refuses and an edit writes --
+    a records file of 0 bytes, _info.txt = 0, an empty _trie, _trie.txt = 0, exit status 0."""
+    d = os.path.join(DBEDIT, "halved_pads")
+    content, delnodes = tmp_path / "c.txt", tmp_path / "delnodes.dmp"
+    content.write_text("ProtA\t21\t21\tP0.1;P2.1\nProtB\t22\t22\tP1.1;P3.1;P5.1\nProtC\t23\t23\tP4.1\n")
+    delnodes.write_text("21\t|\n22\t|\n23\t|\n")
+    assert int(_read(os.path.join(d, "idx_info.txt"))) > 0
+    r = _host(["delete", "-d", os.path.join(d, "idx"), "-o", str(tmp_path / "n"), "-l", str(delnodes), "-c", str(content)], tmp_path)
+    assert r.returncode == 0 and "OUT: Index: 0 entries, trie: 0 entries" in r.stdout, r.stdout
+    assert _read(str(tmp_path / "n")) == b"" and _read(str(tmp_path / "n_info.txt")) == b"0"
+    assert _read(str(tmp_path / "n_trie")) == b"" and _read(str(tmp_path / "n_trie.txt")) == b"0"
+    assert sorted(os.listdir(tmp_path)) == sorted(["c.txt", "delnodes.dmp"] + ["n" + s for s in SUFFIXES])
+
+
 SHRINK = [("s1_30", "update64", ["-s", "1", "-g", "30"]), ("s1_333", "update64", ["-s", "1", "-g", "33.3"]),
           ("s1_150", "update64", ["-s", "1", "-g", "150"]), ("s1_333w", "update128", ["-s", "1", "-g", "33.3"]),
           ("s3", "update64", ["-s", "3"]), ("s3w", "update128", ["-s", "3"])]

@@ -8,9 +8,11 @@ runs or more.  The two `tiny/long protein` cases hold 196 650 records with a pre
 thousand slabs, minutes of launches -- they run at 4096 B and 16384 B instead (some dozens of slabs), everything else compared
 alike.  The hand-made cases of tests/spill_corpus.py run through finish() + fetch() and through finish_slabs(): slab count, every
 slab's records and trie entries and spill_stats() equal the corpus's restatement of the rule, the concatenation equals the
-reference.  Refusals are checked by their text.  A builder with budget 0 gives the same bytes and spill_stats() all zero.  The C++
+reference.  Refusals are checked by their text, and a tiny builder per key width and place of the runs is walked through every
+state with every entry point called out of order (PROTOCOL: status and text).  A builder with budget 0 gives the same bytes and spill_stats() all zero.  The C++
 host builds tests/golden/batches and tests/golden/pairs (--kH 25) in dozens of bricks under a budget of an eighth of the index:
 the five files byte for byte."""
+import ctypes as C
 import gzip
 import os
 import re
@@ -224,8 +226,126 @@ def test_refusals(K):
         b.close()
 
 
+# ---- calls out of order, in every state ------------------------------------------------------------------------------------------------
+OK, E_STATE = 0, 4                                  # KASA_OK, KASA_E_STATE of include/kasa_hip.h
+FINISHED, TWICE, BEGIN_FIRST, FINISH_FIRST = "the build is finished", "called twice", "kasa_build_finish_begin first", "kasa_build_finish first"
+BEFORE_ADD, NO_SLAB, NEED_DEVICE = "before the first kasa_build_add", "no slab is current", "edits need the runs on the device"
+BY_SLAB, END_FIRST, NOT_ON_DEVICE = "handed out slab by slab", "kasa_build_finish_end first", "spilled build are not on the device"
+# What every entry point answers in every state: None = KASA_OK, a text = KASA_E_STATE with that text; {n} = the slabs.  The rows
+# left out of a state are the calls that are in order there.  `slab` is asked for slab 7, which is never next.
+AFTER_THE_FINISH = dict(add=FINISHED, add_index=FINISHED, drop_taxa=FINISHED, shrink=FINISHED, set_resident=BEFORE_ADD, finish=TWICE, finish_begin=TWICE)
+DONE = dict(AFTER_THE_FINISH, slab=FINISHED, fetch_slab=NO_SLAB, finish_end=TWICE)
+NOT_BEGUN = dict(set_resident=BEFORE_ADD, slab=BEGIN_FIRST, fetch_slab=NO_SLAB, finish_end=BEGIN_FIRST, fetch=FINISH_FIRST, fetch_range=FINISH_FIRST,
+                 taxa_histogram=FINISH_FIRST)
+ON_DEVICE = dict(fetch=None, fetch_range=None, taxa_histogram=None)
+PROTOCOL = {
+    # the runs on the device: one slab, made by finish_begin; records, trie and histogram are there from then on
+    ("device", "adding"): dict(NOT_BEGUN, add=None, add_index=None, drop_taxa=None, shrink=None),
+    ("device", "begun"): dict(AFTER_THE_FINISH, **ON_DEVICE, slab="slab 7 asked, slab 0 of 1 is next", fetch_slab=NO_SLAB, finish_end="0 of 1 slabs were taken"),
+    ("device", "slab 0"): dict(AFTER_THE_FINISH, **ON_DEVICE, slab="slab 7 asked, slab 1 of 1 is next", fetch_slab=None),
+    ("device", "ended"): dict(DONE, **ON_DEVICE),
+    ("device", "finish"): dict(DONE, **ON_DEVICE),
+    # the runs in host memory (a budget of one record)
+    ("host", "adding"): dict(NOT_BEGUN, add=None, add_index=NEED_DEVICE, drop_taxa=NEED_DEVICE, shrink=NEED_DEVICE),
+    ("host", "begun"): dict(AFTER_THE_FINISH, slab="slab 7 asked, slab 0 of {n} is next", fetch_slab=NO_SLAB, finish_end="0 of {n} slabs were taken",
+                            fetch=END_FIRST, fetch_range=BY_SLAB, taxa_histogram=NOT_ON_DEVICE),
+    ("host", "slab 0"): dict(AFTER_THE_FINISH, slab="slab 7 asked, slab 1 of {n} is next", fetch_slab=None, finish_end="1 of {n} slabs were taken",
+                             fetch=END_FIRST, fetch_range=BY_SLAB, taxa_histogram=NOT_ON_DEVICE),
+    ("host", "ended"): dict(DONE, fetch=BY_SLAB, fetch_range=BY_SLAB, taxa_histogram=NOT_ON_DEVICE),
+    ("host", "finish"): dict(DONE, fetch=None, fetch_range=None, taxa_histogram=NOT_ON_DEVICE),
+}
+ENTRY_POINTS = ("add", "add_index", "drop_taxa", "shrink", "set_resident", "finish", "finish_begin", "slab", "fetch_slab", "finish_end", "fetch", "fetch_range",
+                "taxa_histogram")
+
+
+class _Tiny:
+    """two amino-acid sequences whose windows share no 6-letter prefix, one brick; every entry point by name -> (status, message)"""
+    TAXIDS = np.array([0, 11, 22, 33], dtype=np.uint32)
+    SEQS = (b"ACDEFGHI", b"YWVTSRQP")
+
+    def __init__(self, K, budget):
+        self.b = capi.Builder(self.TAXIDS, K, 3, None, 0, 0, budget)
+        self.bases = np.frombuffer(b"".join(self.SEQS), dtype=np.uint8)
+        self.off = np.array([0, 8, 16], dtype=np.int64)
+        self.tax = np.array([11, 22], dtype=np.uint32)
+        self.drop = np.array([33], dtype=np.uint32)                   # (no record carries it)
+        self.tp, self.tc = np.zeros(4096, dtype=np.uint32), np.zeros(4096, dtype=np.uint64)     # at most 16 trie entries
+        self.freq = np.zeros((4, K), dtype=np.uint64)
+        self.hist = np.zeros(5, dtype=np.uint64)
+        self.n, self.m, self.d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(self, name, slab=7):
+        L, h, u64, p = capi.lib(), self.b.h, C.c_uint64, lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = {
+            "add": lambda: L.kasa_build_add(h, p(self.bases), p(self.off), C.c_int64(2), p(self.tax), C.c_int(1)),
+            "add_index": lambda: L.kasa_build_add_index(h, u64(0), u64(0), u64(0), None),
+            "drop_taxa": lambda: L.kasa_build_drop_taxa(h, p(self.drop), u64(1)),
+            "shrink": lambda: L.kasa_build_shrink(h, C.c_int(1), C.c_float(0)),       # (every n-th with percentage 0: no record goes)
+            "set_resident": lambda: L.kasa_build_set_resident(h, u64(5)),
+            "finish": lambda: L.kasa_build_finish(h, C.byref(self.n), C.byref(self.m)),
+            "finish_begin": lambda: L.kasa_build_finish_begin(h, C.byref(self.n)),
+            "slab": lambda: L.kasa_build_slab(h, u64(slab), C.byref(self.d), C.byref(self.m)),
+            "fetch_slab": lambda: L.kasa_build_fetch_slab(h, u64(0), u64(0), None, p(self.tp), p(self.tc)),
+            "finish_end": lambda: L.kasa_build_finish_end(h, C.byref(self.d), C.byref(self.m)),
+            "fetch": lambda: L.kasa_build_fetch(h, None, p(self.tp), p(self.tc), p(self.freq)),
+            "fetch_range": lambda: L.kasa_build_fetch_range(h, u64(0), u64(0), None),
+            "taxa_histogram": lambda: L.kasa_build_taxa_histogram(h, p(self.hist), u64(5), C.byref(self.d)),
+        }[name]()
+        return rc, L.kasa_last_error().decode() if rc else ""
+
+    def step(self, name, slab=7):
+        rc, text = self.call(name, slab)
+        assert rc == OK, f"{name}: {text}"
+
+    def check(self, where, state):
+        want = PROTOCOL[(where, state)]
+        for name in ENTRY_POINTS:
+            if name not in want:
+                continue
+            rc, text = self.call(name)
+            exp = want[name]
+            if exp is None:
+                assert rc == OK, f"{where}, {state}: {name} refused: {text}"
+            else:
+                assert rc == E_STATE and exp.format(n=self.n.value) in text, f"{where}, {state}: {name} gave {rc} {text!r}, expected {exp!r}"
+        return len(want)
+
+
+@pytest.mark.parametrize("K", bc.KS)
+@pytest.mark.parametrize("where,budget", [("device", 0), ("host", 1)])
+def test_calls_out_of_order_in_every_state(where, budget, K):
+    """One tiny builder walked through adding -> finish_begin -> slab(0) .. -> finish_end, a second one through finish: at every
+    stage every entry point that is not the next step is called once and answers what PROTOCOL says, by status and by text."""
+    _gpu_or_fail()
+    assert all(set(ENTRY_POINTS) - set(PROTOCOL[(where, s)]) <= {"finish", "finish_begin", "slab", "finish_end"} for s in ("adding", "begun", "slab 0", "ended", "finish"))
+    t = _Tiny(K, budget)
+    try:
+        t.step("add")
+        assert t.check(where, "adding") == 11
+        t.step("finish_begin")
+        n = t.n.value
+        assert n == (1 if where == "device" else 16)                 # (host: sixteen records, a prefix each, one to a slab)
+        assert t.check(where, "begun") == 13
+        t.step("slab", 0)
+        assert t.check(where, "slab 0") == (12 if where == "device" else 13)
+        for s in range(1, n):
+            t.step("slab", s)
+        t.step("finish_end")
+        assert t.check(where, "ended") == 13
+    finally:
+        t.b.close()
+    t = _Tiny(K, budget)
+    try:
+        t.step("add")
+        t.step("finish")
+        assert t.check(where, "finish") == 13
+        assert (t.n.value, t.freq.any()) == (16, True)
+    finally:
+        t.b.close()
+
+
 # ---- the C++ host ---------------------------------------------------------------------------------------------------------------------
-SUFFIXES = ("", "_trie", "_trie.txt", "_info.txt", "_f.txt")
+SUFFIXES =("", "_trie", "_trie.txt", "_info.txt", "_f.txt")
 
 
 def _read(path):
