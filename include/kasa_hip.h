@@ -890,6 +890,47 @@ int kasa_filter_split(int device, const char *records, const uint64_t *recOff, u
                       uint64_t *nOut, uint64_t *nReadsOut);
 void kasa_parse_destroy(kasa_parser *p);
 
+/* ---- an index larger than device memory: partitions come and go in slots (the reference streams its
+ *      index from disk, Compare.hpp:286-318).  The index is cut between `_trie` entries as for kasa_batch_slice_starts; a
+ *      slot of the pager is a kasa_index like any other, loaded again and again into the same device memory.
+ *   kasa_index_pager_create  nSlots (>= 1) slots for partitions of at most maxRecords records of recordBytes (12, 20 or 6: as
+ *                            kasa_index_create) -- keys, dense taxa, meta and a prefix table each --, one set of load
+ *                            transients (raw records, the taxon sort's arrays, rocPRIM scratch, the trie arrays) and one
+ *                            stream of the pager's own; the content's tax IDs go up once.  Nothing is allocated afterwards.
+ *   kasa_index_pager_load    copies `records` (host memory of any kind, e.g. the mapped file) up and prepares the slot on the
+ *                            pager's stream; returns when the slot is ready and the stream idle (overlap comes from a host
+ *                            thread of the caller's).  A slot that already holds partitionId: nothing happens, a hit is
+ *                            counted.  Refusals are kasa_index_create's, with its messages (unsorted or duplicate records, key
+ *                            bits beyond the width, an unknown tax ID, a trie that does not describe the records), plus
+ *                            KASA_E_LIMIT for nRecords > maxRecords; a refusal leaves the slot empty.  KASA_E_STATE while a
+ *                            context is bound to the slot.
+ *   kasa_index_pager_index   the slot as an index; KASA_E_STATE when it is empty.  Valid until the pager is destroyed; its
+ *                            contents change with the next load into the slot.
+ *   kasa_index_pager_stats   out[0..7] = loads, hits, bytes copied, copy us, prepare us, refused loads, device bytes of the
+ *                            pager, 1 when the prepare kernel searches the tax-ID table in LDS.
+ *   kasa_index_pager_tile    records a workgroup of the prepare kernel takes; most taxa whose table it searches in LDS.
+ *   kasa_ctx_set_index       the context works on another index of the same device, key width and number of taxa (else
+ *                            KASA_E_ARG) from its next batch on; its profile stays.  A pager counts the contexts bound to each of
+ *                            its slots (kasa_ctx_create, kasa_ctx_set_index); rebinding or destroying the context releases it.
+ *   kasa_batch_pool_keep     the owner of a sorted batch copies a grouped slice's pool into a buffer of its own and returns the
+ *                            copy's place, valid until kasa_batch_records_import_device; the next kasa_batch_sort_and_range
+ *                            clears the buffers.  (A worker that takes the next slice overwrites its pool.)
+ *   kasa_index_fetch         test tap: one array of an index (`what` below) to host memory; bytes must be the array's size
+ *                            (records x 8 or 16, x 4, x 1 or 2, 2^tb x 4, and 4 for tb itself as int32). */
+typedef struct kasa_index_pager kasa_index_pager;
+enum { KASA_INDEX_KEYS = 0, KASA_INDEX_TAXA = 1, KASA_INDEX_META = 2, KASA_INDEX_TABLE = 3, KASA_INDEX_TABLE_BITS = 4 };
+int kasa_index_pager_create(int device, uint64_t maxRecords, int recordBytes, uint32_t nSlots, const uint32_t *taxIds, uint32_t nTaxa,
+                            kasa_index_pager **out);
+int kasa_index_pager_load(kasa_index_pager *pager, uint32_t slot, uint64_t partitionId, const void *records, uint64_t nRecords,
+                          const uint32_t *triePrefix, const uint64_t *trieCount, uint64_t nTrie);
+int kasa_index_pager_index(kasa_index_pager *pager, uint32_t slot, const kasa_index **ix);
+int kasa_index_pager_stats(kasa_index_pager *pager, uint64_t out[8]);
+int kasa_index_pager_tile(uint32_t *tileRecords, uint32_t *ldsTaxa);
+int kasa_index_pager_destroy(kasa_index_pager *pager);
+int kasa_ctx_set_index(kasa_ctx *ctx, const kasa_index *ix);
+int kasa_batch_pool_keep(kasa_ctx *owner, const uint32_t *poolDev, uint64_t nPoolWords, const uint32_t **keptDev);
+int kasa_index_fetch(const kasa_index *ix, int what, void *out, uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ HOST_SRCS = [os.path.join(HERE, "csrc", "kasa_refbatch.cpp")]   # host-only part
 SO = os.path.join(HERE, "libkasa_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "kasa_hip.h")
 CSRC_HEADERS = [os.path.join(HERE, "csrc", "stdsort_order.h"), os.path.join(HERE, "csrc", "kasa_radix.h"), os.path.join(HERE, "csrc", "kasa_text.h"), os.path.join(HERE, "csrc", "kasa_replay.h"),
-                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_spill.h"), os.path.join(HERE, "csrc", "kasa_spill_plan.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h"), os.path.join(HERE, "csrc", "kasa_filter.h"),
+                os.path.join(HERE, "csrc", "kasa_build.h"), os.path.join(HERE, "csrc", "kasa_edit.h"), os.path.join(HERE, "csrc", "kasa_spill.h"), os.path.join(HERE, "csrc", "kasa_spill_plan.h"), os.path.join(HERE, "csrc", "kasa_parse.h"), os.path.join(HERE, "csrc", "kasa_bgzf.h"), os.path.join(HERE, "csrc", "kasa_inflate.h"), os.path.join(HERE, "csrc", "kasa_gunzip.h"), os.path.join(HERE, "csrc", "kasa_filter.h"), os.path.join(HERE, "csrc", "kasa_pager.h"),
                 os.path.join(HERE, "host", "grisu_powers.inc")]
 
 

@@ -45,6 +45,8 @@ EXPORTS = [
     "kasa_bgzf_inflate", "kasa_inflate_status_text", "kasa_gzip_inflate", "kasa_gzip_parse_append", "kasa_gzip_parse_status", "kasa_gzip_parse_ms", "kasa_bgzf_parse_append", "kasa_bgzf_parse_status", "kasa_bgzf_parse_ms",
     "kasa_ctx_row_classes", "kasa_ctx_hand_over_reasons", "kasa_ctx_row_merge_blocks", "kasa_ctx_keep_staged_lengths", "kasa_batch_staged_lengths",
     "kasa_pool_keep_records", "kasa_pool_fetch_records", "kasa_batch_filter", "kasa_batch_filter_fetch_range", "kasa_filter_split",
+    "kasa_index_pager_create", "kasa_index_pager_load", "kasa_index_pager_index", "kasa_index_pager_stats", "kasa_index_pager_tile", "kasa_index_pager_destroy",
+    "kasa_ctx_set_index", "kasa_batch_pool_keep", "kasa_index_fetch",
 ]
 
 
@@ -227,6 +229,15 @@ def lib():
         L.kasa_batch_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
         L.kasa_batch_filter_fetch_range.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64]
         L.kasa_filter_split.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.kasa_index_pager_create.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.kasa_index_pager_load.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.kasa_index_pager_index.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.kasa_index_pager_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_index_pager_tile.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_index_pager_destroy.argtypes = [C.c_void_p]
+        L.kasa_ctx_set_index.argtypes = [C.c_void_p, C.c_void_p]
+        L.kasa_batch_pool_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.kasa_index_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         _check_runtime(L)
         _lib = L
     return _lib
@@ -264,7 +275,9 @@ def codon_table_from_gcprt(path: str, table_id: str) -> np.ndarray:
 
 def _check(rc: int):
     if rc != 0:
-        raise RuntimeError(lib().kasa_last_error().decode("utf-8", "replace"))
+        e = RuntimeError(lib().kasa_last_error().decode("utf-8", "replace"))
+        e.code = int(rc)                                  # the status of include/kasa_hip.h (KASA_E_*)
+        raise e
 
 
 def _p(a):
@@ -539,9 +552,93 @@ class DeviceIndex:
     def device_bytes(self) -> int:
         return int(lib().kasa_index_device_bytes(self.h))
 
+    def fetch_arrays(self):
+        """Test tap (kasa_index_fetch): (keys u64[n] or KEY128_DTYPE[n], dense taxa u32[n], meta u8[n] or u16[n],
+        prefix table u32[2^tb], tb) as they lie on the device."""
+        from .formats import KEY128_DTYPE
+        tb = np.zeros(1, dtype=np.int32)
+        _check(lib().kasa_index_fetch(self.h, C.c_int(4), _p(tb), C.c_uint64(4)))
+        n = int(lib().kasa_index_size(self.h))
+        out = [np.zeros(n, dtype=KEY128_DTYPE if self.wide else np.uint64), np.zeros(n, dtype=np.uint32),
+               np.zeros(n, dtype=np.uint16 if self.wide else np.uint8), np.zeros(1 << int(tb[0]), dtype=np.uint32)]
+        for what, a in enumerate(out):
+            _check(lib().kasa_index_fetch(self.h, C.c_int(what), _p(a), C.c_uint64(a.nbytes)))
+        return out[0], out[1], out[2], out[3], int(tb[0])
+
     def close(self):
         if getattr(self, "h", None):
-            lib().kasa_index_destroy(self.h)
+            if not getattr(self, "borrowed", False):     # (a pager's slot is the pager's)
+                lib().kasa_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def index_records(ix, halved: bool = False) -> np.ndarray:
+    """The records of a formats.Index as they lie in its file: REC_DTYPE (12 bytes), REC128_DTYPE (20) or -- halved, 64-bit
+    indices only, nothing dropped -- HALF_DTYPE (6: low 30 bits and the dense taxon index; the `_trie` supplies the rest)."""
+    from .formats import REC_DTYPE, REC128_DTYPE, HALF_DTYPE, is_wide
+    if is_wide(ix.kmer):
+        rec = np.zeros(ix.n, dtype=REC128_DTYPE)
+        rec["lo"], rec["hi"], rec["tax"] = ix.kmer["lo"], ix.kmer["hi"], ix.taxid
+    elif halved:
+        rec = np.zeros(ix.n, dtype=HALF_DTYPE)
+        rec["low"], rec["tax"] = (ix.kmer & np.uint64(0x3FFFFFFF)).astype(np.uint32), ix.tax.astype(np.uint16)
+    else:
+        rec = np.zeros(ix.n, dtype=REC_DTYPE)
+        rec["kmer"], rec["tax"] = ix.kmer, ix.taxid
+    return rec
+
+
+def pager_tile():
+    """(records a workgroup of the pager's prepare kernel takes, most taxa whose table it searches in LDS)."""
+    t, m = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().kasa_index_pager_tile(C.byref(t), C.byref(m)))
+    return int(t.value), int(m.value)
+
+
+class IndexPager:
+    """Slots for the partitions of an index larger than device memory (kasa_index_pager_*): a partition is loaded into a
+    slot from host memory, the slot is an index a Context can be bound to (Context.set_index), and the next partition is
+    loaded into the same device memory once no context is bound to it."""
+
+    def __init__(self, max_records: int, record_bytes: int, taxids, slots: int = 2, device: int = 0):
+        ids = np.ascontiguousarray(taxids, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(lib().kasa_index_pager_create(C.c_int(device), C.c_uint64(max_records), C.c_int(record_bytes), C.c_uint32(slots), _p(ids),
+                                             C.c_uint32(ids.shape[0]), C.byref(h)))
+        self.h, self.device, self.n_taxa, self.record_bytes, self.slots = h, device, int(ids.shape[0]), record_bytes, slots
+
+    def load(self, slot: int, partition_id: int, records: np.ndarray, trie_prefix=None, trie_count=None, n_records: int = None):
+        """records: the partition as it lies in the file (a structured array of the pager's record size, or raw bytes)."""
+        records = np.ascontiguousarray(records)
+        n = records.nbytes // self.record_bytes if n_records is None else n_records
+        tp = np.ascontiguousarray(trie_prefix, dtype=np.uint32) if trie_prefix is not None else None
+        tc = np.ascontiguousarray(trie_count, dtype=np.uint64) if trie_count is not None else None
+        _check(lib().kasa_index_pager_load(self.h, C.c_uint32(slot), C.c_uint64(partition_id), _p(records), C.c_uint64(n), _p(tp), _p(tc),
+                                           C.c_uint64(0 if tp is None else tp.shape[0])))
+
+    def index(self, slot: int) -> "DeviceIndex":
+        """The slot as a DeviceIndex (borrowed: closing it releases nothing)."""
+        h = C.c_void_p()
+        _check(lib().kasa_index_pager_index(self.h, C.c_uint32(slot), C.byref(h)))
+        d = DeviceIndex.__new__(DeviceIndex)
+        d.h, d.device, d.n_taxa, d.n, d.wide, d.borrowed = h, self.device, self.n_taxa, int(lib().kasa_index_size(h)), self.record_bytes == 20, True
+        return d
+
+    def stats(self) -> dict:
+        s = np.zeros(8, dtype=np.uint64)
+        _check(lib().kasa_index_pager_stats(self.h, _p(s)))
+        return {"loads": int(s[0]), "hits": int(s[1]), "bytes": int(s[2]), "copy_us": int(s[3]), "prepare_us": int(s[4]), "refused": int(s[5]),
+                "device_bytes": int(s[6]), "lds_table": bool(s[7])}
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().kasa_index_pager_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -958,6 +1055,19 @@ class Context:
     def set_protein(self, protein: bool):
         """Amino-acid input for the next batches (kASA.hpp:155-183)."""
         _check(lib().kasa_ctx_set_protein(self.h, C.c_int(int(protein))))
+
+    def set_index(self, dix: DeviceIndex):
+        """The context works on another index of the same device, key width and taxa from its next batch on
+        (kasa_ctx_set_index); a pager's slot it was bound to is released."""
+        _check(lib().kasa_ctx_set_index(self.h, dix.h))
+        self.dix = dix
+
+    def pool_keep(self, pool_ptr: int, n_pool_words: int) -> int:
+        """The owner's own copy of a grouped slice's pool (device pointer), valid until records_import_device
+        (kasa_batch_pool_keep): the worker that made it goes on to the next slice."""
+        p = C.c_void_p(0)
+        _check(lib().kasa_batch_pool_keep(self.h, C.c_void_p(pool_ptr), C.c_uint64(n_pool_words), C.byref(p)))
+        return int(p.value or 0)
 
     def sort_and_range(self, unique: bool = False):
         _check(lib().kasa_batch_sort_and_range(self.h, C.c_int(int(unique))))

@@ -27,11 +27,13 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -424,6 +426,9 @@ struct kasa_index {
     DevBuf table;  // u32[2^tb]: number of entries whose top `tb` key bits are <= b
     int tb = 0;
     uint64_t bytes() const { return kmer.cap + tax.cap + meta.cap + table.cap; }
+    // a slot of an index pager (kasa_pager.h): the contexts bound to it -- the pager loads no other partition into it while
+    // this is not 0.  Shared with those contexts, so a context that outlives its pager releases nothing that is gone.
+    std::shared_ptr<std::atomic<int>> bound;
 };
 
 template <class Key>
@@ -688,6 +693,8 @@ struct StageTimer {
 
 struct kasa_ctx {
     const kasa_index *ix = nullptr;
+    std::shared_ptr<std::atomic<int>> bound;   // the pager slot's count this context is in (kasa_index::bound), if its index is one
+    std::vector<DevBuf> kept; size_t keptUsed = 0;   // kasa_batch_pool_keep: the slices' pools of this batch, one buffer each (their places do not move)
     int device = 0;
     int kHigh = 12, kLow = 7, nK = 6, frames = 3;
     bool protein = false;                      // amino-acid input (kasa_ctx_set_protein)
@@ -918,7 +925,8 @@ extern "C" int kasa_ctx_create(const kasa_index *ix, int kHigh, int kLow, int fr
     HIPCHK(hipSetDevice(ix->device));
     kasa_ctx *c = new (std::nothrow) kasa_ctx();
     if (!c) return fail(KASA_E_NOMEM, "host allocation failed");
-    c->ix = ix; c->device = ix->device; c->kHigh = kHigh; c->kLow = kLow; c->nK = kHigh - kLow + 1; c->frames = frames;
+    c->ix = ix; c->bound = ix->bound; if (c->bound) ++*c->bound;
+    c->device = ix->device; c->kHigh = kHigh; c->kLow = kLow; c->nK = kHigh - kLow + 1; c->frames = frames;
     auto bail = [&](int code) { kasa_ctx_destroy(c); return code; };
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(KASA_E_HIP, "hipStreamCreate failed"));
     uint8_t lut[366];
@@ -951,6 +959,8 @@ extern "C" void kasa_ctx_destroy(kasa_ctx *c)
     coh_forget(c);
     std::vector<DevBuf *> all = c->buffers();
     for (DevBuf *b : all) b->release();
+    for (DevBuf &b : c->kept) b.release();
+    if (c->bound) --*c->bound;
     auto drop = [](StageTimer &t) {
         for (auto &pr : t.open) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
         for (auto e : t.pool) (void)hipEventDestroy(e);
@@ -2387,6 +2397,7 @@ extern "C" int kasa_batch_sort_and_range(kasa_ctx *c, int unique)
 {
     if (!c) return fail(KASA_E_ARG, "ctx is NULL");
     if (c->state < 2) return fail(KASA_E_STATE, "kasa_batch_sort_and_range: batch not encoded");
+    c->keptUsed = 0;                                                      // the last batch's kept pools (kasa_batch_pool_keep) are gone
     return c->ix->wide ? sort_and_range_impl<key128>(c, unique) : sort_and_range_impl<uint64_t>(c, unique);
 }
 
@@ -9348,3 +9359,8 @@ extern "C" int kasa_ctx_synchronize(kasa_ctx *c)
 // ------------------------------------------------------------------------------------------------
 #include "kasa_parse.h"
 #include "kasa_filter.h"
+
+// ------------------------------------------------------------------------------------------------
+// pager: partitions of an index larger than device memory come and go in slots (kasa_index_pager_*)
+// ------------------------------------------------------------------------------------------------
+#include "kasa_pager.h"

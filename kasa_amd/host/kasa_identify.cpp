@@ -795,6 +795,8 @@ struct Params {
     bool deviceInflate = false;                    // --device-inflate (implies --device-parse): BGZF input goes up compressed and is inflated on the device (kasa_bgzf_parse_append)
     bool deviceFilter = false;                     // --device-filter (implies --device-parse, needs --filter): the two files of --filter are split on the device batch by batch (kasa_batch_filter)
     bool deviceFilterOn = false;                   // ... and this file's input takes that path (identifyFile decides)
+    bool pageIndex = false;                        // --page-index: the index stays on disk (mapped); its partitions come and go in two device slots per batch (kasa_index_pager_*)
+    uint64_t pageRecords = 1ull << 26;             // --page-records n: most records of a partition (not measured: the probe tools/page_probe.py is to settle it)
     bool devicePairs = false;                      // --device-pairs (implies --device-parse): paired-end input is parsed into two pools and paired on the device (kasa_pair_*)
 };
 
@@ -818,8 +820,17 @@ struct IndexFiles {                               // what Compare::ReadIndex loa
     vector<kasa_index *> spread;
     vector<int> spreadDev;
     size_t nPartitions() const { return spread.empty() ? (parts.empty() ? 0 : parts[0].size()) : spread.size(); }
+    // --page-index: no partition is resident.  The file stays mapped (pageMap); partition j = records [pageRec[j], pageRec[j + 1])
+    // and `_trie` entries [pageTrie[j], pageTrie[j + 1]), at most pageMax records; every device slot of a file's run has a pager
+    // of two slots over this one mapping (PagedIndex).  onDevice[d] = a resident index of the first `_trie` entry alone: an
+    // owner's context needs an index of its device for its key width and taxa.
+    bool paged = false;
+    const char *pageMap = nullptr; size_t pageMapBytes = 0;
+    vector<uint64_t> pageRec, pageTrie;
+    uint64_t pageMax = 0;
     ~IndexFiles()
     {
+        if (pageMap) munmap(const_cast<char *>(pageMap), pageMapBytes);
         if (!spread.empty()) { for (auto *ix : spread) kasa_index_destroy(ix); }
         else if (parts.empty()) { for (auto *ix : onDevice) kasa_index_destroy(ix); }
         else for (auto &v : parts) for (auto *ix : v) kasa_index_destroy(ix);
@@ -1165,6 +1176,7 @@ struct Batch {
     vector<uint32_t> segRead;                     // paired-end: read of every sequence
     vector<uint64_t> flagged;                     // --filter: read numbers of contaminants
     uint64_t kmers = 0;
+    vector<size_t> pageVisit;                     // --page-index: the partitions whose slice of this batch is not empty (--coherence visits them again)
     uint32_t flaggedByDevice = 0;                 // reads kasa_batch_rank handed back to the host's std::sort
     bool done = false;
     bool head = false, tail = false;              // read 0 goes on from the batch before / the last read goes on in the next batch (pieces, below)
@@ -2058,8 +2070,89 @@ struct FilterOut {
     }
 };
 
+// --page-index, one per device slot of a file's run: a pager of two slots over the mapped index file, ONE worker context that is
+// bound to the slot of the partition in turn, and a loader thread that brings the next partition up meanwhile (every call of
+// the library returns with its stream idle: the overlap is this thread's).  A partition that still sits in a slot is not
+// copied again (the pager counts a hit), so an index of at most two partitions goes up once per file.
+struct PagedIndex {
+    const IndexFiles &ixf; int device; kasa_index *stub;
+    kasa_index_pager *pager = nullptr;
+    kasa_ctx *worker = nullptr;
+    int64_t inSlot[2] = {-1, -1};                       // the partition a slot holds (or is being loaded with)
+    uint64_t visits = 0;
+    // the loader: one job at a time
+    std::thread thread; std::mutex mu; std::condition_variable cv;
+    bool quit = false, pending = false, busy = false; uint32_t jobSlot = 0; size_t jobPart = 0; int jobRc = 0; string jobErr;
+    PagedIndex(const Params &p, const IndexFiles &ixf, int device, kasa_index *stub) : ixf(ixf), device(device), stub(stub)
+    {
+        if (kasa_index_pager_create(device, ixf.pageMax, ixf.recBytes, 2, ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &pager)) throwLast();
+        if (kasa_ctx_create(stub, p.kHigh, p.kLow, p.frames, ixf.lut.empty() ? nullptr : ixf.lut.data(), &worker)) { const string m = kasa_last_error(); kasa_index_pager_destroy(pager); throw std::runtime_error(m); }
+        thread = std::thread([this] { run(); });
+    }
+    PagedIndex(const PagedIndex &) = delete;
+    ~PagedIndex()
+    {
+        { std::lock_guard<std::mutex> lk(mu); quit = true; }
+        cv.notify_all();
+        if (thread.joinable()) thread.join();
+        kasa_ctx_destroy(worker);
+        kasa_index_pager_destroy(pager);
+    }
+    void run()
+    {
+        (void)kasa_thread_device(device);              // (a fresh thread stands on device 0)
+        std::unique_lock<std::mutex> lk(mu);
+        for (;;) {
+            cv.wait(lk, [&] { return quit || pending; });
+            if (!pending) return;                       // (quit, and no job is left)
+            pending = false; busy = true;
+            const uint32_t s = jobSlot; const size_t j = jobPart;
+            lk.unlock();
+            const uint64_t r0 = ixf.pageRec[j], t0 = ixf.pageTrie[j];
+            const int rc = kasa_index_pager_load(pager, s, j, ixf.pageMap + r0 * (uint64_t)ixf.recBytes, ixf.pageRec[j + 1] - r0, ixf.tp.data() + t0, ixf.tc.data() + t0, ixf.pageTrie[j + 1] - t0);
+            const string err = rc ? kasa_last_error() : "";
+            lk.lock();
+            jobRc = rc; jobErr = err; busy = false;
+            cv.notify_all();
+        }
+    }
+    void fetch(uint32_t slot, size_t part)
+    {
+        { std::lock_guard<std::mutex> lk(mu); jobSlot = slot; jobPart = part; pending = true; }
+        inSlot[slot] = (int64_t)part;
+        cv.notify_all();
+    }
+    void fetched()
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !pending && !busy; });
+        if (jobRc) { const string m = jobErr; jobRc = 0; inSlot[0] = inSlot[1] = -1; throw std::runtime_error(m); }
+    }
+    // The partitions `visit` in order: step(j) runs with the worker bound to partition j while the loader fetches the next one
+    // into the other slot (the worker has left it: binding it to partition j released the slot of the partition before).
+    void sweep(const vector<size_t> &visit, const std::function<void(size_t)> &step)
+    {
+        if (visit.empty()) return;
+        auto slotOf = [&](size_t j, int other) { for (int s = 0; s < 2; ++s) if (inSlot[s] == (int64_t)j) return s; return other < 0 ? 0 : 1 - other; };
+        if (kasa_ctx_set_index(worker, stub)) throwLast();             // (the last sweep left the worker on a slot)
+        int s = slotOf(visit[0], -1);
+        fetch((uint32_t)s, visit[0]);
+        for (size_t i = 0; i < visit.size(); ++i) {
+            fetched();
+            ++visits;
+            const kasa_index *ix = nullptr;
+            if (kasa_index_pager_index(pager, (uint32_t)s, &ix)) throwLast();
+            if (kasa_ctx_set_index(worker, ix)) throwLast();
+            int sNext = -1;
+            if (i + 1 < visit.size()) { sNext = slotOf(visit[i + 1], s); fetch((uint32_t)sNext, visit[i + 1]); }
+            try { step(visit[i]); } catch (...) { try { fetched(); } catch (...) {} throw; }
+            s = sNext;
+        }
+    }
+};
+
 static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int ownerDev, const vector<kasa_ctx *> &partCtx, Batch &b, bool wantRows, double &tDevice, double &tText, WorkerBuffers &wb, OrderedOut &out,
-                     FilterOut *flt = nullptr)
+                     FilterOut *flt = nullptr, PagedIndex *paged = nullptr)
 {
     const auto tDev = std::chrono::steady_clock::now();
     auto secondsSince = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
@@ -2100,7 +2193,35 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
         { ScopedTimerMt t2(g_ht.encode, g_ht.mu); if (kasa_batch_encode(ctx, &nk)) throwLast(); }
         { ScopedTimerMt t2(g_ht.sort, g_ht.mu); if (kasa_batch_sort_and_range(ctx, p.unique ? 1 : 0)) throwLast(); }
         ScopedTimerMt t2(g_ht.score, g_ht.mu);
-        if (partCtx.empty()) { if (kasa_batch_lookup_score(ctx, wantRows, p.coverage)) throwLast(); }
+        if (paged) {
+            // --page-index: the slices as below, but the partitions come and go.  The partitions whose slice is not empty are
+            // visited in order; the one worker context groups every slice straight into its place of this batch's inbox, and a
+            // slice's pool moves into a buffer of the owner's, because the worker's own is overwritten by the next slice.  A
+            // partition with an empty slice is never loaded: the import gets no words for it.
+            const size_t nP = ixf.cuts.size();
+            const void *km = nullptr; uint64_t nq = 0;
+            if (kasa_batch_queries_device(ctx, &km, &nq)) throwLast();
+            vector<uint64_t> starts(nP + 1);
+            if (kasa_batch_slice_starts(ctx, ixf.cuts.data(), (uint32_t)nP, starts.data())) throwLast();
+            const size_t keyBytes = p.K > 12 ? 16 : 8, RW = (p.kHigh - p.kLow + 1) <= 8 ? 8 : 16;
+            vector<const uint32_t *> recs(nP, nullptr), pools(nP, nullptr); vector<uint64_t> nRecW(nP, 0), nPoolW(nP, 0);
+            uint32_t *inbox = nullptr;
+            if (kasa_batch_records_inbox(ctx, nq * RW, &inbox)) throwLast();
+            b.pageVisit.clear();
+            for (size_t j = 0; j < nP; ++j) if (starts[j + 1] > starts[j]) b.pageVisit.push_back(j);
+            paged->sweep(b.pageVisit, [&](size_t j) {
+                kasa_ctx *w = paged->worker;
+                if (kasa_batch_set_sorted_device(w, (const char *)km + starts[j] * keyBytes, starts[j + 1] - starts[j])) throwLast();
+                if (kasa_batch_group_to(w, p.coverage, inbox + starts[j] * RW)) throwLast();
+                if (kasa_profile_absorb(ctx, w)) throwLast();
+                if (kasa_batch_records_device(w, &recs[j], &nRecW[j], &pools[j], &nPoolW[j])) throwLast();
+                if (nPoolW[j] > 1) { if (kasa_batch_pool_keep(ctx, pools[j], nPoolW[j], &pools[j])) throwLast(); }
+                else { pools[j] = nullptr; nPoolW[j] = 0; }
+            });
+            if (kasa_batch_records_import_device(ctx, (uint32_t)nP, recs.data(), nRecW.data(), pools.data(), nPoolW.data())) throwLast();
+            if (kasa_batch_score(ctx, wantRows)) throwLast();
+        }
+        else if (partCtx.empty()) { if (kasa_batch_lookup_score(ctx, wantRows, p.coverage)) throwLast(); }
         else {
             // a partitioned index: the sorted queries are cut at the partitions' first prefixes; every slice is grouped against
             // its partition by that partition's context (the slice is a batch of its own there: its first query opens a new
@@ -2148,7 +2269,22 @@ static void runBatch(const Params &p, const IndexFiles &ixf, kasa_ctx *ctx, int 
         coherence.assign(nr, 0.f);
         uint64_t throwsAt = ~0ull;
         ScopedTimerMt tm(g_ht.coherence, g_ht.mu);
-        if (partCtx.empty()) { if (kasa_batch_coherence(ctx, coherence.data(), &throwsAt)) throwLast(); }
+        if (paged) {
+            // --page-index: a second sweep over the partitions the batch visited (one sweep for both is not attempted: the depth
+            // bytes need the emitted k-mers, which the grouped slices no longer are)
+            const size_t nP = ixf.cuts.size();
+            const void *km = nullptr; uint64_t ne = 0; uint8_t *depth = nullptr;
+            { ScopedTimerMt t2(g_ht.cohBegin, g_ht.mu); if (kasa_batch_coherence_begin(ctx, &km, &ne, &depth)) throwLast(); }
+            {
+                ScopedTimerMt t2(g_ht.cohDepth, g_ht.mu);
+                paged->sweep(b.pageVisit, [&](size_t j) {
+                    if (kasa_batch_match_depth_device(paged->worker, ixf.cuts[j], j + 1 < nP ? ixf.cuts[j + 1] : (uint64_t)1 << 30, km, ne, depth)) throwLast();
+                });
+            }
+            ScopedTimerMt t2(g_ht.cohFinish, g_ht.mu);
+            if (kasa_batch_coherence_finish(ctx, coherence.data(), &throwsAt)) throwLast();
+        }
+        else if (partCtx.empty()) { if (kasa_batch_coherence(ctx, coherence.data(), &throwsAt)) throwLast(); }
         else {
             // a partitioned index: only the partition that owns a k-mer's 6-letter prefix can give it a match length, so every
             // partition's context fills in the depths of its own prefix range and the walk runs here (kasa_hip.h)
@@ -2352,6 +2488,10 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                 if (kasa_ctx_create(ix, p.kHigh, p.kLow, p.frames, ixf.lut.empty() ? nullptr : ixf.lut.data(), &c)) throwLast();
                 partCtx[d].push_back(c);
             }
+    // --page-index: every device slot has its pager, worker context and loader over the one mapping (with several slots they
+    // run side by side; that was not measured)
+    vector<std::unique_ptr<PagedIndex>> paged(nDev);
+    if (ixf.paged) for (size_t d = 0; d < nDev; ++d) paged[d].reset(new PagedIndex(p, ixf, p.devices[(size_t)devSlots[d]], ixf.onDevice[(size_t)devSlots[d]]));
     // device batches: up to 2^32 k-mers, and what fits the HBM that is free next to the index
     uint64_t maxKmersPerBatch = 3000000000ull;
     {
@@ -2384,6 +2524,12 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
             }
             maxKmersPerBatch = std::max<uint64_t>(1u << 20, fit);
         }
+        if (per && ixf.paged) {
+            // --page-index: free memory is read with the pager made.  A query costs the owner's batch, its record in the inbox and
+            // ONE worker context, whose slice is at most the batch.
+            const uint64_t recBytes = (p.kHigh - p.kLow + 1) <= 8 ? 32 : 64;
+            maxKmersPerBatch = std::max<uint64_t>(1u << 20, std::min<uint64_t>(3000000000ull, (uint64_t)(0.8 * (double)freeB) / (2 * per + recBytes)));
+        }
         if (const char *e = getenv("KASA_MAX_BATCH_KMERS")) maxKmersPerBatch = std::max<uint64_t>(1, (uint64_t)atoll(e));   // tests: force several batches
     }
     mark("contexts made");
@@ -2413,6 +2559,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
     p.protein = batcher.protein;
     for (auto *c : ctx) if (kasa_ctx_set_protein(c, p.protein ? 1 : 0)) throwLast();
     for (auto &v : partCtx) for (auto *c : v) if (kasa_ctx_set_protein(c, p.protein ? 1 : 0)) throwLast();
+    for (auto &pg : paged) if (pg && kasa_ctx_set_protein(pg->worker, p.protein ? 1 : 0)) throwLast();
     if (wantRows && !p.hostRank && !p.hostText) {                     // what the device prints for a taxon (kasa_batch_text)
         vector<uint64_t> off(ixf.content.names.size() + 1, 0);
         string blob;
@@ -2471,7 +2618,7 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
                     if (fair) cvWork.notify_all();
                 }
                 mark("device takes batch", b->id);
-                runBatch(p, ixf, ctx[d], p.devices[(size_t)devSlots[d]], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out, flt.get());
+                runBatch(p, ixf, ctx[d], p.devices[(size_t)devSlots[d]], partCtx[d], *b, wantRows, tDevice[d], tText[d], wb, out, flt.get(), paged[d].get());
                 mark("device done with batch", b->id);
                 totalKmers += b->kmers;
                 b->rs = ReadSet();                                   // the reads are done with
@@ -2566,6 +2713,13 @@ static void identifyFile(Params p, const IndexFiles &ixf, const vector<int> &dev
         for (auto &c : comms) ncclCommDestroy(c);
         for (size_t d = 0; d < nDev; ++d) if (rcs[d]) throw std::runtime_error(msgs[d]);
     }
+    if (p.verbose)
+        for (size_t d = 0; d < nDev; ++d) if (paged[d]) {
+            uint64_t st[8] = {0};
+            if (kasa_index_pager_stats(paged[d]->pager, st)) throwLast();
+            std::cout << "OUT: Paged index on device " << paged[d]->device << ": " << ixf.cuts.size() << " partitions, " << nBatches << " batches, " << paged[d]->visits << " visits, " << st[0] << " loads, " << st[1]
+                      << " hits, " << (double)st[2] / 1e9 << " GB copied, copy " << (double)st[3] / 1e6 << " s, prepare " << (double)st[4] / 1e6 << " s" << std::endl;
+        }
     const int nK = p.kHigh - p.kLow + 1;
     vector<double> all((size_t)nK * ixf.content.names.size()); vector<uint64_t> uniq(all.size()), tot(all.size());
     if (kasa_profile_fetch(ctx[0], all.data(), uniq.data(), tot.data())) throwLast();
@@ -2694,6 +2848,8 @@ static vector<string> argsFromYaml(const string &exe, const string &file)
         else if (key == "DeviceFilter") flag("--device-filter", val);
         else if (key == "DeviceInflate") flag("--device-inflate", val);
         else if (key == "DeviceGunzip") flag("--device-gunzip", val);
+        else if (key == "PageIndex") flag("--page-index", val);                      // ours: the reference streams its index from disk by itself
+        else if (key == "PageRecords") opt("--page-records", val);
     }
     vector<string> out = {exe, mode};
     if (!kH.empty() && !kL.empty()) { out.push_back("-k"); out.push_back(kH); out.push_back(kL); }
@@ -3579,6 +3735,8 @@ static int run(int argc, char **argv)
         else if (s == "--device-inflate") p.deviceInflate = p.deviceParse = true;
         else if (s == "--device-gunzip") p.deviceGunzip = p.deviceInflate = p.deviceParse = true;
         else if (s == "--device-pairs") p.devicePairs = p.deviceParse = true;
+        else if (s == "--page-index") p.pageIndex = true;
+        else if (s == "--page-records") { const string v = next(); if (v.empty() || v.size() > 10 || v.find_first_not_of("0123456789") != string::npos || std::stoull(v) == 0 || std::stoull(v) >= 0xFFFFFFF0ull) throw std::runtime_error("--page-records needs a number of records between 1 and 2^32 - 17, not \"" + v + "\""); p.pageRecords = std::stoull(v); }
         else if (s == "--device-filter") p.deviceFilter = p.deviceParse = true;
         else if (s == "--allow-device-split") p.allowDeviceSplit = true;
         else if (s == "--filter") { p.filter = true; p.filterClean = next(); p.filterCont = next(); }
@@ -3594,6 +3752,7 @@ static int run(int argc, char **argv)
         else throw std::runtime_error("Some unknown parameter has been inserted, please check your command line.");
     }
     if (p.partitionDevices && p.devicesGiven) throw std::runtime_error("--partition-devices cannot be combined with --device or --devices: its slots are the devices of the run");
+    if (p.partitionDevices && p.pageIndex) throw std::runtime_error("--page-index cannot be combined with --partition-devices: a partition is either resident on its slot or paged through one device");
     if (p.bgzf && p.rtt.empty()) throw std::runtime_error("--bgzf compresses the per-read file: it needs -q <file>");
     if (p.deviceFilter && !p.filter) throw std::runtime_error("--device-filter splits the files of --filter: it needs --filter <clean> <contaminants>");
     if (frameFlags >= 2) throw std::runtime_error("You'll have to decide between using one, three, or six frames. Currently, more than one option was chosen. Please check your parameters!"); // main.cpp:618-620
@@ -3630,12 +3789,21 @@ static int run(int argc, char **argv)
     }
     uint64_t maxPart = 0xFFFFFFF0ull - 1;                               // what one index object holds (kasa_index_create)
     if (const char *e = getenv("KASA_INDEX_PART_RECORDS")) maxPart = std::max<uint64_t>(1, (uint64_t)atoll(e));   // tests: partitions of a small index
+    if (p.pageIndex) {
+        maxPart = p.pageRecords;
+        if (const char *e = getenv("KASA_INDEX_PAGE_RECORDS")) maxPart = std::min<uint64_t>(0xFFFFFFF0ull - 1, std::max<uint64_t>(1, (uint64_t)atoll(e)));   // tests: pages of a small index
+    }
+    // a resident index that does not fit: the message names the way out
+    auto created = [&](int rc) {
+        if (rc == KASA_E_NOMEM) throw std::runtime_error(string(kasa_last_error()) + " -- the index does not fit this device beside the batch buffers: --page-index keeps it on disk and pages it through the device");
+        if (rc) throwLast();
+    };
     const size_t nSlots = p.partitionDevices ? p.devices.size() : 0;
-    if (ixf.nRec <= maxPart && !p.partitionDevices) {
+    if (ixf.nRec <= maxPart && !p.partitionDevices && !p.pageIndex) {
         for (int dev : p.devices) {
             kasa_index *ix = nullptr;
-            if (kasa_index_create(dev, rec, ixf.nRec, ixf.recBytes, ixf.tp.data(), ixf.tc.data(), ixf.tp.size(), ixf.content.taxids.data(),
-                                  (uint32_t)ixf.content.taxids.size(), &ix)) throwLast();
+            created(kasa_index_create(dev, rec, ixf.nRec, ixf.recBytes, ixf.tp.data(), ixf.tc.data(), ixf.tp.size(), ixf.content.taxids.data(),
+                                      (uint32_t)ixf.content.taxids.size(), &ix));
             ixf.onDevice.push_back(ix);
         }
     } else {
@@ -3660,14 +3828,24 @@ static int run(int argc, char **argv)
             if (nParts >= m) throw std::runtime_error("the index cannot be cut into partitions of at most " + std::to_string(maxPart) + " records between its trie entries");
         }
         for (uint64_t j = 0; j < nParts; ++j) ixf.cuts.push_back(j == 0 ? 0 : (uint64_t)ixf.tp[tLo[j]]);
-        if (nSlots) {
+        if (p.pageIndex) {
+            ixf.paged = true; ixf.pageMap = (const char *)rec; ixf.pageMapBytes = ixf.nRec * ixf.recBytes;
+            ixf.pageRec = rLo; ixf.pageTrie = tLo;
+            for (uint64_t j = 0; j < nParts; ++j) ixf.pageMax = std::max(ixf.pageMax, rLo[j + 1] - rLo[j]);
+            for (int dev : p.devices) {
+                kasa_index *ix = nullptr;
+                created(kasa_index_create(dev, rec, ixf.tc[0], ixf.recBytes, ixf.tp.data(), ixf.tc.data(), 1, ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix));
+                ixf.onDevice.push_back(ix);
+            }
+            if (p.verbose) std::cout << "OUT: Index of " << ixf.nRec << " records paged in " << nParts << " partitions of at most " << ixf.pageMax << " records" << std::endl;
+        } else if (nSlots) {
             // partition j lives on slot j * nSlots / nParts: contiguous runs, every partition created once
             ixf.onDevice.assign(nSlots, nullptr);
             for (uint64_t j = 0; j < nParts; ++j) {
                 const size_t slot = (size_t)(j * nSlots / nParts);
                 kasa_index *ix = nullptr;
-                if (kasa_index_create(p.devices[slot], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
-                                      tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix)) throwLast();
+                created(kasa_index_create(p.devices[slot], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
+                                          tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix));
                 ixf.spread.push_back(ix); ixf.spreadDev.push_back(p.devices[slot]);
                 if (!ixf.onDevice[slot]) ixf.onDevice[slot] = ix;
             }
@@ -3681,8 +3859,8 @@ static int run(int argc, char **argv)
             for (size_t d = 0; d < p.devices.size(); ++d) {
                 for (uint64_t j = 0; j < nParts; ++j) {
                     kasa_index *ix = nullptr;
-                    if (kasa_index_create(p.devices[d], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
-                                          tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix)) throwLast();
+                    created(kasa_index_create(p.devices[d], (const char *)rec + rLo[j] * (uint64_t)ixf.recBytes, rLo[j + 1] - rLo[j], ixf.recBytes, ixf.tp.data() + tLo[j], ixf.tc.data() + tLo[j],
+                                              tLo[j + 1] - tLo[j], ixf.content.taxids.data(), (uint32_t)ixf.content.taxids.size(), &ix));
                     ixf.parts[d].push_back(ix);
                 }
                 ixf.onDevice.push_back(ixf.parts[d][0]);
@@ -3690,7 +3868,8 @@ static int run(int argc, char **argv)
             if (p.verbose) std::cout << "OUT: Index of " << ixf.nRec << " records in " << nParts << " partitions on every device" << std::endl;
         }
     }
-    munmap(rec, ixf.nRec * ixf.recBytes); close(fd);
+    if (!ixf.paged) munmap(rec, ixf.nRec * ixf.recBytes);               // (--page-index: the mapping is the index for the whole run)
+    close(fd);
     if (p.threads == 0) {
         // all CPUs this process may really use: the machine's, capped by a cgroup CPU quota (a container that sees 256 CPUs
         // and is throttled to 16 runs slower with 128 threads than with 16)

@@ -195,6 +195,89 @@ class LocalExchange:
             d.close()
 
 
+class PagedExchange:
+    """The partitions of an index that does not fit the device, on ONE device: they come and go in the slots of a
+    capi.IndexPager, ONE worker context is bound to the slot that holds the partition of the slice in turn
+    (kasa_ctx_set_index), the records go straight into the owner's inbox and a slice's pool into a buffer of the owner's
+    (kasa_batch_pool_keep), because the worker's own is overwritten by the next slice.  A partition whose slice is empty
+    is not loaded; one that still sits in a slot is not loaded again.  Sequential: loading partition j + 1 while partition j is
+    grouped is the driver's business (`kasa_identify identify --page-index`).  Interface of LocalExchange."""
+
+    def __init__(self, parts, cuts, k_high=12, k_low=7, frames=3, device: int = 0, slots: int = 2, halved: bool = False):
+        """parts: formats.Index objects (host memory), cuts as split_index gives them.  halved: the partitions go up in the 6-byte
+        form of `shrink -s 2` (64-bit indices)."""
+        self.cuts, self.parts, self.halved = cuts, list(parts), halved
+        self.K = parts[0].K
+        self.records = [capi.index_records(p, halved) for p in parts]
+        ids = parts[0].content.taxids
+        self.pager = capi.IndexPager(max(p.n for p in parts), self.records[0].dtype.itemsize, ids, slots=slots, device=device)
+        self.slot_of, self.next_slot = {}, 0                       # partition -> slot it sits in; the slot the next load takes
+        # the owner needs an index only for its key width and taxa: the first `_trie` entry of the first partition, resident
+        p0, c0 = parts[0], int(parts[0].trie_count[0])
+        stub = formats.Index(p0.kmer[:c0], p0.taxid[:c0], p0.tax[:c0], p0.trie_prefix[:1], p0.trie_count[:1], p0.content, p0.freq)
+        self.stub = capi.DeviceIndex(stub, device)
+        self.owner = capi.Context(self.stub, k_high, k_low, frames)
+        self.worker = capi.Context(self.stub, k_high, k_low, frames)
+        self.loaded = []                                           # of the last batch: the partitions visited, in order
+
+    def _bind(self, j: int):
+        """Partition j into a slot (round robin; a hit costs nothing) and the worker onto that slot."""
+        slot = self.slot_of.get(j)
+        if slot is None:
+            slot = self.next_slot
+            self.next_slot = (slot + 1) % self.pager.slots
+            if getattr(self.worker.dix, "slot", None) == slot:
+                self.worker.set_index(self.stub)                   # release the slot the worker still sits on
+            self.slot_of = {p: s for p, s in self.slot_of.items() if s != slot}
+        p = self.parts[j]
+        self.pager.load(slot, j, self.records[j], p.trie_prefix, p.trie_count)
+        self.slot_of[j] = slot
+        dix = self.pager.index(slot)
+        dix.slot = slot
+        self.worker.set_index(dix)
+
+    def run_batch(self, batch, want_per_read=True, unique=False):
+        ctx, w = self.owner, self.worker
+        ctx.upload(batch.bases, batch.offsets, batch.seg_read, batch.n if batch.seg_read is not None else None)
+        ctx.encode()
+        ctx.sort_and_range(unique)
+        rw = ctx.rec_words
+        ptr, n, kb = ctx.queries_device()
+        starts = ctx.slice_starts(self.cuts)
+        inbox, parts = ctx.records_inbox(n * rw), []
+        self.loaded = []
+        for j in range(len(self.parts)):
+            at, nq = int(starts[j]), int(starts[j + 1] - starts[j])
+            if nq == 0:
+                parts.append((0, 0, 0, 0))                         # never loaded: an empty slice
+                continue
+            self._bind(j)
+            self.loaded.append(j)
+            w.set_sorted_device(ptr + at * kb, nq)
+            w.group_to(inbox + at * rw * 4)
+            ctx.profile_absorb(w)
+            rp, nrw, pp, npw = w.records_device()
+            parts.append((rp, nrw, ctx.pool_keep(pp, npw) if npw > 1 else 0, npw if npw > 1 else 0))
+        ctx.records_import_device(parts)
+        ctx.score(want_per_read)
+        return ctx
+
+    def coherence(self) -> np.ndarray:
+        """--coherence scores of the batch run_batch has just scored: a second sweep over the partitions it visited."""
+        ptr, n, depth = self.owner.coherence_begin()
+        ends = [int(c) for c in self.cuts[1:]] + [1 << (5 * formats.TRIE_LETTERS)]
+        for j in self.loaded:
+            self._bind(j)
+            self.worker.match_depth_device(int(self.cuts[j]), ends[j], ptr, n, depth)
+        return self.owner.coherence_finish()
+
+    def close(self):
+        self.owner.close()
+        self.worker.close()
+        self.pager.close()
+        self.stub.close()
+
+
 # ---- the wire format of exported records (kasa_batch_records_pack / _unpack in the C ABI; this is its statement in numpy, used
 # by the host-staged exchange and as the cross-check of the device kernels): one byte of classes per four records (2 bits
 # each: 0 = unmatched; 1, 2, 3 = words [1 .. n] of the record, n = 4 / 6 / 7 for 8-word records (at most one / at most three /
